@@ -10,6 +10,10 @@ N > 1: one process per GPU (torch.distributed, backend nccl = RCCL), loci sharde
 total work fixed (strong scaling, as the metric is quoted on 10M loci in total).
 
 Prints ONE JSON line on rank 0.
+
+A plain run does the headline only: set up, warm up, time --steps steps, write the last step's outputs if --dump-outputs DIR is
+given, print the line.  --full adds the untimed legs after the headline region (sweep legs, lazy kinship, shard probe,
+end-to-end, BASELINE configs[1] / configs[3], CPU baseline); their --no-* switches select among them.
 """
 from __future__ import annotations
 
@@ -315,7 +319,51 @@ def parse_args(argv=None):
     ap.add_argument("--e2e-loci", type=int, default=4_000_000, help="loci of the end-to-end leg (6.4 GB of pinned host memory at 200 pools)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="seconds the self-launching parent of --gpus N > 1 waits for its rank processes before it kills them")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs after the headline region (sweep legs, lazy kinship, shard probe, end-to-end, "
+                         "BASELINE configs[1] / configs[3], CPU baseline); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (beta, var, pval of a fixed sample of loci, n_eigenvecs) "
+                         "as DIR/<name>.npy in float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE_LOCI = 1 << 20   # at most 4 arrays x 8 MB in --dump-outputs
+DUMP_SEED = 20251003
+
+
+def dump_sample(p_total: int):
+    """Global locus indices --dump-outputs writes: every locus up to DUMP_SAMPLE_LOCI, else a fixed seeded sample (sorted)."""
+    import numpy as np
+    if p_total <= DUMP_SAMPLE_LOCI:
+        return np.arange(p_total, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.choice(p_total, size=DUMP_SAMPLE_LOCI, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, out, m, lo, hi, p_total, rank, use_dist, dist, torch, np):
+    """The last timed step's results as the caller received them ((beta, var, pval) = out[0..2], shape (p_local, k)), sampled at
+    dump_sample(p_total) and gathered on rank 0, which writes DIR/{locus_index,beta,var,pval,n_eigenvecs}.npy (float64)."""
+    idx = dump_sample(p_total)
+    mine = idx[(idx >= lo) & (idx < hi)]
+    vals = out[:, torch.as_tensor(mine - lo, device=out.device)].cpu().numpy()   # (3, s_local, k)
+    parts = [(mine, vals)]
+    if use_dist:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (mine, vals))
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    got = np.concatenate([p[0] for p in parts])
+    vals = np.concatenate([p[1] for p in parts], axis=1)
+    assert np.array_equal(got, idx), "the ranks' shards do not cover the sample"
+    arrays = {"locus_index": idx.astype(np.float64), "beta": vals[0], "var": vals[1], "pval": vals[2],
+              "n_eigenvecs": np.array([m], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 class _StdoutToStderr:
@@ -559,14 +607,18 @@ def worker(args):
     red_ms, red_n = eng.profile_get("kinship_reduce")
     sw_ms, sw_n = eng.profile_get("sweep")
     fin_ms, fin_n = eng.profile_get("sweep_finish")
+    # `out` still holds the last timed step's results: the legs below reuse it
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, m, lo, hi, p_total, rank, use_dist, dist, torch, np)
 
-    # ---- after the timed region: the general path, so that the per-locus sweep (north_star's HBM-roofline kernel) has a
+    # ---- after the timed region (--full only): the general path, so that the per-locus sweep (north_star's HBM-roofline kernel) has a
     # driver-run number too.  At the default -x 0.75 the eigen rule gives m = 0 and the fits are closed from sums fused into
     # the kinship pass: the sweep kernel (k_ols_sweep_mfma) is never launched by the headline.  Two extra legs of `extra` steps each:
     #   two_pass : same analysis with the fusion off -> kinship (no fused sums) + k_ols_sweep_mfma with [1 | g]   (m = 0)
     #   m8       : --force-m 8 -> host eigenvectors + k_ols_sweep_mfma with [1 | C(8) | g]                      (m = 8)
     legs = {}
-    extra = 0 if args.no_sweep_legs else args.sweep_steps
+    full = args.full
+    extra = 0 if args.no_sweep_legs or not full else args.sweep_steps
     if extra > 0 and args.force_m < 0:
         for tag, fm, env in (("two_pass", -1, "1"), ("m8", 8, None)):
             old = os.environ.get("POOLGEN_TWO_PASS")
@@ -625,14 +677,14 @@ def worker(args):
             lazy = {"error": f"{type(e).__name__}: {e}"}
     # ---- rank-shaped probe and the PCIe-inclusive leg: after the timed region, 1 GPU only, bounded ----
     shard_probe = None
-    if world == 1 and not args.no_shard_probe and args.force_m < 0:
+    if full and world == 1 and not args.no_shard_probe and args.force_m < 0:
         shard_probe = shard_probe_legs(eng, G, Y, n, p_total, args.var_explained, args.probe_steps, torch, np)
     end_to_end = None
-    if world == 1 and not args.no_end_to_end and args.force_m < 0:
+    if full and world == 1 and not args.no_end_to_end and args.force_m < 0:
         end_to_end = end_to_end_leg(eng, G, Y, n, args.e2e_loci, args.var_explained, torch, np)
     # ---- BASELINE configs[1] and configs[3], driver-visible: after the timed region, bounded, 1 GPU only ----
     secondary = None
-    if world == 1 and not args.no_secondary and args.force_m < 0:
+    if full and world == 1 and not args.no_secondary and args.force_m < 0:
         secondary = secondary_legs(eng, dev, args, torch, np)
     eng.profile(False)
 
@@ -710,7 +762,7 @@ def worker(args):
                 "k_ols_sweep_mfma": ({"avg_ms": sw_avg, "gbs_algorithmic": sweep_bytes / (sw_avg * 1e-3) / 1e9,
                                  "frac_of_hbm_peak": sweep_bytes / (sw_avg * 1e-3) / 1e9 / HBM_PEAK_GBS} if sw_n else
                                 {"avg_ms": 0.0, "note": "not launched by the headline: m = 0 fits closed from the sums fused into the "
-                                                        "kinship pass; see roofline_sweep for the general path"}),
+                                                        "kinship pass; see roofline_sweep (--full) for the general path"}),
                 "k_sweep_finish": {"avg_ms": fin_ms / max(fin_n, 1), "launches": fin_n},
                 "host_eig_and_glue_ms": ms_per_step - kin_avg - sw_avg - red_ms / max(red_n, 1) - fin_ms / max(fin_n, 1),
             },
@@ -742,7 +794,7 @@ def worker(args):
             rec["secondary"] = secondary
         if lazy:
             rec.setdefault("secondary", {"what": "untimed legs after the headline region"})["lazy_kinship"] = lazy
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             s = min(args.cpu_sample, p_local)
             rec["cpu_baseline"] = cpu_baseline(G[:s, :n].cpu().numpy(), Y, args.var_explained, args.force_m)
         print(json.dumps(rec))

@@ -63,3 +63,33 @@ def test_rank_gate_go_or_abort_together():
     assert gate(4, 2, 3) == "entered 0 own 1 aborted 3 finished 0"
     assert gate(8, 0, 1) == "entered 0 own 1 aborted 7 finished 0"
     assert gate(2, 1, 50) == "entered 0 own 1 aborted 1 finished 0"
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("poolgen_bench", ROOT / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_plain_and_full_options():
+    bench = _bench_module()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, cwd=ROOT,
+                       env=_clean_env(), timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    import numpy as np
+    bench = _bench_module()
+    assert np.array_equal(bench.dump_sample(1000), np.arange(1000))
+    s = bench.dump_sample(10_000_000)
+    assert np.array_equal(s, bench.dump_sample(10_000_000))
+    assert s.shape == (bench.DUMP_SAMPLE_LOCI,) and np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < 10_000_000
+    # locus_index + beta + var + pval (one trait) + n_eigenvecs, float64
+    assert (4 * bench.DUMP_SAMPLE_LOCI + 1) * 8 <= 64 << 20

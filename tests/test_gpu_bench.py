@@ -8,6 +8,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def last_json(out: str):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--loci", "1000000",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--loci", "1000000",
                         "--cpu-sample", "20000", "--e2e-loci", "400000", "--probe-steps", "3", "--secondary-loci", "100000",
                         "--ridge-loci", "100000"], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -56,7 +57,7 @@ def test_two_rank_control_flow_rehearsal():
     env = dict(os.environ, POOLGEN_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29533", str(ROOT / "bench.py"), "--gpus", "2",
-                        "--steps", "2", "--warmup", "1", "--loci", "1000001", "--no-cpu-baseline"],
+                        "--full", "--steps", "2", "--warmup", "1", "--loci", "1000001", "--no-cpu-baseline"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
@@ -78,7 +79,7 @@ def test_self_launched_two_ranks_rehearsal():
     """`python bench.py --gpus 2` exactly as the driver starts it -- no launcher, no WORLD_SIZE: bench.py starts its own two rank
     processes (the parent never touches the GPU), and prints ONE line with n_gpus = 2.  On this 1-GPU box the two ranks share
     cuda:0 over gloo (POOLGEN_BENCH_BACKEND=gloo, the rehearsal switch; the line says so)."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--loci", "1000001",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--loci", "1000001",
                         "--no-cpu-baseline", "--sweep-steps", "1"], capture_output=True, text=True, cwd=ROOT,
                        env=_no_launcher_env(POOLGEN_BENCH_BACKEND="gloo"), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -98,8 +99,8 @@ def test_self_launch_refuses_more_ranks_than_gpus():
 
 
 def test_secondary_legs_in_the_line():
-    """BASELINE configs[1] and configs[3] are part of the driver-run line (reduced sizes here; the default run uses 1M / 5M)."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--loci", "500000", "--no-cpu-baseline",
+    """BASELINE configs[1] and configs[3] are part of the --full line (reduced sizes here; the default run uses 1M / 5M)."""
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--loci", "500000", "--no-cpu-baseline",
                         "--sweep-steps", "1", "--secondary-loci", "200000", "--ridge-loci", "200000"], capture_output=True, text=True,
                        cwd=ROOT, env=_no_launcher_env(), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -132,10 +133,54 @@ def test_one_rank_through_the_real_rccl_path():
     process group of one rank, the library's own communicator set up through it (pg_comm_init_rank with the id carried by
     torch.distributed), the kinship all-reduce inside libpoolgen_hip, barriers and max-over-ranks timing."""
     env = dict(os.environ, POOLGEN_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29537", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--loci", "2000000",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--loci", "2000000",
                         "--no-cpu-baseline", "--sweep-steps", "1"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
     assert d["n_gpus"] == 1 and d["config"]["allreduce"].startswith("RCCL inside libpoolgen_hip"), d["config"]
     assert d["config"]["comm_size"] == 1 and d["config"]["rccl_version"] >= 20000
     assert d["value"] > 0 and "roofline_sweep" in d and d["roofline_sweep"]["two_pass"]["launches"] == 1
+
+
+DUMPED = ("locus_index", "beta", "var", "pval", "n_eigenvecs")
+
+
+def _dumped(path):
+    return {name: np.load(path / f"{name}.npy") for name in DUMPED}
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run is the headline alone (no untimed legs), --steps sets the timed steps, and --dump-outputs writes the last
+    step's results of a fixed sample of loci: identical inputs from run to run, and the same results from two ranks (gloo
+    rehearsal on one GPU) as from one."""
+    loci = 1_100_000      # > the 2^20 loci written: a sample
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--loci", str(loci)]
+    lines = []
+    for tag in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(last_json(r.stdout))
+    d = lines[0]
+    assert NEED <= set(d) and d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - loci / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for leg in ("cpu_baseline", "secondary", "shard_probe", "end_to_end", "roofline_sweep"):
+        assert leg not in d, leg
+    a, b = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    idx = a["locus_index"]
+    assert idx.shape == (1 << 20,) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < loci
+    assert a["n_eigenvecs"][0] == d["config"]["n_eigenvecs"]
+    for name in DUMPED:
+        assert a[name].dtype == np.float64
+        assert np.array_equal(a[name], b[name], equal_nan=True), name
+    for name in ("beta", "var", "pval"):
+        assert a[name].shape == (1 << 20, 1) and np.isfinite(a[name]).mean() > 0.99
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--loci", str(loci),
+                        "--dump-outputs", str(tmp_path / "two")], capture_output=True, text=True, cwd=ROOT,
+                       env=_no_launcher_env(POOLGEN_BENCH_BACKEND="gloo"), timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert last_json(r.stdout)["n_gpus"] == 2
+    two = _dumped(tmp_path / "two")
+    assert np.array_equal(two["locus_index"], idx) and two["n_eigenvecs"][0] == a["n_eigenvecs"][0]
+    for name in ("beta", "var", "pval"):
+        assert np.allclose(two[name], a[name], rtol=1e-9, atol=0, equal_nan=True), name

@@ -1,26 +1,27 @@
 #!/bin/bash
-# Round-3 evidence for the bench line, all from ONE command line (python3 bench.py [flags]) on one MI355X box:
-#   1. the bench JSON itself                                   -> gpurun_out/${TAG}_bench.json
-#   2. rocprofv3 --kernel-trace --stats of the same command    -> gpurun_out/${TAG}_kernel_stats.csv (our kernels' rows)
+# Round-3 evidence for the bench line, all from ONE command line (python3 bench.py --full [flags]) on one MI355X box:
+#   1. the bench JSON itself                                   -> $OUT/${TAG}_bench.json
+#   2. rocprofv3 --kernel-trace --stats of the same command    -> $OUT/${TAG}_kernel_stats.csv (our kernels' rows)
 #   3. rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | MFMA busy), one counter group per pass, --kernel-trace only
-#                                                             -> gpurun_out/${TAG}_pmc_summary.txt, gpurun_out/${TAG}_pmc_traffic.json
+#                                                             -> $OUT/${TAG}_pmc_summary.txt, $OUT/${TAG}_pmc_traffic.json
 # Copy the four files into profiles/ afterwards (profiles/pmc_traffic.json is what bench.py reads for `traffic`; it carries the
 # hash of the kernel sources it was measured on, and bench.py says "stale" when the sources have changed since).
 # New against r02_profile.sh: the two sweep legs (m = 0 two-pass, forced m = 8) are told apart by dispatch order instead of
 # sharing one per-kernel mean, and the secondary legs (count operators, ridge passes) are in the same passes.
 # The bench JSON is taken LAST, with the fresh counter file already in place, so that its `traffic` fields are this box's own.
-# usage: tools/r03_profile.sh [tag]   (files gpurun_out/<tag>_*; default r03_b)
+# usage: tools/r03_profile.sh [tag]   (files $OUT/<tag>_*; default r03_b)
 TAG=${1:-r03_b}; export TAG
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+OUT=${OUT:-profile_out}; export OUT
+mkdir -p "$OUT"
 # ... and once FIRST, on the box as it comes: after six minutes of profiling passes the memory-bound kernels of the same box run
 # 8-10 % slower (sweep 2.97 against 2.71 ms under rocprof minutes earlier: r03_d / r03_e of round 3).  The early line is the one
 # kept when the committed counter file already belongs to these sources (its `traffic` is then fresh as well).
-python3 bench.py > gpurun_out/${TAG}_bench_first.json 2> gpurun_out/${TAG}_bench_first.err; echo "first bench rc=$?"
-rm -rf gpurun_out/${TAG}_prof && mkdir -p gpurun_out/${TAG}_prof
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_prof -- python3 bench.py --no-cpu-baseline > gpurun_out/${TAG}_prof.log 2>&1; echo "rocprof rc=$?"
-f=$(find gpurun_out/${TAG}_prof -name "*kernel_stats.csv" | head -1)
-python3 - "$f" > gpurun_out/${TAG}_kernel_stats.csv <<'PY'
+python3 bench.py --full > $OUT/${TAG}_bench_first.json 2> $OUT/${TAG}_bench_first.err; echo "first bench rc=$?"
+rm -rf $OUT/${TAG}_prof && mkdir -p $OUT/${TAG}_prof
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -- python3 bench.py --full --no-cpu-baseline > $OUT/${TAG}_prof.log 2>&1; echo "rocprof rc=$?"
+f=$(find $OUT/${TAG}_prof -name "*kernel_stats.csv" | head -1)
+python3 - "$f" > $OUT/${TAG}_kernel_stats.csv <<'PY'
 import csv, sys
 rows = list(csv.reader(open(sys.argv[1])))
 w = csv.writer(sys.stdout)
@@ -30,17 +31,17 @@ for r in rows[1:]:
         r[0] = r[0].replace("(anonymous namespace)::", "")
         w.writerow(r)
 PY
-cut -c1-150 gpurun_out/${TAG}_kernel_stats.csv
-rm -rf gpurun_out/${TAG}_prof
-: > gpurun_out/${TAG}_pmc_summary.txt
+cut -c1-150 $OUT/${TAG}_kernel_stats.csv
+rm -rf $OUT/${TAG}_prof
+: > $OUT/${TAG}_pmc_summary.txt
 i=0
 for ctrs in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  rm -rf gpurun_out/${TAG}_pmc_$i && mkdir -p gpurun_out/${TAG}_pmc_$i
-  timeout -k 10 500 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d gpurun_out/${TAG}_pmc_$i -- python3 bench.py --steps 3 --warmup 1 --sweep-steps 2 --no-cpu-baseline > gpurun_out/${TAG}_pmc_$i.log 2>&1
+  rm -rf $OUT/${TAG}_pmc_$i && mkdir -p $OUT/${TAG}_pmc_$i
+  timeout -k 10 500 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_$i -- python3 bench.py --full --steps 3 --warmup 1 --sweep-steps 2 --no-cpu-baseline > $OUT/${TAG}_pmc_$i.log 2>&1
   echo "pmc pass $i ($ctrs) rc=$?"
-  f=$(find gpurun_out/${TAG}_pmc_$i -name "*counter_collection.csv" | head -1)
-  python3 - "$f" >> gpurun_out/${TAG}_pmc_summary.txt <<'PY'
+  f=$(find $OUT/${TAG}_pmc_$i -name "*counter_collection.csv" | head -1)
+  python3 - "$f" >> $OUT/${TAG}_pmc_summary.txt <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r.get("Dispatch_Id", 0)))
@@ -58,15 +59,16 @@ for k, d in sorted(acc.items()):
             print(f"{(k + ' [leg two_pass]')[:44]:44s} {c:28s} n={h:3d} mean={sum(v[:h])/h:.6g}")
             print(f"{(k + ' [leg m8]')[:44]:44s} {c:28s} n={h:3d} mean={sum(v[h:])/h:.6g}")
 PY
-  rm -rf gpurun_out/${TAG}_pmc_$i
+  rm -rf $OUT/${TAG}_pmc_$i
 done
 python3 - <<'PY'
 import hashlib, json, re
+import os; OUT = os.environ["OUT"]
 from pathlib import Path
 vals = {}
 import os
 TAG = os.environ["TAG"]
-for line in open(f"gpurun_out/{TAG}_pmc_summary.txt"):
+for line in open(f"{OUT}/{TAG}_pmc_summary.txt"):
     m = re.match(r"(.{44})\s(\S+)\s+n=\s*(\d+)\s+mean=(\S+)", line)
     if m: vals[(m.group(1).strip(), m.group(2))] = float(m.group(4))
 def find(prefix, ctr):
@@ -79,7 +81,7 @@ def hbm(prefix):  # gfx950: FETCH_SIZE (KiB) counts half of a wide streaming rea
 src = hashlib.sha256()
 for p in sorted(list(Path("poolgen_amd/csrc").glob("*.hip")) + list(Path("poolgen_amd/csrc").glob("*.h"))):
     src.update(p.read_bytes())
-out = {"_comment": "HBM bytes per launch from rocprofv3 --pmc passes of `python3 bench.py --steps 3 --warmup 1 --sweep-steps 2 --no-cpu-baseline` "
+out = {"_comment": "HBM bytes per launch from rocprofv3 --pmc passes of `python3 bench.py --full --steps 3 --warmup 1 --sweep-steps 2 --no-cpu-baseline` "
                    "(tools/r03_profile.sh; per-kernel means in the `source` file): (2 * FETCH_SIZE + WRITE_SIZE) * 1024, the factor 2 being the "
                    "gfx950 wide-read correction of MI355X_MICROARCH.md.  The sweep legs are separated by dispatch order.",
        "source": f"profiles/{TAG}_pmc_summary.txt", "workload": "200x10000000", "kernel_sources_sha256": src.hexdigest(),
@@ -93,20 +95,21 @@ out = {"_comment": "HBM bytes per launch from rocprofv3 --pmc passes of `python3
        "ridge_predict_hbm_bytes_per_launch": hbm("k_gp_predict_folds")}
 mf, ga = find("k_kinship_syrk<true, true, 3", "SQ_VALU_MFMA_BUSY_CYCLES"), find("k_kinship_syrk<true, true, 3", "GRBM_GUI_ACTIVE")
 if mf and ga: out["kinship_mfma_busy_frac"] = mf / 1024.0 / (ga / 8.0)
-json.dump(out, open(f"gpurun_out/{TAG}_pmc_traffic.json", "w"), indent=1)
+json.dump(out, open(f"{OUT}/{TAG}_pmc_traffic.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
 PY
-cp gpurun_out/${TAG}_pmc_traffic.json profiles/pmc_traffic.json
-python3 bench.py > gpurun_out/${TAG}_bench_last.json 2> gpurun_out/${TAG}_bench.err; echo "bench rc=$?"
+cp $OUT/${TAG}_pmc_traffic.json profiles/pmc_traffic.json
+python3 bench.py --full > $OUT/${TAG}_bench_last.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
 python3 - <<'PY'
 import json, os, shutil
+OUT = os.environ["OUT"]
 tag = os.environ["TAG"]
-first, last = f"gpurun_out/{tag}_bench_first.json", f"gpurun_out/{tag}_bench_last.json"
+first, last = f"{OUT}/{tag}_bench_first.json", f"{OUT}/{tag}_bench_last.json"
 try:
     fresh_first = not json.load(open(first))["roofline"].get("traffic_stale", True)
 except Exception:
     fresh_first = False
-shutil.copy(first if fresh_first else last, f"gpurun_out/{tag}_bench.json")
+shutil.copy(first if fresh_first else last, f"{OUT}/{tag}_bench.json")
 print("bench line kept:", "the first (counter file already matched the sources)" if fresh_first else "the last (taken with the new counter file)")
 for f in (first, last):
     try:
@@ -115,7 +118,7 @@ for f in (first, last):
         print(f, "unreadable:", e)
 PY
 python3 -c "
-import json; d = json.load(open('gpurun_out/${TAG}_bench.json'))
+import json; d = json.load(open('$OUT/${TAG}_bench.json'))
 print('step %.3f ms' % d['ms_per_step'], 'roofline', d['roofline']['frac'], 'traffic', d['roofline']['traffic'], 'stale' if d['roofline'].get('traffic_stale') else 'fresh')
 for leg in ('two_pass', 'm8'): print(leg, d['roofline_sweep'][leg]['avg_ms'], d['roofline_sweep'][leg]['frac'], d['roofline_sweep'][leg]['ms_per_step'])
 s = d['secondary']
