@@ -270,7 +270,9 @@ int pg_gp_ols_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld
  * repetitions are scored -- (n_reps * n_folds * k + k) * p doubles (BASELINE configs[3]: 101 x 40 MB) -- so that they can be
  * formed 16 columns per pass over G whatever repetition they belong to; when that is more than half of the free device memory
  * (or with POOLGEN_RIDGE_PER_REP=1) one repetition's n_folds * k columns are resident at a time and every repetition costs a
- * pass of its own.  Same results, bit for bit. */
+ * pass of its own.  Same results, bit for bit.
+ * Every fit on every path (folds, all-rows fit, per-fold and per-repetition fallbacks) takes gp::ols' branch from n and p as
+ * pg_gp_ols_dev does: a tall design (n >= p + 1) is fitted by pinv(X'X) X'y, one fold at a time. */
 int pg_gp_ridge_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y,
                     int k, const int64_t *row_idx, int n_rows, const int32_t *fold_of, int n_reps,
                     int n_folds, double alpha, double lambda_step, double *beta_dev,

@@ -664,8 +664,10 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
     // Every pool is validated by exactly ONE fold of a repetition, so all folds share two passes over G: one that
     // forms the slopes of every fold's training fit (n_folds * k coefficient columns), one (per alpha) that predicts
     // every pool with the coefficients of the fold that holds it out.  (Fallback below: one pair of passes per fold.)
+    // The fused passes take every fit from pinv(X X^T) (pg_gp_subset_solve): the wide branch of gp/ols.rs:47.  A tall design (n >= p + 1:
+    // at most n - 1 loci) takes the other formula there, so it goes one fold at a time through pg_gp_ols_dev, which follows that rule.
     const int C = n_folds * k;
-    const bool fused = C <= PG_MAX_SWEEP_COLS && !std::getenv("POOLGEN_RIDGE_PER_FOLD");
+    const bool fused = C <= PG_MAX_SWEEP_COLS && (int64_t)n < p + 1 && !std::getenv("POOLGEN_RIDGE_PER_FOLD");
     double *bf = nullptr;       // C x p (column-major) slopes of the folds' fits
     FoldMasses *fm_dev = nullptr;
     int32_t *colof_dev = nullptr;

@@ -963,6 +963,7 @@ int launch_sweep(pg_ctx *ctx, const SweepArgs &A, int grid) {
 // else 2.  Fewer than 33 pools stay with the row kernel: measured with 20 and 30 pools x 10-20 M loci, 0.50 / 0.56-0.60 of the
 // HBM peak here against 0.61 / 0.62 there (rows this short are mostly closing arithmetic per byte, and padding below 5 chunks).
 constexpr int MS_MAX_COLS = 48;
+constexpr int MS_LZ_PER_CU = 2; // workgroups per CU whose partials the lazy route's buffer (ctx->lz_dev) holds
 template <int U, int R, int NCG, int MODE>
 int launch_sweep_mfma_as(pg_ctx *ctx, const SweepArgs &A, MsGeom M, int kernel_id) {
     constexpr int threads = ms_threads(NCG), waves = threads / 64;
@@ -977,6 +978,7 @@ int launch_sweep_mfma_as(pg_ctx *ctx, const SweepArgs &A, MsGeom M, int kernel_i
     PG_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, shmem));
     if (per_cu < 1) return pg_fail(ctx, PG_ERR_UNSUPPORTED, "sweep: %zu bytes of LDS per workgroup do not fit", shmem);
     if (const char *e = std::getenv("POOLGEN_SWEEP_GRID_MULT")) per_cu = std::max(1, std::atoi(e)); // experiments
+    if (MODE == 2) per_cu = std::min(per_cu, MS_LZ_PER_CU); // one (1'S1, trace S) pair per wave of the grid: what lz_dev holds
     const int64_t blocks = (M.n64 + waves - 1) / waves, cap = (int64_t)ctx->cus * per_cu;
     pg_prof_begin(ctx, kernel_id);
     hipLaunchKernelGGL(kern, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(threads), shmem, ctx->stream, A.G, A.W, A.syy,
@@ -995,10 +997,12 @@ int ms_pick_u(int nc) {
     if (const char *e = std::getenv("POOLGEN_SWEEP_U")) { const int u = std::atoi(e); if (u >= 5 && u <= 8) U = u; } // experiments
     return U;
 }
-// does the B table ([column groups][padded chunks] KB) plus the closing stage fit the 160 KB of a CU?
-bool ms_fits(int n, int cu) {
+// row pitch (doubles) of the closing stage: MODE 2 keeps the locus' shift behind the sums
+constexpr int ms_pitch(int cu, int mode) { return mode == 2 ? ((cu + 2) | 1) : ((cu + 1) | 1); }
+// does the B table ([column groups][padded chunks] KB) plus the closing stage of a MODE launch fit the 160 KB of a CU?
+bool ms_fits(int n, int cu, int mode) {
     const int nc = (n + 7) / 8, U = ms_pick_u(nc), ncp = (nc + U - 1) / U * U, ncg = (cu + 15) / 16;
-    return nc >= 5 && cu <= MS_MAX_COLS && ((size_t)ncg * ncp * 128 + (size_t)(ms_threads(ncg) / 64) * 64 * ((cu + 1) | 1)) * sizeof(double) <= 160 * 1024;
+    return nc >= 5 && cu <= MS_MAX_COLS && ((size_t)ncg * ncp * 128 + (size_t)(ms_threads(ncg) / 64) * 64 * ms_pitch(cu, mode)) * sizeof(double) <= 160 * 1024;
 }
 
 template <int MODE>
@@ -1007,7 +1011,7 @@ int launch_sweep_mfma(pg_ctx *ctx, const SweepArgs &A, int cols, int cu, int ker
     M.nc = (A.D.n + 7) / 8;
     M.cols = cols;
     M.cu = cu;
-    M.pitch = (MODE == 2) ? ((cu + 2) | 1) : ((cu + 1) | 1); // MODE 2 keeps the locus' shift behind the sums
+    M.pitch = ms_pitch(cu, MODE);
     M.n64 = (A.D.p + 63) / 64;
     const int U = ms_pick_u(M.nc);
     const int ncg = (cu + 15) / 16;
@@ -1340,7 +1344,7 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
     }
     // the matrix-core sweep unless an A/B run asks for one of the vector-ALU kernels
     const int cu = ctx->st_m + 1 + ctx->st_k;
-    if (ms_fits(n, cu) && !std::getenv("POOLGEN_SWEEP_V1") && !std::getenv("POOLGEN_SWEEP_V2"))
+    if (ms_fits(n, cu, 0) && !std::getenv("POOLGEN_SWEEP_V1") && !std::getenv("POOLGEN_SWEEP_V2"))
         return launch_sweep_mfma<0>(ctx, P, ctx->st_cols, cu, PG_K_SWEEP);
     int64_t blocks = (P.D.ntiles + SW_WAVES - 1) / SW_WAVES;
     int mult = 8;
@@ -1374,10 +1378,10 @@ extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
     // One HBM-bound pass then gives the outputs of the m = 0 analysis (the sweep kernel's own: bit-identical to the two-pass
     // route); if the bound does not clear x by 1e-9 -- never on an uncentred kinship of real frequencies -- the full route below runs.
     if (!K_out && force_m < 0 && G_dev && Y && beta_dev && var_dev && pval_dev && p > 0 && n >= 3 && k >= 1 && k <= 15 && ld >= n &&
-        (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && ms_fits(n, 1 + k) && !std::getenv("POOLGEN_NO_LAZY_KINSHIP")) {
+        (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && ms_fits(n, 1 + k, 2) && !std::getenv("POOLGEN_NO_LAZY_KINSHIP")) {
         rc = pg_covariates_set(ctx, n, nullptr, 0, Y, k);
         if (rc) return rc;
-        const size_t lzbytes = sizeof(double) * 2 * (size_t)ctx->cus * 8 * 2; // a workgroup per CU (launch bounds), 8 waves each; twice that
+        const size_t lzbytes = sizeof(double) * 2 * (size_t)ctx->cus * (ms_threads(1) / 64) * MS_LZ_PER_CU; // the MODE-2 grid is clamped to it
         if (!ctx->lz_dev) PG_HIP(ctx, hipMalloc((void **)&ctx->lz_dev, lzbytes));
         PG_HIP(ctx, hipMemsetAsync(ctx->lz_dev, 0, lzbytes, ctx->stream));
         SweepArgs P;
@@ -1393,20 +1397,24 @@ extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
         P.D.ss = nullptr;
         P.D.lz = ctx->lz_dev;
         rc = launch_sweep_mfma<2>(ctx, P, ctx->st_cols, 1 + k, PG_K_SWEEP);
-        if (rc) return rc;
-        rc = pg_pin_reserve(ctx, lzbytes);
-        if (rc) return rc;
-        PG_HIP(ctx, hipMemcpyAsync(ctx->pin, ctx->lz_dev, lzbytes, hipMemcpyDeviceToHost, ctx->stream));
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const double *hp = static_cast<const double *>(ctx->pin);
-        double tot = 0.0, tr = 0.0;
-        for (size_t w = 0; w < lzbytes / 16; ++w) { tot += hp[2 * w]; tr += hp[2 * w + 1]; }
-        if (tr > 0.0 && std::isfinite(tot) && (tot / n) / tr >= var_explained + 1e-9) {
-            if (m_out) *m_out = 0;
-            ctx->lazy_taken = true;
-            return PG_OK;
+        if (rc == PG_OK) {
+            rc = pg_pin_reserve(ctx, lzbytes);
+            if (rc) return rc;
+            PG_HIP(ctx, hipMemcpyAsync(ctx->pin, ctx->lz_dev, lzbytes, hipMemcpyDeviceToHost, ctx->stream));
+            PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            const double *hp = static_cast<const double *>(ctx->pin);
+            double tot = 0.0, tr = 0.0;
+            for (size_t w = 0; w < lzbytes / 16; ++w) { tot += hp[2 * w]; tr += hp[2 * w + 1]; }
+            if (tr > 0.0 && std::isfinite(tot) && (tot / n) / tr >= var_explained + 1e-9) {
+                if (m_out) *m_out = 0;
+                ctx->lazy_taken = true;
+                return PG_OK;
+            }
+        } else {
+            (void)hipGetLastError(); // a launch the device refused decides nothing
         }
-        // (a NaN frequency, or a kinship whose leading share is not decided by the ones vector: the full route says what the reference says)
+        // (a refused launch, a NaN frequency, or a kinship whose leading share is not decided by the ones vector: the full route says
+        // what the reference says)
     }
     ctx->lazy_taken = false;
     if (ctx->S_n < n) {
@@ -1588,7 +1596,7 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
     const int grid = (int)(blocks < cap ? blocks : cap);
     int rc;
     // the matrix-core kernel of the sweep in its products-only mode: every shape, one read of G at the sweep's rate
-    if (ms_fits(n, ncol) && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && !std::getenv("POOLGEN_GP_BETA_OLD")) {
+    if (ms_fits(n, ncol, 1) && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && !std::getenv("POOLGEN_GP_BETA_OLD")) {
         SweepArgs P;
         P.G = G_dev; P.W = ctx->W_dev; P.syy = nullptr; P.tcoef = nullptr;
         P.beta = out_dev; P.var = nullptr; P.pval = nullptr;

@@ -496,9 +496,20 @@ def test_gp_proxy_matches_oracle(engine, oracle, exact, n, p, k, rows):
         assert np.allclose(got[l], sol, rtol=1e-6, atol=1e-8 * np.abs(ref).max()), l
 
 
-@pytest.mark.parametrize("n,p,k,alpha,proxy", [(48, 2000, 1, -0.1, False), (40, 1500, 2, -0.1, False),
-                                                (48, 2000, 1, 1.0, True), (44, 1200, 2, 0.0, True)])
-def test_gp_penalised_family_matches_oracle(engine, oracle, exact, n, p, k, alpha, proxy):
+# gp::ols takes pinv(X X^T) for a wide design and pinv(X'X) for a tall one (n >= p + 1 with the intercept column, gp/ols.rs:47;
+# pg_gp_ols_dev, pg_sweep.hip:1679; the fused passes only where it is wide, pg_gp.hip:667-670).  Shapes at the edge on both sides
+# (p = n - 1 tall, p = n wide) and well inside the tall side (p ~ n / 3); n_reps 1 and 3 (the batched passes need n_reps > 1).
+# (The reference's own 5 x 3 shape leaves a fold with a single validation pool at these fold counts: its error index is 0 / 0.)
+@pytest.mark.parametrize("n,p,k,alpha,proxy,n_reps", [
+    pytest.param(48, 2000, 1, -0.1, False, 3, id="48-2000-1--0.1-False"), pytest.param(40, 1500, 2, -0.1, False, 3, id="40-1500-2--0.1-False"),
+    pytest.param(48, 2000, 1, 1.0, True, 3, id="48-2000-1-1.0-True"), pytest.param(44, 1200, 2, 0.0, True, 3, id="44-1200-2-0.0-True"),
+    (40, 39, 1, -0.1, False, 3),    # tall, at the edge
+    (40, 40, 2, -0.1, False, 1),    # wide, at the edge
+    (40, 40, 2, 0.0, True, 1),      # wide, at the edge (the proxy models' binary128 fits have no tall branch: exq_gp_ols)
+    (45, 15, 1, -0.1, False, 1),    # well inside tall
+    (60, 20, 2, -0.1, False, 3),    # well inside tall
+])
+def test_gp_penalised_family_matches_oracle(engine, oracle, exact, n, p, k, alpha, proxy, n_reps):
     """penalise_glmnet (alpha < 0: the alpha x lambda grid, gp/penalise.rs:168-195, :479-498) and the
     *_with_iterative_proxy_norms models (:197-246) with explicit folds.  For the proxy models the oracle's path takes its fold fits
     and its proxy coefficients from the binary128 restatements (everything downstream -- expand_and_contract, error_index, the
@@ -507,7 +518,7 @@ def test_gp_penalised_family_matches_oracle(engine, oracle, exact, n, p, k, alph
     Y = Y[:, :k]
     rng = np.random.default_rng(12)
     rows = np.array([i for i in range(n) if i % 11 != 5])
-    n_folds, n_reps = 3, 3
+    n_folds = 3
     folds = np.stack([rng.permutation(np.arange(len(rows)) % n_folds) for _ in range(n_reps)])
     beta, al, lam, perf = engine.gp_penalised(G, Y, rows, folds, n_folds, alpha, proxy, n=n)
     Xt = np.vstack([np.ones((1, n)), G.cpu().numpy()[:, :n]])
@@ -576,15 +587,24 @@ def test_gp_ols_with_duplicated_pools_uses_the_pseudo_inverse(engine, oracle):
     assert np.allclose(Xt.T @ beta, Y, atol=1e-6 * np.abs(Y).max())
 
 
-@pytest.mark.parametrize("n,p,k,alpha", [(60, 3000, 1, 0.0), (40, 2000, 2, 0.0), (50, 1500, 1, 1.0)])
-def test_gp_ridge_path_matches_oracle(engine, oracle, n, p, k, alpha):
+# tall / wide shapes: see test_gp_penalised_family_matches_oracle, which also carries the shapes well inside the tall side (here
+# their error indices reach 15 and more, and fp64 noise of 1e-11 relative exceeds the absolute 1e-10 of the 2 % clause below)
+@pytest.mark.parametrize("n,p,k,alpha,n_reps", [
+    pytest.param(60, 3000, 1, 0.0, 3, id="60-3000-1-0.0"), pytest.param(40, 2000, 2, 0.0, 3, id="40-2000-2-0.0"),
+    pytest.param(50, 1500, 1, 1.0, 3, id="50-1500-1-1.0"),
+    (40, 39, 1, 0.0, 3),     # tall, at the edge
+    (40, 39, 2, 1.0, 1),     # tall, at the edge
+    (40, 40, 2, 0.0, 3),     # wide, at the edge
+    (41, 41, 1, 0.0, 1),     # wide, at the edge
+])
+def test_gp_ridge_path_matches_oracle(engine, oracle, n, p, k, alpha, n_reps):
     """penalise_ridge_like / the lambda path with k-fold CV (gp/penalise.rs:133-159, :461-669) with the
     folds made explicit (the reference's are unseeded random, :452-453)."""
     G, Y = make(p, n, 47)
     Y = Y[:, :k]
     rng = np.random.default_rng(8)
     rows = np.array([i for i in range(n) if i % 9 != 4])          # an outer training subset
-    n_folds, n_reps = 4, 3
+    n_folds = 4
     folds = np.stack([rng.permutation(np.arange(len(rows)) % n_folds) for _ in range(n_reps)])
     beta, lam, perf = engine.gp_ridge(G, Y, rows, folds, n_folds, alpha=alpha, n=n)
     Xt = np.vstack([np.ones((1, n)), G.cpu().numpy()[:, :n]])
