@@ -66,13 +66,13 @@ int pg_synchronize(pg_ctx *ctx);
 /* Per-kernel HIP-event timing (used by bench.py for the roofline record). */
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
-                    PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_COUNT = 11 };
+                    PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_COUNT = 12 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
 int pg_profile_get(pg_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
 /* Diagnostics of the last batch operator call (pg_ols_iter_batch[_dev], pg_pearson_batch[_dev], pg_chisq_batch[_dev],
- * pg_load_plan_dev) on this context: *loci = L of that call, *listed = the loci its streaming pass could not close in place
+ * pg_fisher_batch[_dev], pg_load_plan_dev) on this context: *loci = L of that call, *listed = the loci its streaming pass could not close in place
  * and handed to the second pass (three or more surviving alleles, or a speculated allele pair that did not hold; summed
  * over the launch groups of a multi-trait call).  Either pointer may be NULL. */
 int pg_locus_op_stats(const pg_ctx *ctx, int64_t *loci, int64_t *listed);
@@ -210,6 +210,15 @@ int pg_pearson_batch_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int
 int pg_chisq_batch_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n,
                        const double *pool_sizes, const pg_filter *filter, int32_t *n_out_dev,
                        int32_t *allele_ids_dev, double *chi2_dev, double *pval_dev);
+/* tables::fisher (tables/fisher_exact_test.rs:32-130): n_out = alleles kept (listed in allele_ids, slot-major),
+ * p_observed[L], pval[L] = p_observed + p_extremes.  Slots / values of loci with n_out == 0 are unspecified.
+ * The table is the FILTERED COUNTS (n pools x surviving alleles), scaled to at most 34 reads when it holds more
+ * (coef = 34 / total, cell = floor(cell * coef), :50-58); p_observed = the hypergeometric ratio of that table, p_extremes =
+ * the sum of the ratio over the n * p tables the reference rebuilds (:72-118; duplicates counted as often as they occur, so
+ * pval may exceed 1).  A locus' result depends on its counts, the filter and n only -- not on the batch or the context. */
+int pg_fisher_batch_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const double *pool_sizes,
+                        const pg_filter *filter, int32_t *n_out_dev, int32_t *allele_ids_dev,
+                        double *p_observed_dev, double *pval_dev);
 /* The loader, FileSyncPhen::load + into_genotypes_and_phenotypes (base/sync.rs:972-1180), on counts that
  * are already in HBM: per locus LocusCounts::filter (:195-303) -> to_frequencies over the surviving
  * alleles (:166-192) -> with keep_p_minus_1 sort by decreasing frequency and drop the first allele
@@ -233,7 +242,7 @@ int pg_expand_counts_u16_dev(pg_ctx *ctx, const uint16_t *src_dev, int64_t n_val
  * p x ld like G; every column row of a locus holds, per pool, the depth summed over the locus' surviving alleles. */
 int pg_load_emit_cov_dev(pg_ctx *ctx, const int32_t *pool_map, int n_out, double *G_dev, int64_t ld,
                          int64_t *col_locus_dev, int32_t *col_allele_dev, double *cov_dev);
-/* Host-buffer forms of the three batch operators (H2D/D2H inside). */
+/* Host-buffer forms of the batch operators (H2D/D2H inside). */
 int pg_ols_iter_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n,
                       const double *pool_sizes, const pg_filter *filter, const double *Y, int k,
                       int32_t *n_out, int32_t *allele_ids, double *mean_freq, double *stat,
@@ -245,6 +254,9 @@ int pg_pearson_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n,
 int pg_chisq_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const double *pool_sizes,
                    const pg_filter *filter, int32_t *n_out, int32_t *allele_ids, double *chi2,
                    double *pval);
+int pg_fisher_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const double *pool_sizes,
+                    const pg_filter *filter, int32_t *n_out, int32_t *allele_ids, double *p_observed,
+                    double *pval);
 
 /* ---------------------------------------------------------------------------------------
  * Genomic prediction: gp::ols (gp/ols.rs:8-101) for the n < p case, b = X^T pinv(X X^T) y,

@@ -62,11 +62,13 @@ SIGNATURES = {
     "pg_ols_iter_batch_dev": (_i, _batch),
     "pg_pearson_batch_dev": (_i, _batch),
     "pg_chisq_batch_dev": (_i, [_vp, _vp, _i64, _i, _vp, _pf, _vp, _vp, _vp, _vp]),
+    "pg_fisher_batch_dev": (_i, [_vp, _vp, _i64, _i, _vp, _pf, _vp, _vp, _vp, _vp]),
     "pg_load_plan_dev": (_i, [_vp, _vp, _i64, _i, _vp, _pf, _i, _vp, _vp]),
     "pg_load_emit_dev": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _vp]),
     "pg_ols_iter_batch": (_i, _batch),
     "pg_pearson_batch": (_i, _batch),
     "pg_chisq_batch": (_i, [_vp, _vp, _i64, _i, _vp, _pf, _vp, _vp, _vp, _vp]),
+    "pg_fisher_batch": (_i, [_vp, _vp, _i64, _i, _vp, _pf, _vp, _vp, _vp, _vp]),
     "pg_gp_xxt_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp]),
     "pg_gp_ols_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i, _vp, _i, _vp, _vp]),
     "pg_gp_ridge_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i, _vp, _i, _vp, _i, _i, _d, _d, _vp, _vp, _vp]),
@@ -86,7 +88,7 @@ SIGNATURES = {
 }
 
 KERNEL_IDS = {"kinship": 0, "kinship_reduce": 1, "sweep": 2, "ols_iter": 3, "pearson": 4,
-              "chisq": 5, "gp_xxt": 6, "gp_beta": 7, "sweep_finish": 8, "allreduce": 9, "gp_predict": 10}
+              "chisq": 5, "gp_xxt": 6, "gp_beta": 7, "sweep_finish": 8, "allreduce": 9, "gp_predict": 10, "fisher": 11}
 
 
 def load_library():

@@ -1,5 +1,5 @@
 // apitest.cpp -- the reference's operator-level unit tests, transcribed: same inputs, same expected strings
-// (gwas/correlation_test.rs:136-182, tables/chisq_test.rs:53-82), plus gwas::ols_iterate on the same locus against the
+// (gwas/correlation_test.rs:136-182, tables/chisq_test.rs:53-82, tables/fisher_exact_test.rs:137-173), plus gwas::ols_iterate on the same locus against the
 // values SURVEY.md section 8c derives.  Runs on the GPU; prints one line per check and exits non-zero on a mismatch.
 #include "operators.h"
 #include <cmath>
@@ -24,6 +24,27 @@ static void expect_line(const char *what, const std::string &got, const std::str
     const size_t cg = got.rfind(','), cw = want.rfind(',');
     bool ok = cg != std::string::npos && cw != std::string::npos && got.substr(0, cg) == want.substr(0, cw);
     if (ok) ok = std::fabs(std::strtod(got.c_str() + cg + 1, nullptr) - std::strtod(want.c_str() + cw + 1, nullptr)) <= 1e-10;
+    std::printf("%s %s\n", ok ? "ok  " : "FAIL", what);
+    if (!ok) { std::printf("  got : %s  want: %s", got.c_str(), want.c_str()); ++failures; }
+}
+
+// fisher's line ends in TWO numbers printed at full precision (p_observed, p_observed + p_extremes): the device's 10^x is within
+// a few ulp of the host library's, so both are held to a relative 1e-10 and the fields before them to equality.
+static void expect_fisher_line(const char *what, const std::string &got, const std::string &want) {
+    auto split = [](const std::string &s, std::string &head, double &a, double &b) {
+        const size_t c2 = s.rfind(',');
+        if (c2 == std::string::npos || c2 == 0) return false;
+        const size_t c1 = s.rfind(',', c2 - 1);
+        if (c1 == std::string::npos) return false;
+        head = s.substr(0, c1);
+        a = std::strtod(s.c_str() + c1 + 1, nullptr);
+        b = std::strtod(s.c_str() + c2 + 1, nullptr);
+        return true;
+    };
+    std::string hg, hw;
+    double ag = 0, bg = 0, aw = 0, bw = 0;
+    bool ok = split(got, hg, ag, bg) && split(want, hw, aw, bw) && hg == hw;
+    if (ok) ok = std::fabs(ag - aw) <= 1e-10 * std::fabs(aw) && std::fabs(bg - bw) <= 1e-10 * std::fabs(bw);
     std::printf("%s %s\n", ok ? "ok  " : "FAIL", what);
     if (!ok) { std::printf("  got : %s  want: %s", got.c_str(), want.c_str()); ++failures; }
 }
@@ -63,6 +84,18 @@ int main() {
         l.matrix = {0, 20, 20, 0, 0, 20, 20, 0};
         expect_line("chisq(locus_counts, filter_stats) == expected_line (p-value within 1e-10)", op.chisq(l, f).value_or("None\n"),
                "Chromosome1,12345,AT,4,0.7797774084757156\n");
+    }
+    { // test_fisher (tables/fisher_exact_test.rs:137-173)
+        FilterStats f;
+        f.remove_ns = true; f.max_base_error_rate = 0.005; f.min_coverage_depth = 1; f.min_coverage_breadth = 1.0;
+        f.min_allele_frequency = 0.005; f.max_missingness_rate = 0.0; f.pool_sizes = {0.2, 0.2, 0.2};
+        LocusCounts l;
+        l.chromosome = "Chromosome1"; l.position = 12345; l.alleles_vector = {"T", "C"};
+        l.matrix = {0, 3, 1, 5, 2, 6};
+        const std::string got = op.fisher(l, f).value_or("None\n");
+        std::printf("     fisher -> %s", got.c_str());
+        expect_fisher_line("fisher(locus_counts, filter_stats) == expected_output3 (both numbers within 1e-10)", got,
+                           "Chromosome1,12345,TC,0.24705882352941286,0.6073529411764731\n");
     }
     pg_destroy(ctx);
     std::printf("%s\n", failures ? "apitest: FAILED" : "apitest: all checks passed");

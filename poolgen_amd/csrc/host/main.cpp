@@ -1,5 +1,5 @@
 // main.cpp -- `poolgen` command line for the hot subcommands, flag-compatible with the
-// reference CLI (src/main.rs:26-143): pileup2sync, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship
+// reference CLI (src/main.rs:26-143): pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship
 // (and gp_ols as a plain coefficient dump).  Parsing/formatting/ordering follow the reference
 // (base/sync.rs:606-970, :972-1180; gwas/ols.rs:255-275, :372-433); all arithmetic on the loci
 // is done by libpoolgen_hip.so through its C ABI.  Anything else the reference CLI offers is out
@@ -77,8 +77,8 @@ static int flag_int(const std::string &v, const std::string &flag, int64_t lo = 
 
 static const char *USAGE =
     "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
-    "analyses: pileup2sync, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship, mle_iter_with_kinship,\n"
-    "          genomic_prediction_cross_validation, fst, heterozygosity\n"
+    "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship,\n"
+    "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity\n"
     "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
     "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
     "                                     writes A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on pileup-derived\n"
@@ -94,8 +94,8 @@ static const char *USAGE =
     "      --window-size-bp <100>  --window-slide-size-bp <50>  --min-loci-per-window <10>   fst, heterozygosity\n"
     "      --n-threads <1>                 parser / writer threads\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
-    "      --n-gpus <N>  [--gpu-ids a,b,..]  chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship: one contiguous part of\n"
-    "                                      the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
+    "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship: one contiguous\n"
+    "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
     "                                      all-reduced over the GPUs with RCCL; the kinship path then needs an input sorted by\n"
     "                                      (chromosome, position)\n"
     "environment: PGH_TIMING=1 prints the phases' wall-clock on stderr\n";
@@ -691,7 +691,7 @@ static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &l
     return done_ok();
 }
 
-// chisq_test / pearson_corr / ols_iter (main.rs:245-271): the per-locus operators know nothing beyond their own line, so
+// fisher_exact_test / chisq_test / pearson_corr / ols_iter (main.rs:245-271; mode 3 / 0 / 1 / 2): the per-locus operators know nothing beyond their own line, so
 // the file is taken in pieces whatever its size -- the worker threads parse piece c + 1 into one of two pinned buffers
 // (16-bit counts when they fit) while the GPU takes piece c and its rows are formatted and appended, in file order
 // (sync.rs:927-946).  Nothing of the size of the input is ever allocated, pinned or copied in one go.
@@ -725,7 +725,8 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
     }
     const int n2 = (int)keep.size();
     const bool subset = n2 != n;
-    const char *header = mode == 0 ? "#chr,pos,alleles,statistic,pvalue\n"                 // sync.rs:766
+    const bool tables = mode == 0 || mode == 3; // chisq_test, fisher_exact_test: counts only, one row per locus, no phenotype used
+    const char *header = tables ? "#chr,pos,alleles,statistic,pvalue\n"                    // sync.rs:766
                                    : "#chr,pos,alleles,freq,phenotype,statistic,pvalue\n"; // sync.rs:950
     // One rank = one contiguous range of pieces, one GPU, its own pinned buffers and parser threads, and -- when there are
     // several -- its own part file, like the reference's one `.tmp` file per worker thread (sync.rs:794-870), concatenated in
@@ -778,7 +779,7 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
         std::vector<uint32_t> counts2;
         std::vector<int32_t> n_out, ids;
         std::vector<double> mfq, stat, pv;
-        const size_t per_stat = mode == 0 ? 1 : (size_t)PG_MAX_OUT * k;
+        const size_t per_stat = tables ? 1 : (size_t)PG_MAX_OUT * k;
         for (int c = c0; c < c1; ++c) {
             SyncBatch sb = next.get();
             if (c + 1 < c1) next = std::async(std::launch::async, parse_piece, c + 1);
@@ -804,7 +805,9 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
                 hip_ok(hipMemcpy(counts_dev, counts2.data(), sizeof(uint32_t) * counts2.size(), hipMemcpyHostToDevice), "H2D counts");
             } else
                 upload(gpu, sb, counts_dev);
-            if (mode == 0)
+            if (mode == 3)
+                gpu.ok(pg_fisher_batch_dev(gpu.c, counts_dev, L, n2, ps.data(), &flt, n_out_dev, ids_dev, stat_dev, pv_dev), "fisher_exact_test");
+            else if (mode == 0)
                 gpu.ok(pg_chisq_batch_dev(gpu.c, counts_dev, L, n2, ps.data(), &flt, n_out_dev, ids_dev, stat_dev, pv_dev), "chisq_test");
             else if (mode == 1)
                 gpu.ok(pg_pearson_batch_dev(gpu.c, counts_dev, L, n2, ps.data(), &flt, Y.data(), k, n_out_dev, ids_dev, mf_dev, stat_dev, pv_dev),
@@ -819,9 +822,9 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
             int used = 0;
             for (int64_t l = 0; l < L; ++l) used = std::max(used, (int)n_out[l]);
             used = std::min(used, (int)PG_MAX_OUT);
-            const size_t per_stat_used = mode == 0 ? 1 : (size_t)used * k;
+            const size_t per_stat_used = tables ? 1 : (size_t)used * k;
             hip_ok(hipMemcpy(ids.data(), ids_dev, sizeof(int32_t) * L * used, hipMemcpyDeviceToHost), "D2H results");
-            if (mode != 0) hip_ok(hipMemcpy(mfq.data(), mf_dev, sizeof(double) * L * used, hipMemcpyDeviceToHost), "D2H results");
+            if (!tables) hip_ok(hipMemcpy(mfq.data(), mf_dev, sizeof(double) * L * used, hipMemcpyDeviceToHost), "D2H results");
             hip_ok(hipMemcpy(stat.data(), stat_dev, sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
             hip_ok(hipMemcpy(pv.data(), pv_dev, sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
             if (!fo) {
@@ -830,7 +833,7 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
             }
             write_rows_parallel(fo, L, threads, [&](int64_t l, std::string &line) {
                 // slot-major arrays: slot i of locus l sits i * L elements after its slot 0
-                const size_t so = mode == 0 ? (size_t)l : (size_t)l * k;
+                const size_t so = tables ? (size_t)l : (size_t)l * k;
                 format_locus_rows(mode, sb.chrom(l), sb.pos[l], n_out[l], &ids[(size_t)l], &mfq[(size_t)l], &stat[so], &pv[so], k, line, (size_t)L);
             });
         }
@@ -1102,10 +1105,10 @@ static int run(int argc, char **argv) {
     const std::map<std::string, int> known{{"chisq_test", 0}, {"pearson_corr", 1}, {"ols_iter", 2},
                                            {"ols_iter_with_kinship", 3}, {"pileup2sync", 4},
                                            {"genomic_prediction_cross_validation", 5}, {"fst", 6}, {"heterozygosity", 7},
-                                           {"mle_iter_with_kinship", 8}};
+                                           {"mle_iter_with_kinship", 8}, {"fisher_exact_test", 9}};
     if (!known.count(a.analysis))
         throw std::runtime_error("Invalid analysis utility for this build: `" + a.analysis +
-                                 "` (available: pileup2sync, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship, "
+                                 "` (available: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship, "
                                  "mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity)");
     if (a.generate_plots || a.sig_only)
         throw std::runtime_error("--generate-plots / --output-sig-snps-only call the reference's python scripts and are out of scope here");
@@ -1134,8 +1137,8 @@ static int run(int argc, char **argv) {
         std::cout << out << "\n"; // main.rs:507
         return done_ok();
     }
-    if (a.n_gpus > 0 && known.at(a.analysis) > 3)
-        throw std::runtime_error("--n-gpus applies to chisq_test, pearson_corr, ols_iter and ols_iter_with_kinship; `" + a.analysis + "` runs on one GPU");
+    if (a.n_gpus > 0 && known.at(a.analysis) > 3 && known.at(a.analysis) != 9)
+        throw std::runtime_error("--n-gpus applies to fisher_exact_test, chisq_test, pearson_corr, ols_iter and ols_iter_with_kinship; `" + a.analysis + "` runs on one GPU");
     const RankSetup ranks = rank_setup(a, a.analysis == "ols_iter_with_kinship");
     Ctx gpu(ranks.devices[0]); // first: the pinned allocator below needs a HIP context
     lap("start-up");
@@ -1180,10 +1183,10 @@ static int run(int argc, char **argv) {
             }
         }
     }
-    if (known.at(a.analysis) <= 2) {
+    if (known.at(a.analysis) <= 2 || known.at(a.analysis) == 9) {
         size_t piece = (size_t)(a.stream_chunk_mb > 0 ? a.stream_chunk_mb : 128) << 20;
         if (const char *e = std::getenv("PGH_STREAM_CHUNK_BYTES")) piece = (size_t)std::strtoull(e, nullptr, 10); // tests: small pieces
-        return run_batch_streamed(a, ph, gpu, lap, known.at(a.analysis), piece, is_pileup, pf, flt, ranks);
+        return run_batch_streamed(a, ph, gpu, lap, known.at(a.analysis) == 9 ? 3 : known.at(a.analysis), piece, is_pileup, pf, flt, ranks);
     }
     SyncBatch sb;
     if (is_pileup) {

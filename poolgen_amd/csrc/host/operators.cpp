@@ -9,6 +9,14 @@ void format_locus_rows(int mode, const std::string &chromosome, uint64_t positio
                        const double *stat, const double *pval, int k, std::string &line, size_t slot_stride) {
     if (n_out <= 0) return;
     const size_t S = slot_stride; // the library's arrays are slot-major: slot i of this locus is S elements (S * k for stat / pval) further on
+    if (mode == 3) { // fisher_exact_test.rs:119-129: both numbers with to_string()
+        line += chromosome; line.push_back(','); line += std::to_string(position); line.push_back(',');
+        for (int j = 0; j < n_out && j < PG_MAX_OUT; ++j) line.push_back(ALLELES[ids[j * S]]);
+        line.push_back(',');
+        append_rust_display(line, stat[0]); line.push_back(',');
+        append_rust_display(line, pval[0]); line.push_back('\n');
+        return;
+    }
     if (mode == 0) { // chisq_test.rs:37-45
         line += chromosome; line.push_back(','); line += std::to_string(position); line.push_back(',');
         for (int j = 0; j < n_out && j < PG_MAX_OUT; ++j) line.push_back(ALLELES[ids[j * S]]);
@@ -59,7 +67,8 @@ std::optional<std::string> Operators::run(int mode, const LocusCounts &lc, const
     double mf[PG_MAX_OUT] = {0};
     std::vector<double> stat((size_t)PG_MAX_OUT * (k > 0 ? k : 1)), pv(stat.size());
     int rc;
-    if (mode == 0) rc = pg_chisq_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, &n_out, ids, stat.data(), pv.data());
+    if (mode == 3) rc = pg_fisher_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, &n_out, ids, stat.data(), pv.data());
+    else if (mode == 0) rc = pg_chisq_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, &n_out, ids, stat.data(), pv.data());
     else if (mode == 1) rc = pg_pearson_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, Y, k, &n_out, ids, mf, stat.data(), pv.data());
     else rc = pg_ols_iter_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, Y, k, &n_out, ids, mf, stat.data(), pv.data());
     if (rc != PG_OK) throw std::runtime_error(pg_last_error(ctx_)); // a broken device, not a property of the locus
@@ -70,6 +79,8 @@ std::optional<std::string> Operators::run(int mode, const LocusCounts &lc, const
 }
 
 std::optional<std::string> Operators::chisq(LocusCounts &locus, const FilterStats &f) const { return run(0, locus, nullptr, 0, f); }
+
+std::optional<std::string> Operators::fisher(LocusCounts &locus, const FilterStats &f) const { return run(3, locus, nullptr, 0, f); }
 
 std::optional<std::string> Operators::correlation(LocusCountsAndPhenotypes &l, const FilterStats &f) const {
     const size_t n = l.locus_counts.alleles_vector.empty() ? 0 : l.locus_counts.matrix.size() / l.locus_counts.alleles_vector.size();

@@ -2,6 +2,7 @@
 //   ols_iter      gwas::ols_iterate   (gwas/ols.rs:201-276)
 //   pearson_corr  gwas::correlation   (gwas/correlation_test.rs:73-129, :7-71)
 //   chisq_test    tables::chisq       (tables/chisq_test.rs:5-47)
+//   fisher_exact_test  tables::fisher (tables/fisher_exact_test.rs:32-130; at the end of the file: the loader's filter pass + k_fisher)
 // all of which start with LocusCounts::filter + to_frequencies (base/sync.rs:195-303, :166-192).
 //
 // Input: counts[L][n][6] u32 (sync columns A,T,C,G,N,D), 24n bytes per locus -- integer/byte
@@ -2917,6 +2918,315 @@ int load_emit(pg_ctx *ctx, const int32_t *pool_map, int n_out, double *G_dev, in
     return PG_OK;
 }
 
+// ---- fisher_exact_test: tables::fisher (tables/fisher_exact_test.rs:32-130) ----------------------------------------------
+// Per locus: the filtered COUNTS (n pools x p surviving alleles), scaled to at most 34 reads (coef = 34 / total, then
+// floor(c * coef) per cell: one division, one multiply, floor -- this file is compiled with -ffp-contract=off), p_observed =
+// hyper(table), and p_extremes = the sum of hyper over the n * p tables the reference rebuilds in place, one per (max_i, max_j).
+// The filter is the loader's (launch_passes<OP_LOAD>, sort_desc = 0: one header word per locus); k_fisher does the rest.
+//
+// What keeps the enumeration small: the scaled table holds <= 34 reads, so <= 34 rows (and <= 6 columns) are non-zero; an all-zero
+// row or column stays zero in every rebuilt table (mx = min(0, .)), and the table of (max_i, max_j) depends only on t_r = the number
+// of non-zero rows before max_i and t_c = the number of non-zero columns before max_j.  So one table per distinct (t_r, t_c) over the
+// compacted marginals, weighted by the number of (max_i, max_j) that map to it; "last row / last column" (always filled) mean the TRUE
+// last pool / last surviving allele -- when that one is all zero, no compacted row / column is "last".  A rebuilt table is a function
+// of the marginals alone: forward (row-major) every cell takes min(row remainder, column remainder) or 0, so a non-zero cell leaves
+// one of its two remainders at zero; the backward pass (columns descending, rows descending inside) writes min(remainders) where
+// that is positive, i.e. only into cells that are still zero, and again zeroes a remainder -- it never overwrites a non-zero cell.
+// The kernel therefore keeps remainders, not tables, and sums log10-factorials of the cell values as they are set.
+// A GROUP OF 16 / 32 / 64 LANES PER LOCUS: lanes = pools while the counts are read (twice: total first, the second read hits the
+// cache), lanes = tables during the enumeration.  The result is a function of the locus' counts, the filter and n alone.
+constexpr int FI_MAXR = 36;   // compacted rows: at most 34 are non-zero
+constexpr int FI_UNIT = 64;   // consecutive loci per wave and turn: their results leave as contiguous runs
+struct FisherTab { double F[35]; }; // F[x] = sum_{i=2..x} log10(i) in that order (fisher_exact_test.rs:6-18), built on the host
+
+__device__ __forceinline__ void fi_wave_sync() { // LDS written by some lanes of this wave, read by others
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int fi_byte(unsigned long long v, int j) { return (int)((v >> (8 * j)) & 255); }
+
+// LPL lanes per locus (a function of n alone, see fisher_dev): 64 / LPL loci are in flight per wave, which is what hides the
+// latency of a locus' dependent steps (header, total, cells) -- the pass is latency-bound, not bandwidth-bound, per locus.
+template <int LPL>
+__global__ __launch_bounds__(LO_THREADS) void k_fisher(const uint32_t *__restrict__ counts, const int32_t *__restrict__ flags,
+                                                       int64_t L, int n, const FisherTab tab, int32_t *__restrict__ n_out,
+                                                       int32_t *__restrict__ ids_out, double *__restrict__ pobs_out,
+                                                       double *__restrict__ pval_out) {
+    constexpr int GPW = 64 / LPL, NG = LO_THREADS / LPL; // groups (= loci in flight) per wave, per workgroup
+    __shared__ double sF[35];
+    __shared__ unsigned long long s_cells[NG][FI_MAXR]; // the six scaled cells of a non-zero row, a byte each
+    __shared__ unsigned short s_rpos[NG][FI_MAXR];      // its pool
+    __shared__ unsigned char s_rs[NG][FI_MAXR + 4];     // its sum
+    __shared__ unsigned char s_rfin[NG][FI_MAXR][LPL];  // per table (= lane of the group): what the forward pass left of the row
+    __shared__ double s_po[LO_WAVES][FI_UNIT], s_pv[LO_WAVES][FI_UNIT];
+    __shared__ int s_no[LO_WAVES][FI_UNIT];
+    __shared__ unsigned int s_ids[LO_WAVES][FI_UNIT];   // 5 x 3 bits
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int g = threadIdx.x / LPL, gw = lane / LPL, gl = lane % LPL; // group in the workgroup / in the wave, lane in the group
+    if (threadIdx.x < 35) sF[threadIdx.x] = tab.F[threadIdx.x];
+    __syncthreads();
+    const int64_t nunits = (L + FI_UNIT - 1) / FI_UNIT;
+    for (int64_t unit = (int64_t)blockIdx.x * LO_WAVES + wv; unit < nunits; unit += (int64_t)gridDim.x * LO_WAVES) {
+        const int64_t l0 = unit * FI_UNIT;
+        const int nl = (int)((L - l0) < FI_UNIT ? (L - l0) : FI_UNIT);
+        for (int u = gw; u < nl; u += GPW) {
+            const int64_t l = l0 + u;
+            const int hdr = flags[l];
+            const int mask = (hdr >> 1) & 63;
+            const bool alive = (hdr & FLAG_ALIVE) != 0 && mask != 0;
+            int p = 0;
+            unsigned int idbits = 0;
+            double pobs = NAN, pval = NAN;
+            if (alive) {
+                const uint32_t *row = counts + (size_t)l * n * 6;
+                // total of the surviving alleles' counts (every count < 2^29: exact as integers, and as the f64 sum of the reference)
+                unsigned long long tot = 0;
+                for (int base = 0; base < n; base += LPL) {
+                    const int pool = base + gl;
+                    if (pool < n) {
+                        const uint2_t *cp = reinterpret_cast<const uint2_t *>(row + (size_t)pool * 6);
+                        const uint2_t a = cp[0], b = cp[1], d = cp[2];
+                        const uint32_t c[NA] = {a.x, a.y, b.x, b.y, d.x, d.y};
+#pragma unroll
+                        for (int j = 0; j < NA; ++j) tot += ((mask >> j) & 1) ? c[j] : 0u;
+                    }
+                }
+#pragma unroll
+                for (int off = LPL / 2; off >= 1; off >>= 1) tot += __shfl_xor(tot, off);
+                const double total = (double)tot;
+                const bool scale = total > 34.0;
+                const double coef = 34.0 / total; // fisher_exact_test.rs:50-58
+                // scaled cells; non-zero rows compacted into LDS in pool order; column sums packed 6 x 6 bits (each <= 34)
+                unsigned long long csp = 0;
+                int nr = 0;
+                for (int base = 0; base < n; base += LPL) {
+                    const int pool = base + gl;
+                    unsigned long long cells = 0;
+                    int rs = 0;
+                    if (pool < n) {
+                        const uint2_t *cp = reinterpret_cast<const uint2_t *>(row + (size_t)pool * 6);
+                        const uint2_t a = cp[0], b = cp[1], d = cp[2];
+                        const uint32_t c[NA] = {a.x, a.y, b.x, b.y, d.x, d.y};
+#pragma unroll
+                        for (int j = 0; j < NA; ++j) {
+                            const double cv = ((mask >> j) & 1) ? (double)c[j] : 0.0;
+                            const double sv = scale ? floor(cv * coef) : cv;
+                            const int v = min((int)sv, 34);
+                            rs += v;
+                            cells |= (unsigned long long)v << (8 * j);
+                            csp += (unsigned long long)v << (6 * j);
+                        }
+                    }
+                    const bool nz = rs > 0;
+                    unsigned long long bal = __ballot(nz);
+                    if (LPL < 64) bal = (bal >> (gw * LPL)) & ((1ull << (LPL & 63)) - 1ull);
+                    const int at = nr + __popcll(bal & ((1ull << gl) - 1ull));
+                    if (nz && at < FI_MAXR) { s_cells[g][at] = cells; s_rpos[g][at] = (unsigned short)pool; s_rs[g][at] = (unsigned char)min(rs, 34); }
+                    nr += __popcll(bal);
+                }
+                nr = min(nr, FI_MAXR - 2);
+#pragma unroll
+                for (int off = LPL / 2; off >= 1; off >>= 1) csp += __shfl_xor(csp, off);
+                // columns: the surviving alleles in column order; the non-zero ones compacted (sum and index among the survivors, a byte each)
+                unsigned long long ccp = 0, cposp = 0;
+                int nc = 0, lastc = -1, ntot = 0;
+#pragma unroll
+                for (int j = 0; j < NA; ++j) {
+                    if ((mask >> j) & 1) {
+                        const int v = min((int)((csp >> (6 * j)) & 63), 34);
+                        if (p < PG_MAX_OUT) idbits |= (unsigned)j << (3 * p);
+                        lastc = -1;
+                        if (v > 0) {
+                            ccp |= (unsigned long long)v << (8 * nc);
+                            cposp |= (unsigned long long)p << (8 * nc);
+                            lastc = nc; // (stays only if this is the last surviving allele)
+                            ++nc;
+                        }
+                        ntot += v;
+                        ++p;
+                    }
+                }
+                ntot = min(ntot, 34);
+                fi_wave_sync();
+                const int lastr = (nr > 0 && (int)s_rpos[g][nr - 1] == n - 1) ? nr - 1 : -1;
+                // lp = sum F[rs_i] + sum F[cs_j], rows first (zero rows and columns add F[0] = 0); the observed table, row-major
+                double lp = 0.0, so = 0.0;
+                for (int i = 0; i < nr; ++i) lp = lp + sF[s_rs[g][i]];
+                for (int j = 0; j < nc; ++j) lp = lp + sF[fi_byte(ccp, j)];
+                for (int i = 0; i < nr; ++i) {
+                    const unsigned long long cells = s_cells[g][i];
+                    for (int j = 0; j < NA; ++j) so = so + sF[fi_byte(cells, j)];
+                }
+                // the rebuilt tables, one per (t_r, t_c) and lane of the group
+                const int ntab = (nr + 1) * (nc + 1);
+                double pext = 0.0;
+                for (int q0 = 0; q0 < ntab; q0 += LPL) {
+                    const int q = q0 + gl;
+                    const bool on = q < ntab;
+                    const int tr = on ? q / (nc + 1) : 0, tc = on ? q - tr * (nc + 1) : 0;
+                    // how many (max_i, max_j) give this (t_r, t_c)
+                    int mr, mc;
+                    if (nr == 0) mr = n;
+                    else if (tr == 0) mr = (int)s_rpos[g][0] + 1;
+                    else if (tr < nr) mr = (int)s_rpos[g][tr] - (int)s_rpos[g][tr - 1];
+                    else mr = n - 1 - (int)s_rpos[g][nr - 1];
+                    if (nc == 0) mc = p;
+                    else if (tc == 0) mc = fi_byte(cposp, 0) + 1;
+                    else if (tc < nc) mc = fi_byte(cposp, tc) - fi_byte(cposp, tc - 1);
+                    else mc = p - 1 - fi_byte(cposp, nc - 1);
+                    unsigned long long crem = ccp; // the columns' remainders, a byte each
+                    double s = 0.0;
+                    int filled = 0;
+                    for (int i = 0; i < nr; ++i) { // forward, row-major (fisher_exact_test.rs:76-93)
+                        int rrem = s_rs[g][i];
+                        for (int j = 0; j < nc; ++j) {
+                            const int mx = min(rrem, fi_byte(crem, j));
+                            const bool keep = i == lastr || j == lastc || !(i < tr || j < tc);
+                            const int v = keep ? mx : 0;
+                            s = s + sF[v];
+                            rrem -= v; crem -= (unsigned long long)v << (8 * j); filled += v;
+                        }
+                        s_rfin[g][i][gl] = (unsigned char)rrem;
+                    }
+                    for (int j = nc - 1; j >= 0; --j) { // backward: columns descending, rows descending inside (:94-111)
+                        int cr = fi_byte(crem, j);
+                        for (int i = nr - 1; i >= 0; --i) {
+                            const int rrem = s_rfin[g][i][gl];
+                            const int mx = min(rrem, cr);
+                            s = s + sF[mx];
+                            s_rfin[g][i][gl] = (unsigned char)(rrem - mx);
+                            cr -= mx; filled += mx;
+                        }
+                    }
+                    const double ph = exp10(lp - (s + sF[min(filled, 34)])); // fisher_exact_test.rs:20-30
+                    pext = pext + ((on && mr > 0 && mc > 0) ? (double)(mr * mc) * ph : 0.0);
+                }
+#pragma unroll
+                for (int off = LPL / 2; off >= 1; off >>= 1) pext += __shfl_xor(pext, off);
+                pobs = exp10(lp - (so + sF[ntot]));
+                pval = pobs + pext;
+            }
+            if (gl == 0) { s_no[wv][u] = alive ? p : 0; s_ids[wv][u] = idbits; s_po[wv][u] = pobs; s_pv[wv][u] = pval; }
+            fi_wave_sync(); // the group's next locus rewrites the rows
+        }
+        fi_wave_sync();
+        if (lane < nl) {
+            const int64_t l = l0 + lane;
+            const int no = s_no[wv][lane];
+            const unsigned int idb = s_ids[wv][lane];
+            n_out[l] = no;
+            pobs_out[l] = s_po[wv][lane];
+            pval_out[l] = s_pv[wv][lane];
+            for (int r = 0; r < PG_MAX_OUT; ++r)
+                if (r < no) ids_out[(size_t)r * (size_t)L + (size_t)l] = (int)((idb >> (3 * r)) & 7);
+        }
+        fi_wave_sync();
+    }
+}
+
+int fisher_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const double *pool_sizes, const pg_filter *flt,
+               int32_t *n_out, int32_t *ids, double *pobs, double *pval) {
+    PG_CHECK(ctx, counts_dev && pool_sizes && flt && n_out && ids && pobs && pval, "fisher: null pointer");
+    PG_CHECK(ctx, L > 0 && n >= 1, "fisher: bad shape L=%lld n=%d", (long long)L, n);
+    PG_CHECK(ctx, (reinterpret_cast<uintptr_t>(counts_dev) & 15) == 0, "fisher: counts must be 16-byte aligned");
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<double> w(n);
+    double total = 0.0;
+    for (int i = 0; i < n; ++i) total = total + pool_sizes[i];
+    for (int i = 0; i < n; ++i) w[i] = pool_sizes[i] / total; // sync.rs:266-268
+    const int M = stream_period(n);
+    PG_CHECK(ctx, (int64_t)64 * M * n * 24 < ((int64_t)1 << 31), "fisher: too many pools (%d) for one unit of loci", n);
+    const size_t slots = (size_t)((L + 63) / 64) * 64;
+    // workspace: [w][flags: i32 per locus][second list: L x i64][the same, grouped][its length]
+    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    size_t off = 0;
+    const size_t o_w = off; off = al16(off + sizeof(double) * n);
+    const size_t o_flags = off; off = al16(off + sizeof(int32_t) * slots);
+    const size_t o_second = off; off = al16(off + sizeof(int64_t) * (size_t)L);
+    const size_t o_sorted = off; off = al16(off + sizeof(int64_t) * ((size_t)L + 64 * LO_NB));
+    const size_t o_count = off; off = al16(off + 8 * (SC_WORDS + 1));
+    int rc = pg_ws_reserve(ctx, off);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(ctx->ws);
+    StreamWs W;
+    W.table = reinterpret_cast<double *>(ws + o_w);
+    W.Y = nullptr; W.tcoef = nullptr; W.rec = nullptr;
+    W.flags = reinterpret_cast<int32_t *>(ws + o_flags);
+    W.second = reinterpret_cast<int64_t *>(ws + o_second);
+    W.sorted = reinterpret_cast<int64_t *>(ws + o_sorted);
+    W.second_count = reinterpret_cast<unsigned long long *>(ws + o_count);
+    PG_HIP(ctx, hipMemcpyAsync(W.table, w.data(), sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    LocusParams P;
+    std::memset(&P, 0, sizeof P);
+    P.L = L; P.n = n; P.k = 1; P.k_total = 1; P.t0 = 0;
+    P.remove_ns = flt->remove_ns ? 1 : 0;
+    P.pshift = 0; // flags are indexed by the locus
+    P.sort_desc = 0;
+    P.min_cov = (double)flt->min_coverage_depth;
+    P.maf = flt->min_allele_frequency;
+    P.max_miss = flt->max_missingness_rate;
+    P.qband = 8.0 * ((double)n + 16.0) * 2.220446049250313e-16;
+    P.y_complete = 1;
+    int64_t listed = 0;
+    bool complaint = false;
+    // the filter, exactly as the loader runs it: the streaming kernel whatever the context ran before (OP_LOAD never takes, and
+    // never updates, the kernel choice of ols_iter / chisq_test)
+    rc = launch_passes<OP_LOAD>(ctx, PG_K_FISHER, counts_dev, W, StreamOut{nullptr, nullptr, nullptr, nullptr, nullptr}, P, 1,
+                                flt->remove_ns != 0, &listed, &complaint);
+    if (rc) return rc;
+    PG_CHECK(ctx, !complaint, "fisher: a count of 2^29 (536 870 912) reads or more: beyond what the streaming pass sums exactly");
+    FisherTab tab;
+    for (int x = 0; x < 35; ++x) {
+        double out = 0.0;
+        for (int i = 2; i <= x; ++i) out = out + std::log10((double)i);
+        tab.F[x] = out;
+    }
+    const int64_t nunits = (L + FI_UNIT - 1) / FI_UNIT, want = (nunits + LO_WAVES - 1) / LO_WAVES, cap = (int64_t)ctx->cus * 8;
+    pg_prof_begin(ctx, PG_K_FISHER | PG_PROF_CONT);
+    // lanes per locus: enough that a lane reads at most eight pools, as few as that allows
+    const dim3 grid((unsigned)(want < cap ? want : cap)), block(LO_THREADS);
+    if (n <= 128)
+        hipLaunchKernelGGL(k_fisher<16>, grid, block, 0, ctx->stream, counts_dev, (const int32_t *)W.flags, L, n, tab, n_out, ids, pobs, pval);
+    else if (n <= 256)
+        hipLaunchKernelGGL(k_fisher<32>, grid, block, 0, ctx->stream, counts_dev, (const int32_t *)W.flags, L, n, tab, n_out, ids, pobs, pval);
+    else
+        hipLaunchKernelGGL(k_fisher<64>, grid, block, 0, ctx->stream, counts_dev, (const int32_t *)W.flags, L, n, tab, n_out, ids, pobs, pval);
+    pg_prof_end(ctx);
+    PG_HIP(ctx, hipGetLastError());
+    ctx->lo_last_L = L; ctx->lo_last_listed = listed;
+    return PG_OK;
+}
+
+int fisher_host(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const double *pool_sizes, const pg_filter *flt,
+                int32_t *n_out, int32_t *ids, double *pobs, double *pval) {
+    PG_CHECK(ctx, counts && n_out && ids && pobs && pval && L > 0 && n >= 1, "fisher: bad arguments");
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t cb = ((size_t)L * n * 6 * sizeof(uint32_t) + 15) & ~(size_t)15;
+    const size_t sb = (size_t)L * sizeof(double), ib = (size_t)L * PG_MAX_OUT * sizeof(int32_t);
+    char *d = nullptr;
+    PG_HIP(ctx, hipMalloc((void **)&d, cb + 2 * sb + ib + (size_t)L * 4 + 256));
+    uint32_t *cd = reinterpret_cast<uint32_t *>(d);
+    double *od = reinterpret_cast<double *>(d + cb);
+    double *pd = od + L;
+    int32_t *idd = reinterpret_cast<int32_t *>(pd + L);
+    int32_t *nd = idd + (size_t)L * PG_MAX_OUT;
+    int rc = PG_OK;
+    if (hipMemcpyAsync(cd, counts, (size_t)L * n * 6 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = pg_fail(ctx, PG_ERR_HIP, "fisher: H2D failed");
+    if (!rc) rc = fisher_dev(ctx, cd, L, n, pool_sizes, flt, nd, idd, od, pd);
+    if (!rc) {
+        bool okc = hipMemcpyAsync(n_out, nd, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        okc = okc && hipMemcpyAsync(ids, idd, ib, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        okc = okc && hipMemcpyAsync(pobs, od, sb, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        okc = okc && hipMemcpyAsync(pval, pd, sb, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        if (!okc) rc = pg_fail(ctx, PG_ERR_HIP, "fisher: D2H failed");
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
 } // namespace
 
 extern "C" int pg_locus_op_stats(const pg_ctx *ctx, int64_t *loci, int64_t *listed) {
@@ -2978,6 +3288,21 @@ extern "C" int pg_chisq_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, in
     if (!ctx) return PG_ERR_INVALID;
     return run_locus_op_host<OP_CHISQ>(ctx, PG_K_CHISQ, counts, L, n, pool_sizes, filter, nullptr, 1, n_out,
                                        allele_ids, nullptr, chi2, pval);
+}
+
+extern "C" int pg_fisher_batch_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const double *pool_sizes,
+                                   const pg_filter *filter, int32_t *n_out_dev, int32_t *allele_ids_dev,
+                                   double *p_observed_dev, double *pval_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    return fisher_dev(ctx, counts_dev, L, n, pool_sizes, filter, n_out_dev, allele_ids_dev, p_observed_dev, pval_dev);
+}
+
+extern "C" int pg_fisher_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const double *pool_sizes,
+                               const pg_filter *filter, int32_t *n_out, int32_t *allele_ids, double *p_observed,
+                               double *pval) {
+    if (!ctx) return PG_ERR_INVALID;
+    PG_CHECK(ctx, pool_sizes && filter, "fisher: null pointer");
+    return fisher_host(ctx, counts, L, n, pool_sizes, filter, n_out, allele_ids, p_observed, pval);
 }
 
 namespace {

@@ -5,6 +5,7 @@ Method names follow the reference operators they stand in for:
   ols_iterate          gwas::ols_iterate             (gwas/ols.rs:201-276)
   correlation          gwas::correlation             (gwas/correlation_test.rs:73-129)
   chisq                tables::chisq                 (tables/chisq_test.rs:5-47)
+  fisher               tables::fisher                (tables/fisher_exact_test.rs:32-130)
   gp_ols               gp::ols                       (gp/ols.rs:8-101)
 All heavy arguments are torch CUDA tensors (device memory owned by torch); results are
 torch CUDA tensors.  Everything is computed by libpoolgen_hip.so.
@@ -287,6 +288,25 @@ class Engine:
             return n_out, ids, chi2, pv
         live = torch.arange(5, device=dev)[None, :] < n_out[:, None]
         return n_out, torch.where(live, ids.T, torch.tensor(-1, dtype=torch.int32, device=dev)), chi2, pv
+
+    def fisher(self, counts, pool_sizes, flt: Filter, raw: bool = False):
+        """tables::fisher: n_out, ids, p_observed, pval (= p_observed + p_extremes) per locus; a locus' result depends on
+        its own counts, the filter and n only."""
+        L, n, _ = counts.shape
+        ps = _host_f64(pool_sizes)
+        dev = counts.device
+        n_out = torch.empty(L, dtype=torch.int32, device=dev)
+        ids = torch.empty((5, L), dtype=torch.int32, device=dev)   # the surviving alleles of the row in the slots below n_out
+        pobs = torch.empty(L, dtype=torch.float64, device=dev)
+        pv = torch.empty(L, dtype=torch.float64, device=dev)
+        f = flt.to_c()
+        self._check(self._lib.pg_fisher_batch_dev(self._ctx, self._dev(counts, torch.int32), L, n, ps.ctypes.data,
+                                                  C.byref(f), n_out.data_ptr(), ids.data_ptr(),
+                                                  pobs.data_ptr(), pv.data_ptr()), "pg_fisher_batch_dev")
+        if raw:
+            return n_out, ids, pobs, pv
+        live = torch.arange(5, device=dev)[None, :] < n_out[:, None]
+        return n_out, torch.where(live, ids.T, torch.tensor(-1, dtype=torch.int32, device=dev)), pobs, pv
 
     def last_listed(self):
         """(loci, listed) of the last batch operator call: how many loci its streaming pass handed to the second pass."""
