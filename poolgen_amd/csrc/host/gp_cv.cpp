@@ -1,7 +1,7 @@
 // gp_cv.cpp -- see gp_cv.h
 #include "gp_cv.h"
+#include "gpu_mem.h"
 #include "host_util.h"
-#include <hip/hip_runtime.h>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -15,9 +15,6 @@ namespace {
 
 void ok(pg_ctx *ctx, int rc, const char *what) {
     if (rc != PG_OK) throw std::runtime_error(std::string(what) + ": " + pg_last_error(ctx));
-}
-void hip_ok(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 FILE *create_new_file(const std::string &name) {
     const int fd = ::open(name.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
@@ -112,15 +109,13 @@ std::string gp_cross_validate(pg_ctx *ctx, const double *G_dev, int64_t p, int n
     const int nmod = 6;
     const int k = a.k_folds, r = a.n_reps;
     SplitMix64 rng(a.seed);
-    double *beta_dev = nullptr;
-    hip_ok(hipMalloc((void **)&beta_dev, sizeof(double) * (size_t)(p + 1) * m), "device memory for the coefficients");
+    const DeviceBuf<double> beta_buf(sizeof(double) * (size_t)(p + 1) * m, "device memory for the coefficients");
+    double *beta_dev = beta_buf.get();
     std::vector<double> xxt((size_t)n * n);
     { // the full-data X X^T once: every training subset of every fit uses a principal sub-block
-        double *S = nullptr;
-        hip_ok(hipMalloc((void **)&S, sizeof(double) * n * n), "device memory");
-        ok(ctx, pg_gp_xxt_dev(ctx, G_dev, p, n, ld, S), "X X^T");
-        hip_ok(hipMemcpy(xxt.data(), S, sizeof(double) * n * n, hipMemcpyDeviceToHost), "D2H");
-        (void)hipFree(S);
+        const DeviceBuf<double> S(sizeof(double) * n * n, "device memory");
+        ok(ctx, pg_gp_xxt_dev(ctx, G_dev, p, n, ld, S.get()), "X X^T");
+        hip_ok(hipMemcpy(xxt.data(), S.get(), sizeof(double) * n * n, hipMemcpyDeviceToHost), "D2H");
     }
     const GpData data{ctx, G_dev, p, n, ld, &Y, m, &xxt, &rng};
     auto fit = [&](int mi, const std::vector<int64_t> &rows, std::string &name) { name = functions[mi](data, rows, beta_dev); };
@@ -216,7 +211,6 @@ std::string gp_cross_validate(pg_ctx *ctx, const double *G_dev, int64_t p, int n
         fwrite(text.data(), 1, text.size(), fo);
         fclose(fo);
     }
-    (void)hipFree(beta_dev);
     return out;
 }
 

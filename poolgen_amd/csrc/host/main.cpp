@@ -6,6 +6,8 @@
 // of scope and reported as such.
 #include "host_util.h"
 #include "pileup.h"
+#include "gpu_mem.h"
+#include "piece_reader.h"
 #include "../../../include/poolgen_hip.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -14,7 +16,6 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
-#include <future>
 #include <iostream>
 #include <climits>
 #include <map>
@@ -32,7 +33,6 @@
 #include <time.h>
 #include <sys/stat.h>
 #include <fcntl.h>
-#include <sys/mman.h>
 #include <unistd.h>
 
 using namespace pgh;
@@ -164,6 +164,18 @@ static Args parse_args(int argc, char **argv) {
     return a;
 }
 
+static PileupFilter pileup_filter(const Args &a, const std::vector<double> &pool_sizes) {
+    PileupFilter pf;
+    pf.remove_ns = !a.keep_ns;
+    pf.keep_lowercase_reference = a.keep_lowercase_reference;
+    pf.max_base_error_rate = a.max_base_error_rate;
+    pf.min_coverage_depth = a.min_coverage_depth;
+    pf.min_coverage_breadth = a.min_coverage_breadth;
+    pf.min_allele_frequency = a.min_allele_frequency;
+    pf.pool_sizes = pool_sizes;
+    return pf;
+}
+
 static std::string basename_no_ext(const std::string &f) { // sync.rs:889-902
     const auto p = f.rfind('.');
     return p == std::string::npos ? std::string() : f.substr(0, p);
@@ -287,7 +299,7 @@ struct Lap {
 };
 
 // The results are on disk and the file name is printed: end the process here.  Releasing tens of GB of device and pinned
-// memory buffer by buffer (destructors, hipFree, the HIP runtime's shutdown) took 0.3 s of a 1.4 s run; the driver
+// memory buffer by buffer (destructors, device frees, the HIP runtime's shutdown) took 0.3 s of a 1.4 s run; the driver
 // reclaims everything when the process ends.  PGH_CLEAN_EXIT=1 keeps the orderly teardown (leak checkers).
 static void stamp(const char *what) { // PGH_TIMING=1: the wall clock itself, so that a wrapper can see what lies outside the laps
     if (!std::getenv("PGH_TIMING")) return;
@@ -314,56 +326,18 @@ static int done_ok() {
 // ---------------------------------------------------------------------------------------------------------
 struct UnsortedInput : std::runtime_error { using std::runtime_error::runtime_error; };
 
-// The text of a piece is not looked at again once it is parsed: its pages leave the mapping here, on a thread of their own,
-// instead of all at once when the process ends -- unmapping 27 GB of touched file pages (6.6 M page-table entries, one thread,
-// inside exit) was 0.25 s per 5 GB of input AFTER the program's last line (profiles/r04_stream_*.log).  MADV_DONTNEED on a
-// read-only private file mapping only drops the entries; the page cache keeps the file.  PGH_KEEP_MAPPED=1 leaves them.
-// The helper threads belong to an object that lives SHORTER than the mapping (declare it after the MappedFile): its destructor
-// joins them, so that no madvise is still on its way when the mapping goes (an exception, the fall-back to the whole-file path)
-// and the address range may already belong to something else -- where MADV_DONTNEED would discard live data.
-class TextDropper {
-    std::mutex m_;
-    std::vector<std::thread> th_;
-    const bool keep_ = std::getenv("PGH_KEEP_MAPPED") != nullptr;
-public:
-    TextDropper() = default;
-    TextDropper(const TextDropper &) = delete;
-    TextDropper &operator=(const TextDropper &) = delete;
-    void operator()(const char *b, const char *e) {
-        if (keep_) return;
-        const uintptr_t pg = (uintptr_t)sysconf(_SC_PAGESIZE);
-        const uintptr_t lo = ((uintptr_t)b + pg - 1) / pg * pg, hi = (uintptr_t)e / pg * pg;
-        if (hi <= lo || hi - lo < ((uintptr_t)1 << 20)) return;
-        std::lock_guard<std::mutex> g(m_);
-        th_.emplace_back([lo, hi] { (void)::madvise(reinterpret_cast<void *>(lo), hi - lo, MADV_DONTNEED); });
-    }
-    ~TextDropper() {
-        for (auto &t : th_) if (t.joinable()) t.join();
-    }
-};
-
 // The counts of a parsed batch -> the 32-bit device buffer the operators read.  A 16-bit batch (every count fits: the
 // usual case) crosses the bus at half the size and is widened on the device; `stage16` is a reusable device scratch.
 struct CountsUpload {
-    uint16_t *stage16 = nullptr;
-    size_t cap16 = 0;
-    ~CountsUpload() { if (stage16) (void)hipFree(stage16); }
+    DeviceBuf<uint16_t> stage16;
     void operator()(Ctx &gpu, const SyncBatch &sb, uint32_t *counts_dev) {
-        auto hip_ok = [](hipError_t e, const char *what) {
-            if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-        };
         if (!sb.counts16) {
             hip_ok(hipMemcpyAsync(counts_dev, sb.counts, sb.counts_bytes(), hipMemcpyHostToDevice, nullptr), "H2D counts");
             return;
         }
-        if (sb.counts_bytes() > cap16) {
-            if (stage16) hip_ok(hipFree(stage16), "free");
-            stage16 = nullptr;
-            cap16 = sb.counts_bytes() + sb.counts_bytes() / 8;
-            hip_ok(hipMalloc((void **)&stage16, cap16), "device memory for the compact counts");
-        }
-        hip_ok(hipMemcpyAsync(stage16, sb.counts16, sb.counts_bytes(), hipMemcpyHostToDevice, nullptr), "H2D counts");
-        gpu.ok(pg_expand_counts_u16_dev(gpu.c, stage16, (int64_t)sb.L * sb.n * 6, counts_dev), "expand counts");
+        stage16.reserve(sb.counts_bytes(), "device memory for the compact counts");
+        hip_ok(hipMemcpyAsync(stage16.get(), sb.counts16, sb.counts_bytes(), hipMemcpyHostToDevice, nullptr), "H2D counts");
+        gpu.ok(pg_expand_counts_u16_dev(gpu.c, stage16.get(), (int64_t)sb.L * sb.n * 6, counts_dev), "expand counts");
     }
 };
 
@@ -429,44 +403,79 @@ static void run_ranks(int n_ranks, F fn) { // fn(rank) on one thread per rank; t
     for (auto &e : err) if (e) std::rethrow_exception(e);
 }
 
+// The loader on counts that are on the device (pg_load_plan_dev / pg_load_emit[_cov]_dev): filter + frequencies per locus, one
+// column per surviving allele of a p x ld locus-major matrix in HBM, the loci in the order of `order_dev` (null: as they come),
+// the n2 kept pools placed by `pool_map`.  The columns' labels come back to the host.  p == 0: nothing else is filled.
+struct LoadedMatrix {
+    int64_t p = 0;
+    DeviceBuf<double> G, coverages;  // coverages: laid out like the matrix (pg_load_emit_cov_dev); only when asked for
+    std::vector<int64_t> col_locus;  // per column: its locus (a row of the counts) ...
+    std::vector<int32_t> col_allele; // ... and its allele (an index into ALLELES)
+};
+
+static LoadedMatrix load_matrix(Ctx &gpu, const uint32_t *counts_dev, int64_t L, int n, const std::vector<double> &pool_sizes,
+                                const pg_filter &flt, bool keep_p_minus_1, const int64_t *order_dev, const std::vector<int32_t> &pool_map,
+                                int n2, int64_t ld, bool with_coverages) {
+    LoadedMatrix m;
+    gpu.ok(pg_load_plan_dev(gpu.c, counts_dev, L, n, pool_sizes.data(), &flt, keep_p_minus_1 ? 1 : 0, order_dev, &m.p), "load");
+    if (m.p <= 0) return m;
+    const size_t p = (size_t)m.p;
+    m.G.reset(sizeof(double) * p * ld, "device memory for the genotype matrix");
+    DeviceBuf<int64_t> col_locus_dev(sizeof(int64_t) * p, "device memory");
+    DeviceBuf<int32_t> col_allele_dev(sizeof(int32_t) * p, "device memory");
+    if (with_coverages) {
+        m.coverages.reset(sizeof(double) * p * ld, "device memory for the coverages");
+        gpu.ok(pg_load_emit_cov_dev(gpu.c, pool_map.data(), n2, m.G.get(), ld, col_locus_dev.get(), col_allele_dev.get(), m.coverages.get()), "load");
+    } else
+        gpu.ok(pg_load_emit_dev(gpu.c, pool_map.data(), n2, m.G.get(), ld, col_locus_dev.get(), col_allele_dev.get()), "load");
+    m.col_locus.resize(p); m.col_allele.resize(p);
+    hip_ok(hipMemcpy(m.col_locus.data(), col_locus_dev.get(), sizeof(int64_t) * p, hipMemcpyDeviceToHost), "D2H labels");
+    hip_ok(hipMemcpy(m.col_allele.data(), col_allele_dev.get(), sizeof(int32_t) * p, hipMemcpyDeviceToHost), "D2H labels");
+    return m;
+}
+
+// The CSV of ols_iter_with_kinship / mle_iter_with_kinship: p coefficients x k traits of beta / pval; `label(i, text)` appends
+// the "chr,pos,allele" of coefficient i.
+template <typename Label>
+static void write_kinship_csv(const std::string &out, int64_t p, int k, const std::vector<double> &beta, const std::vector<double> &pval,
+                              int n_threads, Label label) {
+    FILE *fo = create_new(out);
+    fputs("#chr,pos,alleles,phenotype,statistic,pvalue\n", fo); // ols.rs:409
+    write_rows_parallel(fo, (int64_t)k * p, n_threads, [&](int64_t r, std::string &text) {
+        const int64_t j = r / p, i = r - j * p; // rows are trait-major (ols.rs:411-433)
+        label(i, text);
+        text += ",Pheno_"; text += std::to_string(j); text.push_back(',');
+        append_rust_display(text, beta[(size_t)i * k + j]); text.push_back(',');
+        append_rust_display(text, pval[(size_t)i * k + j]); text.push_back('\n');
+    });
+    fclose(fo);
+}
+
 struct KinRank {
     int rank = 0, device = 0, threads = 1, c0 = 0, c1 = 0;
     std::unique_ptr<Ctx> own;
     Ctx *gpu = nullptr;
-    std::vector<double *> Gs;                         // the rank's pieces of the frequency matrix, resident in HBM
+    // the rank's pieces of the frequency matrix, resident in HBM (owned: an exception on the way -- unsorted input, out of memory --
+    // must not leave the pieces behind: the caller may fall back to the whole-file path)
+    std::vector<DeviceBuf<double>> Gs;
     std::vector<int64_t> ps;
     std::vector<std::string> chrom_names;             // the rank's dictionary
     std::vector<int32_t> lab_chr;                     // per column
     std::vector<uint64_t> lab_pos;
     std::vector<char> lab_al;
     std::vector<double> S_total;
-    double *S_dev = nullptr;
-    uint32_t *counts_dev = nullptr;
-    struct Slot { void *p = nullptr; size_t cap = 0; } slot[2];
+    DeviceBuf<double> S_dev;
     std::string first_chrom, last_chrom;
     uint64_t first_pos = 0, last_pos = 0;
     bool have_last = false;
     int64_t p = 0, col0 = 0;
     int m = 0;
     double t_wait = 0, t_host = 0, t_gpu = 0;
-    KinRank() = default;
-    KinRank(const KinRank &) = delete;
-    KinRank &operator=(const KinRank &) = delete;
-    ~KinRank() { // an exception on the way (unsorted input, out of memory) must not leave the pieces behind: the caller may fall back to the whole-file path
-        for (double *g : Gs) (void)hipFree(g);
-        if (S_dev) (void)hipFree(S_dev);
-        if (counts_dev) (void)hipFree(counts_dev);
-        for (auto &sl : slot) if (sl.p) (void)hipHostFree(sl.p);
-    }
 };
 
 static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, size_t chunk_bytes, bool is_pileup,
                                 const PileupFilter &pf, const pg_filter &flt, const RankSetup &rs) {
-    auto hip_ok = [](hipError_t e, const char *what) {
-        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-    };
     const MappedFile mf(a.fname);
-    TextDropper drop_parsed_text; // (after mf: joined before the mapping goes)
     const int R = rs.n_ranks;
     const size_t want_pieces = std::max<size_t>((size_t)R, (mf.size() + chunk_bytes - 1) / chunk_bytes);
     const std::vector<size_t> cuts = mf.cuts(want_pieces);
@@ -502,42 +511,19 @@ static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &l
         gate.pass([&] {
             hip_ok(hipSetDevice(K.device), "hipSetDevice");
             K.S_total.assign((size_t)n2 * n2, 0.0);
-            hip_ok(hipMalloc((void **)&K.S_dev, sizeof(double) * n2 * n2), "device memory");
+            K.S_dev.reset(sizeof(double) * n2 * n2);
         });
         if (rs.rccl) // collective over the rank threads: entered by all of them or by none, and its outcome agreed on
             gate.pass([&] { gpu.ok(pg_comm_init_rank(gpu.c, rs.id, R, r), "RCCL communicator"); });
         if (K.c0 >= K.c1) return;
-        auto alloc_for = [&K](int i) { // two pinned buffers that grow on demand and are handed out in turn
-            SyncAlloc al;
-            al.alloc = [&K, i](size_t bytes) -> void * {
-                if (bytes > K.slot[i].cap) {
-                    if (K.slot[i].p) (void)hipHostFree(K.slot[i].p);
-                    K.slot[i].p = nullptr; K.slot[i].cap = 0;
-                    const size_t want = bytes + bytes / 8;
-                    if (hipHostMalloc(&K.slot[i].p, want, hipHostMallocDefault) != hipSuccess) return nullptr;
-                    K.slot[i].cap = want;
-                }
-                return K.slot[i].p;
-            };
-            al.release = [](void *) {};
-            return al;
-        };
-        auto parse_piece = [&](int c) {
-            (void)hipSetDevice(K.device); // the pinned allocator runs on the parser's thread
-            const char *b = mf.data() + cuts[c], *e = mf.data() + cuts[c + 1];
-            SyncBatch parsed = is_pileup ? parse_pileup_buffer(b, e, K.threads, pf, alloc_for(c & 1))
-                                         : parse_sync_buffer(b, e, K.threads, n, alloc_for(c & 1), true);
-            drop_parsed_text(b, e);
-            return parsed;
-        };
-        std::future<SyncBatch> next = std::async(std::launch::async, parse_piece, K.c0);
+        // (the pinned slots, the counts and the 16-bit scratch live to the end of this phase only)
+        PieceReader pieces(mf, cuts, K.c0, K.c1, K.device, K.threads, is_pileup, pf, n, true);
         std::vector<double> S_piece((size_t)n2 * n2);
-        size_t counts_cap = 0;
+        DeviceBuf<uint32_t> counts_dev;
         CountsUpload upload;
-        for (int c = K.c0; c < K.c1; ++c) {
+        while (pieces.more()) {
             double t0 = clk();
-            SyncBatch sb = next.get();
-            if (c + 1 < K.c1) next = std::async(std::launch::async, parse_piece, c + 1);
+            SyncBatch sb = pieces.next();
             K.t_wait += clk() - t0; t0 = clk();
             if (sb.L == 0) continue;
             if (sb.n != n) throw std::runtime_error("the number of pools in the input and in the phenotype file differ");
@@ -553,31 +539,14 @@ static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &l
                 K.last_pos = sb.pos[l];
             }
             K.t_host += clk() - t0; t0 = clk();
-            const size_t bytes32 = sizeof(uint32_t) * (size_t)sb.L * n * 6;
-            if (bytes32 > counts_cap) {
-                if (K.counts_dev) hip_ok(hipFree(K.counts_dev), "free");
-                K.counts_dev = nullptr;
-                counts_cap = bytes32 + bytes32 / 8;
-                hip_ok(hipMalloc((void **)&K.counts_dev, counts_cap), "device memory for the counts");
-            }
-            upload(gpu, sb, K.counts_dev);
-            int64_t pc = 0;
-            gpu.ok(pg_load_plan_dev(gpu.c, K.counts_dev, sb.L, n, ph.pool_sizes.data(), &flt, a.keep_p_minus_1 ? 1 : 0, nullptr, &pc), "load");
+            counts_dev.reserve(sizeof(uint32_t) * (size_t)sb.L * n * 6, "device memory for the counts");
+            upload(gpu, sb, counts_dev.get());
+            LoadedMatrix piece = load_matrix(gpu, counts_dev.get(), sb.L, n, ph.pool_sizes, flt, a.keep_p_minus_1, nullptr, pool_map, n2, ld, false);
+            const int64_t pc = piece.p;
             if (pc == 0) continue;
-            double *G = nullptr;
-            int64_t *col_locus_dev = nullptr;
-            int32_t *col_allele_dev = nullptr;
-            hip_ok(hipMalloc((void **)&G, sizeof(double) * (size_t)pc * ld), "device memory for the genotype matrix");
-            K.Gs.push_back(G);
+            const double *G = piece.G.get();
+            K.Gs.push_back(std::move(piece.G));
             K.ps.push_back(pc);
-            hip_ok(hipMalloc((void **)&col_locus_dev, sizeof(int64_t) * pc), "device memory");
-            hip_ok(hipMalloc((void **)&col_allele_dev, sizeof(int32_t) * pc), "device memory");
-            gpu.ok(pg_load_emit_dev(gpu.c, pool_map.data(), n2, G, ld, col_locus_dev, col_allele_dev), "load");
-            std::vector<int64_t> col_locus(pc);
-            std::vector<int32_t> col_allele(pc);
-            hip_ok(hipMemcpy(col_locus.data(), col_locus_dev, sizeof(int64_t) * pc, hipMemcpyDeviceToHost), "D2H labels");
-            hip_ok(hipMemcpy(col_allele.data(), col_allele_dev, sizeof(int32_t) * pc, hipMemcpyDeviceToHost), "D2H labels");
-            (void)hipFree(col_locus_dev); (void)hipFree(col_allele_dev);
             K.t_gpu += clk() - t0; t0 = clk();
             std::vector<int32_t> remap(sb.chrom_names.size());
             for (size_t i = 0; i < sb.chrom_names.size(); ++i) {
@@ -587,19 +556,17 @@ static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &l
                 remap[i] = g;
             }
             for (int64_t q = 0; q < pc; ++q) {
-                K.lab_chr.push_back(remap[sb.chrom_id[col_locus[q]]]);
-                K.lab_pos.push_back(sb.pos[col_locus[q]]);
-                K.lab_al.push_back(ALLELES[col_allele[q]]);
+                K.lab_chr.push_back(remap[sb.chrom_id[piece.col_locus[q]]]);
+                K.lab_pos.push_back(sb.pos[piece.col_locus[q]]);
+                K.lab_al.push_back(ALLELES[piece.col_allele[q]]);
             }
             K.t_host += clk() - t0; t0 = clk();
-            gpu.ok(pg_kinship_partial_dev(gpu.c, G, pc, n2, ld, K.S_dev), "kinship");
-            hip_ok(hipMemcpy(S_piece.data(), K.S_dev, sizeof(double) * n2 * n2, hipMemcpyDeviceToHost), "D2H kinship");
+            gpu.ok(pg_kinship_partial_dev(gpu.c, G, pc, n2, ld, K.S_dev.get()), "kinship");
+            hip_ok(hipMemcpy(S_piece.data(), K.S_dev.get(), sizeof(double) * n2 * n2, hipMemcpyDeviceToHost), "D2H kinship");
             for (size_t i = 0; i < K.S_total.size(); ++i) K.S_total[i] += S_piece[i];
             K.p += pc;
             K.t_gpu += clk() - t0;
         }
-        if (K.counts_dev) { (void)hipFree(K.counts_dev); K.counts_dev = nullptr; }
-        for (auto &sl : K.slot) if (sl.p) { (void)hipHostFree(sl.p); sl.p = nullptr; sl.cap = 0; }
     });
     if (std::getenv("PGH_TIMING"))
         for (const KinRank &K : ranks)
@@ -638,22 +605,19 @@ static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &l
         Ctx &gpu = *K.gpu;
         gate.pass([&] {
             hip_ok(hipSetDevice(K.device), "hipSetDevice");
-            hip_ok(hipMemcpy(K.S_dev, rs.rccl ? K.S_total.data() : S_host.data(), sizeof(double) * n2 * n2, hipMemcpyHostToDevice), "H2D kinship");
+            hip_ok(hipMemcpy(K.S_dev.get(), rs.rccl ? K.S_total.data() : S_host.data(), sizeof(double) * n2 * n2, hipMemcpyHostToDevice), "H2D kinship");
         });
-        if (rs.rccl) gpu.ok(pg_allreduce_sum_dev(gpu.c, K.S_dev, (int64_t)n2 * n2), "RCCL all-reduce of the kinship sums");
-        gpu.ok(pg_kinship_set(gpu.c, K.S_dev, p, n2, Y.data(), k, a.xxt, -1, &K.m, nullptr, nullptr), "ols_iter_with_kinship");
+        if (rs.rccl) gpu.ok(pg_allreduce_sum_dev(gpu.c, K.S_dev.get(), (int64_t)n2 * n2), "RCCL all-reduce of the kinship sums");
+        gpu.ok(pg_kinship_set(gpu.c, K.S_dev.get(), p, n2, Y.data(), k, a.xxt, -1, &K.m, nullptr, nullptr), "ols_iter_with_kinship");
         int64_t off = K.col0;
         for (size_t c = 0; c < K.Gs.size(); ++c) {
-            double *out_dev = nullptr;
             const size_t cnt = (size_t)K.ps[c] * k;
-            hip_ok(hipMalloc((void **)&out_dev, sizeof(double) * 3 * cnt), "device memory for the results");
-            gpu.ok(pg_ols_sweep_dev(gpu.c, K.Gs[c], K.ps[c], n2, ld, out_dev, out_dev + cnt, out_dev + 2 * cnt), "ols_iter_with_kinship");
+            DeviceBuf<double> out_dev(sizeof(double) * 3 * cnt, "device memory for the results");
+            gpu.ok(pg_ols_sweep_dev(gpu.c, K.Gs[c].get(), K.ps[c], n2, ld, out_dev.get(), out_dev.get() + cnt, out_dev.get() + 2 * cnt), "ols_iter_with_kinship");
             gpu.ok(pg_synchronize(gpu.c), "ols_iter_with_kinship");
-            hip_ok(hipMemcpy(beta.data() + (size_t)off * k, out_dev, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
-            hip_ok(hipMemcpy(pval.data() + (size_t)off * k, out_dev + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
-            (void)hipFree(out_dev);
-            (void)hipFree(K.Gs[c]);
-            K.Gs[c] = nullptr;
+            hip_ok(hipMemcpy(beta.data() + (size_t)off * k, out_dev.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+            hip_ok(hipMemcpy(pval.data() + (size_t)off * k, out_dev.get() + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+            K.Gs[c].reset(); // a piece leaves HBM right after its sweep
             off += K.ps[c];
         }
         K.Gs.clear();
@@ -668,40 +632,27 @@ static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &l
     // label of global column q: the rank whose range holds it
     std::vector<int64_t> starts;
     for (const KinRank &K : ranks) starts.push_back(K.col0);
-    auto label = [&](int64_t q, std::string &text) {
+    write_kinship_csv(out, p, k, beta, pval, a.n_threads, [&](int64_t i, std::string &text) {
+        // coefficient i carries label i of the (1+p)-long vectors whose entry 0 is "intercept" (ols.rs:421-425)
+        if (i == 0) { text += "intercept,0,intercept"; return; }
+        const int64_t q = i - 1;
         const int r = (int)(std::upper_bound(starts.begin(), starts.end(), q) - starts.begin()) - 1;
         const KinRank &K = ranks[r];
-        const int64_t i = q - K.col0;
-        text += K.chrom_names[K.lab_chr[i]]; text += ","; text += std::to_string(K.lab_pos[i]); text += ","; text.push_back(K.lab_al[i]);
-    };
-    FILE *fo = create_new(out);
-    fputs("#chr,pos,alleles,phenotype,statistic,pvalue\n", fo); // ols.rs:409
-    write_rows_parallel(fo, (int64_t)k * p, a.n_threads, [&](int64_t r, std::string &text) {
-        const int64_t j = r / p, i = r - j * p; // rows are trait-major (ols.rs:411-433)
-        // coefficient i carries label i of the (1+p)-long vectors whose entry 0 is "intercept" (ols.rs:421-425)
-        if (i == 0) text += "intercept,0,intercept";
-        else label(i - 1, text);
-        text += ",Pheno_"; text += std::to_string(j); text.push_back(',');
-        append_rust_display(text, beta[(size_t)i * k + j]); text.push_back(',');
-        append_rust_display(text, pval[(size_t)i * k + j]); text.push_back('\n');
+        const int64_t c = q - K.col0;
+        text += K.chrom_names[K.lab_chr[c]]; text += ","; text += std::to_string(K.lab_pos[c]); text += ","; text.push_back(K.lab_al[c]);
     });
-    fclose(fo);
     lap("format + write CSV");
     std::cout << out << "\n";
     return done_ok();
 }
 
-// fisher_exact_test / chisq_test / pearson_corr / ols_iter (main.rs:245-271; mode 3 / 0 / 1 / 2): the per-locus operators know nothing beyond their own line, so
+// fisher_exact_test / chisq_test / pearson_corr / ols_iter (main.rs:245-271): the per-locus operators know nothing beyond their own line, so
 // the file is taken in pieces whatever its size -- the worker threads parse piece c + 1 into one of two pinned buffers
 // (16-bit counts when they fit) while the GPU takes piece c and its rows are formatted and appended, in file order
 // (sync.rs:927-946).  Nothing of the size of the input is ever allocated, pinned or copied in one go.
-static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, int mode, size_t chunk_bytes, bool is_pileup,
+static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analysis op, size_t chunk_bytes, bool is_pileup,
                               const PileupFilter &pf, const pg_filter &flt, const RankSetup &rs) {
-    auto hip_ok = [](hipError_t e, const char *what) {
-        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-    };
     const MappedFile mf(a.fname);
-    TextDropper drop_parsed_text; // (after mf: joined before the mapping goes)
     const int R = rs.n_ranks;
     const std::vector<size_t> cuts = mf.cuts(std::max<size_t>((size_t)R, (mf.size() + chunk_bytes - 1) / chunk_bytes));
     const int nchunks = (int)cuts.size() - 1;
@@ -714,7 +665,7 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
     std::vector<int> keep(n);
     std::iota(keep.begin(), keep.end(), 0);
     std::vector<double> Y = ph.phen, ps = ph.pool_sizes;
-    if (mode == 2) {
+    if (op == Analysis::ols_iter) {
         keep = complete_pools(ph);
         if (keep.empty()) throw std::runtime_error("All pools have missing data. Please check the phenotype file.");
         if ((int)keep.size() != n) {
@@ -725,7 +676,7 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
     }
     const int n2 = (int)keep.size();
     const bool subset = n2 != n;
-    const bool tables = mode == 0 || mode == 3; // chisq_test, fisher_exact_test: counts only, one row per locus, no phenotype used
+    const bool tables = counts_only(op); // chisq_test, fisher_exact_test
     const char *header = tables ? "#chr,pos,alleles,statistic,pvalue\n"                    // sync.rs:766
                                    : "#chr,pos,alleles,freq,phenotype,statistic,pvalue\n"; // sync.rs:950
     // One rank = one contiguous range of pieces, one GPU, its own pinned buffers and parser threads, and -- when there are
@@ -743,90 +694,65 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
         Ctx *gp = &gpu0;
         if (!(r == 0 && gpu0.device == device)) { own.reset(new Ctx(device)); gp = own.get(); }
         Ctx &gpu = *gp;
-        struct Slot { void *p = nullptr; size_t cap = 0; } slot[2];
-        auto alloc_for = [&](int i) {
-            SyncAlloc al;
-            al.alloc = [&slot, i](size_t bytes) -> void * {
-                if (bytes > slot[i].cap) {
-                    if (slot[i].p) (void)hipHostFree(slot[i].p);
-                    slot[i].p = nullptr; slot[i].cap = 0;
-                    const size_t want = bytes + bytes / 8;
-                    if (hipHostMalloc(&slot[i].p, want, hipHostMallocDefault) != hipSuccess) return nullptr;
-                    slot[i].cap = want;
-                }
-                return slot[i].p;
-            };
-            al.release = [](void *) {};
-            return al;
-        };
-        auto parse_piece = [&](int c) {
-            (void)hipSetDevice(device);
-            const char *b = mf.data() + cuts[c], *e = mf.data() + cuts[c + 1];
-            SyncBatch parsed = is_pileup ? parse_pileup_buffer(b, e, threads, pf, alloc_for(c & 1))
-                                         : parse_sync_buffer(b, e, threads, 0, alloc_for(c & 1), !subset);
-            drop_parsed_text(b, e);
-            return parsed;
-        };
         const int c0 = first[r], c1 = first[r + 1];
         if (c0 >= c1) return;
-        std::future<SyncBatch> next = std::async(std::launch::async, parse_piece, c0);
+        PieceReader pieces(mf, cuts, c0, c1, device, threads, is_pileup, pf, 0, !subset);
         FILE *fo = nullptr;
-        uint32_t *counts_dev = nullptr;
-        int32_t *n_out_dev = nullptr, *ids_dev = nullptr;
-        double *mf_dev = nullptr, *stat_dev = nullptr, *pv_dev = nullptr;
+        DeviceBuf<uint32_t> counts_dev;
+        DeviceBuf<int32_t> n_out_dev, ids_dev;
+        DeviceBuf<double> mf_dev, stat_dev, pv_dev;
         int64_t cap_loci = 0;
         CountsUpload upload;
         std::vector<uint32_t> counts2;
         std::vector<int32_t> n_out, ids;
         std::vector<double> mfq, stat, pv;
         const size_t per_stat = tables ? 1 : (size_t)PG_MAX_OUT * k;
-        for (int c = c0; c < c1; ++c) {
-            SyncBatch sb = next.get();
-            if (c + 1 < c1) next = std::async(std::launch::async, parse_piece, c + 1);
+        while (pieces.more()) {
+            SyncBatch sb = pieces.next();
             if (sb.L == 0) continue;
             if (sb.n != n) throw std::runtime_error("the number of pools in the sync file and in the phenotype file differ");
             const int64_t L = sb.L;
             totals[r] += L;
             if (L > cap_loci) {
-                for (void *q : {(void *)counts_dev, (void *)n_out_dev, (void *)ids_dev, (void *)mf_dev, (void *)stat_dev, (void *)pv_dev})
-                    if (q) (void)hipFree(q);
                 cap_loci = L + L / 8;
-                hip_ok(hipMalloc((void **)&counts_dev, sizeof(uint32_t) * (size_t)cap_loci * n * 6), "device memory for the counts");
-                hip_ok(hipMalloc((void **)&n_out_dev, sizeof(int32_t) * cap_loci), "device memory");
-                hip_ok(hipMalloc((void **)&ids_dev, sizeof(int32_t) * cap_loci * PG_MAX_OUT), "device memory");
-                hip_ok(hipMalloc((void **)&mf_dev, sizeof(double) * cap_loci * PG_MAX_OUT), "device memory");
-                hip_ok(hipMalloc((void **)&stat_dev, sizeof(double) * cap_loci * per_stat), "device memory");
-                hip_ok(hipMalloc((void **)&pv_dev, sizeof(double) * cap_loci * per_stat), "device memory");
+                counts_dev.reset(sizeof(uint32_t) * (size_t)cap_loci * n * 6, "device memory for the counts");
+                n_out_dev.reset(sizeof(int32_t) * cap_loci);
+                ids_dev.reset(sizeof(int32_t) * cap_loci * PG_MAX_OUT);
+                mf_dev.reset(sizeof(double) * cap_loci * PG_MAX_OUT);
+                stat_dev.reset(sizeof(double) * cap_loci * per_stat);
+                pv_dev.reset(sizeof(double) * cap_loci * per_stat);
             }
             if (subset) { // rare: drop the pools without phenotype on the host (32-bit counts), then one copy
                 counts2.resize((size_t)L * n2 * 6);
                 for (int64_t l = 0; l < L; ++l)
                     for (int i = 0; i < n2; ++i) std::memcpy(&counts2[((size_t)l * n2 + i) * 6], &sb.counts[((size_t)l * n + keep[i]) * 6], 24);
-                hip_ok(hipMemcpy(counts_dev, counts2.data(), sizeof(uint32_t) * counts2.size(), hipMemcpyHostToDevice), "H2D counts");
+                hip_ok(hipMemcpy(counts_dev.get(), counts2.data(), sizeof(uint32_t) * counts2.size(), hipMemcpyHostToDevice), "H2D counts");
             } else
-                upload(gpu, sb, counts_dev);
-            if (mode == 3)
-                gpu.ok(pg_fisher_batch_dev(gpu.c, counts_dev, L, n2, ps.data(), &flt, n_out_dev, ids_dev, stat_dev, pv_dev), "fisher_exact_test");
-            else if (mode == 0)
-                gpu.ok(pg_chisq_batch_dev(gpu.c, counts_dev, L, n2, ps.data(), &flt, n_out_dev, ids_dev, stat_dev, pv_dev), "chisq_test");
-            else if (mode == 1)
-                gpu.ok(pg_pearson_batch_dev(gpu.c, counts_dev, L, n2, ps.data(), &flt, Y.data(), k, n_out_dev, ids_dev, mf_dev, stat_dev, pv_dev),
-                       "pearson_corr");
+                upload(gpu, sb, counts_dev.get());
+            if (op == Analysis::fisher_exact_test)
+                gpu.ok(pg_fisher_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, n_out_dev.get(), ids_dev.get(), stat_dev.get(), pv_dev.get()),
+                       "fisher_exact_test");
+            else if (op == Analysis::chisq_test)
+                gpu.ok(pg_chisq_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, n_out_dev.get(), ids_dev.get(), stat_dev.get(), pv_dev.get()),
+                       "chisq_test");
+            else if (op == Analysis::pearson_corr)
+                gpu.ok(pg_pearson_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, Y.data(), k, n_out_dev.get(), ids_dev.get(), mf_dev.get(),
+                                            stat_dev.get(), pv_dev.get()), "pearson_corr");
             else
-                gpu.ok(pg_ols_iter_batch_dev(gpu.c, counts_dev, L, n2, ps.data(), &flt, Y.data(), k, n_out_dev, ids_dev, mf_dev, stat_dev, pv_dev),
-                       "ols_iter");
+                gpu.ok(pg_ols_iter_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, Y.data(), k, n_out_dev.get(), ids_dev.get(), mf_dev.get(),
+                                             stat_dev.get(), pv_dev.get()), "ols_iter");
             n_out.resize(L); ids.resize((size_t)L * PG_MAX_OUT); mfq.resize((size_t)L * PG_MAX_OUT);
             stat.resize((size_t)L * per_stat); pv.resize((size_t)L * per_stat);
-            hip_ok(hipMemcpy(n_out.data(), n_out_dev, sizeof(int32_t) * L, hipMemcpyDeviceToHost), "D2H results");
+            hip_ok(hipMemcpy(n_out.data(), n_out_dev.get(), sizeof(int32_t) * L, hipMemcpyDeviceToHost), "D2H results");
             // slot-major arrays: the slots any locus of the piece uses are a prefix of every array (one slot on biallelic data)
             int used = 0;
             for (int64_t l = 0; l < L; ++l) used = std::max(used, (int)n_out[l]);
             used = std::min(used, (int)PG_MAX_OUT);
             const size_t per_stat_used = tables ? 1 : (size_t)used * k;
-            hip_ok(hipMemcpy(ids.data(), ids_dev, sizeof(int32_t) * L * used, hipMemcpyDeviceToHost), "D2H results");
-            if (!tables) hip_ok(hipMemcpy(mfq.data(), mf_dev, sizeof(double) * L * used, hipMemcpyDeviceToHost), "D2H results");
-            hip_ok(hipMemcpy(stat.data(), stat_dev, sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
-            hip_ok(hipMemcpy(pv.data(), pv_dev, sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
+            hip_ok(hipMemcpy(ids.data(), ids_dev.get(), sizeof(int32_t) * L * used, hipMemcpyDeviceToHost), "D2H results");
+            if (!tables) hip_ok(hipMemcpy(mfq.data(), mf_dev.get(), sizeof(double) * L * used, hipMemcpyDeviceToHost), "D2H results");
+            hip_ok(hipMemcpy(stat.data(), stat_dev.get(), sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
+            hip_ok(hipMemcpy(pv.data(), pv_dev.get(), sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
             if (!fo) {
                 fo = create_new(part[r]);
                 if (R == 1) fputs(header, fo);
@@ -834,13 +760,10 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
             write_rows_parallel(fo, L, threads, [&](int64_t l, std::string &line) {
                 // slot-major arrays: slot i of locus l sits i * L elements after its slot 0
                 const size_t so = tables ? (size_t)l : (size_t)l * k;
-                format_locus_rows(mode, sb.chrom(l), sb.pos[l], n_out[l], &ids[(size_t)l], &mfq[(size_t)l], &stat[so], &pv[so], k, line, (size_t)L);
+                format_locus_rows(op, sb.chrom(l), sb.pos[l], n_out[l], &ids[(size_t)l], &mfq[(size_t)l], &stat[so], &pv[so], k, line, (size_t)L);
             });
         }
         if (fo) fclose(fo);
-        for (void *q : {(void *)counts_dev, (void *)n_out_dev, (void *)ids_dev, (void *)mf_dev, (void *)stat_dev, (void *)pv_dev})
-            if (q) (void)hipFree(q);
-        for (auto &sl : slot) if (sl.p) (void)hipHostFree(sl.p);
     });
     } catch (...) { cleanup_parts(); throw; }
     int64_t total = 0;
@@ -960,24 +883,12 @@ static int run_popgen(const Args &a, bool is_fst, Ctx &gpu, const double *G_dev,
 struct GenotypesAndPhenotypes {
     std::vector<std::string> chromosome, allele; // 1 + p entries
     std::vector<uint64_t> position;
-    double *intercept_and_allele_frequencies = nullptr; // device
+    DeviceBuf<double> intercept_and_allele_frequencies;
     int64_t p = 0, ld = 0;
     int n = 0, k = 0;
     std::vector<double> phenotypes;                     // n x k
     std::vector<std::string> pool_names;
-    double *coverages = nullptr;                        // device, laid out like the matrix (pg_load_emit_cov_dev); optional
-    GenotypesAndPhenotypes() = default;
-    GenotypesAndPhenotypes(const GenotypesAndPhenotypes &) = delete;
-    GenotypesAndPhenotypes &operator=(const GenotypesAndPhenotypes &) = delete;
-    GenotypesAndPhenotypes(GenotypesAndPhenotypes &&o) noexcept { *this = std::move(o); }
-    GenotypesAndPhenotypes &operator=(GenotypesAndPhenotypes &&o) noexcept {
-        std::swap(chromosome, o.chromosome); std::swap(allele, o.allele); std::swap(position, o.position);
-        std::swap(intercept_and_allele_frequencies, o.intercept_and_allele_frequencies); std::swap(p, o.p); std::swap(ld, o.ld);
-        std::swap(n, o.n); std::swap(k, o.k); std::swap(phenotypes, o.phenotypes); std::swap(pool_names, o.pool_names);
-        std::swap(coverages, o.coverages);
-        return *this;
-    }
-    ~GenotypesAndPhenotypes() { (void)hipFree(intercept_and_allele_frequencies); (void)hipFree(coverages); }
+    DeviceBuf<double> coverages;                        // laid out like the matrix (pg_load_emit_cov_dev); optional
 };
 
 // FileSyncPhen::into_genotypes_and_phenotypes (base/sync.rs:1106-1179) = load (:1044-1104: filter + frequencies per locus,
@@ -987,9 +898,6 @@ struct GenotypesAndPhenotypes {
 // gwas/ols.rs:287); the popgen tools keep every pool.
 static GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt,
                                                             bool keep_p_minus_1, bool remove_missing, bool with_coverages, Lap &lap) {
-    auto hip_ok = [](hipError_t e, const char *what) {
-        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-    };
     const int n = sb.n, k = ph.k;
     const int64_t L = sb.size();
     std::vector<int64_t> order(L);
@@ -1008,39 +916,25 @@ static GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const Sync
     g.ld = g.n + (g.n & 1);
     std::vector<int32_t> pool_map(n, -1);
     for (int i = 0; i < g.n; ++i) pool_map[keep[i]] = i;
-    uint32_t *counts_dev = nullptr;
-    int64_t *order_dev = nullptr;
-    hip_ok(hipMalloc((void **)&counts_dev, sizeof(uint32_t) * (size_t)L * n * 6), "device memory for the counts");
-    hip_ok(hipMalloc((void **)&order_dev, sizeof(int64_t) * L), "device memory");
-    CountsUpload upload;
-    upload(gpu, sb, counts_dev);
-    hip_ok(hipMemcpy(order_dev, order.data(), sizeof(int64_t) * L, hipMemcpyHostToDevice), "H2D order");
-    gpu.ok(pg_load_plan_dev(gpu.c, counts_dev, L, n, ph.pool_sizes.data(), &flt, keep_p_minus_1 ? 1 : 0, order_dev, &g.p), "load");
-    if (g.p <= 0) throw std::runtime_error("no loci passed the filters");
-    int64_t *col_locus_dev = nullptr;
-    int32_t *col_allele_dev = nullptr;
-    hip_ok(hipMalloc((void **)&g.intercept_and_allele_frequencies, sizeof(double) * (size_t)g.p * g.ld), "device memory for the genotype matrix");
-    hip_ok(hipMalloc((void **)&col_locus_dev, sizeof(int64_t) * g.p), "device memory");
-    hip_ok(hipMalloc((void **)&col_allele_dev, sizeof(int32_t) * g.p), "device memory");
-    if (with_coverages) {
-        hip_ok(hipMalloc((void **)&g.coverages, sizeof(double) * (size_t)g.p * g.ld), "device memory for the coverages");
-        gpu.ok(pg_load_emit_cov_dev(gpu.c, pool_map.data(), g.n, g.intercept_and_allele_frequencies, g.ld, col_locus_dev, col_allele_dev,
-                                    g.coverages), "load");
-    } else
-        gpu.ok(pg_load_emit_dev(gpu.c, pool_map.data(), g.n, g.intercept_and_allele_frequencies, g.ld, col_locus_dev, col_allele_dev), "load");
-    lap("sort + H2D + GPU loader");
-    hip_ok(hipFree(counts_dev), "free");
-    hip_ok(hipFree(order_dev), "free");
-    std::vector<int64_t> col_locus(g.p);
-    std::vector<int32_t> col_allele(g.p);
-    hip_ok(hipMemcpy(col_locus.data(), col_locus_dev, sizeof(int64_t) * g.p, hipMemcpyDeviceToHost), "D2H labels");
-    hip_ok(hipMemcpy(col_allele.data(), col_allele_dev, sizeof(int32_t) * g.p, hipMemcpyDeviceToHost), "D2H labels");
-    (void)hipFree(col_locus_dev); (void)hipFree(col_allele_dev);
+    LoadedMatrix m;
+    {
+        DeviceBuf<uint32_t> counts_dev(sizeof(uint32_t) * (size_t)L * n * 6, "device memory for the counts");
+        DeviceBuf<int64_t> order_dev(sizeof(int64_t) * L, "device memory");
+        CountsUpload upload;
+        upload(gpu, sb, counts_dev.get());
+        hip_ok(hipMemcpy(order_dev.get(), order.data(), sizeof(int64_t) * L, hipMemcpyHostToDevice), "H2D order");
+        m = load_matrix(gpu, counts_dev.get(), L, n, ph.pool_sizes, flt, keep_p_minus_1, order_dev.get(), pool_map, g.n, g.ld, with_coverages);
+        if (m.p <= 0) throw std::runtime_error("no loci passed the filters");
+        lap("sort + H2D + GPU loader");
+    }
+    g.p = m.p;
+    g.intercept_and_allele_frequencies = std::move(m.G);
+    g.coverages = std::move(m.coverages);
     g.chromosome.assign(1, "intercept"); g.allele.assign(1, "intercept"); g.position.assign(1, 0);
     g.chromosome.reserve(g.p + 1); g.allele.reserve(g.p + 1); g.position.reserve(g.p + 1);
     for (int64_t c = 0; c < g.p; ++c) {
-        g.chromosome.push_back(sb.chrom(col_locus[c])); g.position.push_back(sb.pos[col_locus[c]]);
-        g.allele.push_back(std::string(1, ALLELES[col_allele[c]]));
+        g.chromosome.push_back(sb.chrom(m.col_locus[c])); g.position.push_back(sb.pos[m.col_locus[c]]);
+        g.allele.push_back(std::string(1, ALLELES[m.col_allele[c]]));
     }
     for (int i : keep) {
         g.pool_names.push_back(ph.pool_names[i]);
@@ -1057,43 +951,35 @@ static GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const Sync
 static std::string ols_with_covariate(Ctx &gpu, GenotypesAndPhenotypes &g, double xxt_eigen_variance_explained,
                                       const std::string &fname_input, const std::string &fname_output, int n_threads, Lap &lap,
                                       bool mle = false) {
-    auto hip_ok = [](hipError_t e, const char *what) {
-        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-    };
     const int64_t p = g.p;
     const int k = g.k;
     if (!fname_output.empty()) { FILE *t = create_new(fname_output); fclose(t); ::unlink(fname_output.c_str()); } // ols.rs:285
     std::vector<double> beta((size_t)p * k), pval((size_t)p * k);
     int m = 0;
-    double *out_dev = nullptr;
-    hip_ok(hipMalloc((void **)&out_dev, sizeof(double) * 3 * (size_t)p * k), "device memory for the results");
-    if (mle)
-        gpu.ok(pg_mle_kinship_dev(gpu.c, g.intercept_and_allele_frequencies, p, g.n, g.ld, g.phenotypes.data(), k, xxt_eigen_variance_explained, -1,
-                                  &m, nullptr, out_dev, out_dev + (size_t)p * k, out_dev + 2 * (size_t)p * k), "mle_iter_with_kinship");
-    else
-    gpu.ok(pg_ols_kinship_dev(gpu.c, g.intercept_and_allele_frequencies, p, g.n, g.ld, g.phenotypes.data(), k, xxt_eigen_variance_explained, -1,
-                              &m, nullptr, out_dev, out_dev + (size_t)p * k, out_dev + 2 * (size_t)p * k), "ols_iter_with_kinship");
-    gpu.ok(pg_synchronize(gpu.c), "ols_iter_with_kinship");
-    hip_ok(hipMemcpy(beta.data(), out_dev, sizeof(double) * (size_t)p * k, hipMemcpyDeviceToHost), "D2H results");
-    hip_ok(hipMemcpy(pval.data(), out_dev + 2 * (size_t)p * k, sizeof(double) * (size_t)p * k, hipMemcpyDeviceToHost), "D2H results");
-    (void)hipFree(out_dev);
+    const size_t cnt = (size_t)p * k;
+    {
+        DeviceBuf<double> out_dev(sizeof(double) * 3 * cnt, "device memory for the results");
+        const double *G = g.intercept_and_allele_frequencies.get();
+        if (mle)
+            gpu.ok(pg_mle_kinship_dev(gpu.c, G, p, g.n, g.ld, g.phenotypes.data(), k, xxt_eigen_variance_explained, -1, &m, nullptr, out_dev.get(),
+                                      out_dev.get() + cnt, out_dev.get() + 2 * cnt), "mle_iter_with_kinship");
+        else
+            gpu.ok(pg_ols_kinship_dev(gpu.c, G, p, g.n, g.ld, g.phenotypes.data(), k, xxt_eigen_variance_explained, -1, &m, nullptr, out_dev.get(),
+                                      out_dev.get() + cnt, out_dev.get() + 2 * cnt), "ols_iter_with_kinship");
+        gpu.ok(pg_synchronize(gpu.c), "ols_iter_with_kinship");
+        hip_ok(hipMemcpy(beta.data(), out_dev.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+        hip_ok(hipMemcpy(pval.data(), out_dev.get() + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+    }
     lap("kinship + fits + D2H");
     std::string out = fname_output;
     if (out.empty()) // ols.rs:393-398
         out = basename_no_ext(fname_input) + (mle ? "-mle_iterative_xxt_" : "-ols_iterative_xxt_") + std::to_string(m + 1) + "_eigens-" +
               unix_time_string() + ".csv"; // ols.rs:393-398, mle.rs:423-427
-    FILE *fo = create_new(out);
-    fputs("#chr,pos,alleles,phenotype,statistic,pvalue\n", fo); // ols.rs:409
-    write_rows_parallel(fo, (int64_t)k * p, n_threads, [&](int64_t r, std::string &text) {
-        const int64_t j = r / p, i = r - j * p; // rows are trait-major (ols.rs:411-433)
+    write_kinship_csv(out, p, k, beta, pval, n_threads, [&](int64_t i, std::string &text) {
         // the reference labels coefficient i with entry i of the (1+p)-long label vectors, i.e.
         // shifted by the intercept entry (ols.rs:421-425) -- reproduced as is
         text += g.chromosome[i]; text.push_back(','); text += std::to_string(g.position[i]); text.push_back(','); text += g.allele[i];
-        text += ",Pheno_"; text += std::to_string(j); text.push_back(',');
-        append_rust_display(text, beta[(size_t)i * k + j]); text.push_back(',');
-        append_rust_display(text, pval[(size_t)i * k + j]); text.push_back('\n');
     });
-    fclose(fo);
     lap("format + write CSV");
     return out;
 }
@@ -1102,33 +988,27 @@ static int run(int argc, char **argv) {
     stamp("main");
     const Args a = parse_args(argc, argv);
     Lap lap;
-    const std::map<std::string, int> known{{"chisq_test", 0}, {"pearson_corr", 1}, {"ols_iter", 2},
-                                           {"ols_iter_with_kinship", 3}, {"pileup2sync", 4},
-                                           {"genomic_prediction_cross_validation", 5}, {"fst", 6}, {"heterozygosity", 7},
-                                           {"mle_iter_with_kinship", 8}, {"fisher_exact_test", 9}};
-    if (!known.count(a.analysis))
+    const std::map<std::string, Analysis> known{
+        {"chisq_test", Analysis::chisq_test}, {"pearson_corr", Analysis::pearson_corr}, {"ols_iter", Analysis::ols_iter},
+        {"fisher_exact_test", Analysis::fisher_exact_test}, {"ols_iter_with_kinship", Analysis::ols_iter_with_kinship},
+        {"mle_iter_with_kinship", Analysis::mle_iter_with_kinship},
+        {"genomic_prediction_cross_validation", Analysis::genomic_prediction_cross_validation}, {"fst", Analysis::fst},
+        {"heterozygosity", Analysis::heterozygosity}, {"pileup2sync", Analysis::pileup2sync}};
+    const auto found = known.find(a.analysis);
+    if (found == known.end())
         throw std::runtime_error("Invalid analysis utility for this build: `" + a.analysis +
                                  "` (available: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship, "
                                  "mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity)");
     if (a.generate_plots || a.sig_only)
         throw std::runtime_error("--generate-plots / --output-sig-snps-only call the reference's python scripts and are out of scope here");
+    const Analysis analysis = found->second;
     Phen ph = parse_phen(a.phen_fname, a.phen_delim, a.phen_name_col, a.phen_pool_size_col, a.phen_value_col);
+    const PileupFilter pf = pileup_filter(a, ph.pool_sizes);
     // the counts are parsed straight into pinned memory: the copy to the device needs no staging pass
     SyncAlloc pinned;
-    pinned.alloc = [](size_t bytes) -> void * {
-        void *p = nullptr;
-        return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
-    };
-    pinned.release = [](void *p) { (void)hipHostFree(p); };
-    if (a.analysis == "pileup2sync") { // main.rs:212-225; text to text, no GPU involved
-        PileupFilter pf;
-        pf.remove_ns = !a.keep_ns;
-        pf.keep_lowercase_reference = a.keep_lowercase_reference;
-        pf.max_base_error_rate = a.max_base_error_rate;
-        pf.min_coverage_depth = a.min_coverage_depth;
-        pf.min_coverage_breadth = a.min_coverage_breadth;
-        pf.min_allele_frequency = a.min_allele_frequency;
-        pf.pool_sizes = ph.pool_sizes;
+    pinned.alloc = PinnedBuf::alloc;
+    pinned.release = PinnedBuf::release;
+    if (analysis == Analysis::pileup2sync) { // main.rs:212-225; text to text, no GPU involved
         std::string out = a.output;
         if (out.empty()) out = basename_no_ext(a.fname) + "-" + unix_time_string() + ".sync"; // pileup.rs:478-494
         const int64_t kept = pileup_to_sync_file(a.fname, ph.pool_names, pf, out, a.n_threads);
@@ -1137,9 +1017,9 @@ static int run(int argc, char **argv) {
         std::cout << out << "\n"; // main.rs:507
         return done_ok();
     }
-    if (a.n_gpus > 0 && known.at(a.analysis) > 3 && known.at(a.analysis) != 9)
+    if (a.n_gpus > 0 && !per_locus(analysis) && analysis != Analysis::ols_iter_with_kinship)
         throw std::runtime_error("--n-gpus applies to fisher_exact_test, chisq_test, pearson_corr, ols_iter and ols_iter_with_kinship; `" + a.analysis + "` runs on one GPU");
-    const RankSetup ranks = rank_setup(a, a.analysis == "ols_iter_with_kinship");
+    const RankSetup ranks = rank_setup(a, analysis == Analysis::ols_iter_with_kinship);
     Ctx gpu(ranks.devices[0]); // first: the pinned allocator below needs a HIP context
     lap("start-up");
     // A pileup input (*.pileup / *.mpileup) is converted in memory -- the counts pileup2sync would write and the
@@ -1149,20 +1029,12 @@ static int run(int argc, char **argv) {
         return x.size() >= m && x.compare(x.size() - m, m, suf) == 0;
     };
     const bool is_pileup = ends_with(a.fname, ".pileup") || ends_with(a.fname, ".mpileup");
-    PileupFilter pf;
-    pf.remove_ns = !a.keep_ns;
-    pf.keep_lowercase_reference = a.keep_lowercase_reference;
-    pf.max_base_error_rate = a.max_base_error_rate;
-    pf.min_coverage_depth = a.min_coverage_depth;
-    pf.min_coverage_breadth = a.min_coverage_breadth;
-    pf.min_allele_frequency = a.min_allele_frequency;
-    pf.pool_sizes = ph.pool_sizes;
     pg_filter flt{};
     flt.remove_ns = a.keep_ns ? 0 : 1;
     flt.min_coverage_depth = a.min_coverage_depth;
     flt.min_allele_frequency = a.min_allele_frequency;
     flt.max_missingness_rate = a.max_missingness_rate;
-    if (a.analysis == "ols_iter_with_kinship") {
+    if (analysis == Analysis::ols_iter_with_kinship) {
         // inputs above 256 MiB are taken in pieces of 128 MiB of text, above 1 GiB in pieces of 256 MiB (parse of piece c + 1 overlaps the GPU work on
         // piece c, and the pinned buffers stay small); an unsorted input falls back to the whole-file path unless
         // the pieces were asked for explicitly
@@ -1183,46 +1055,45 @@ static int run(int argc, char **argv) {
             }
         }
     }
-    if (known.at(a.analysis) <= 2 || known.at(a.analysis) == 9) {
+    if (per_locus(analysis)) {
         size_t piece = (size_t)(a.stream_chunk_mb > 0 ? a.stream_chunk_mb : 128) << 20;
         if (const char *e = std::getenv("PGH_STREAM_CHUNK_BYTES")) piece = (size_t)std::strtoull(e, nullptr, 10); // tests: small pieces
-        return run_batch_streamed(a, ph, gpu, lap, known.at(a.analysis) == 9 ? 3 : known.at(a.analysis), piece, is_pileup, pf, flt, ranks);
+        return run_batch_streamed(a, ph, gpu, lap, analysis, piece, is_pileup, pf, flt, ranks);
     }
     SyncBatch sb;
     if (is_pileup) {
         sb = parse_pileup_file(a.fname, a.n_threads, pf, pinned);
         lap("pileup -> counts");
     } else {
-        // the analyses on the loaded matrix copy the counts themselves: 16-bit counts when they fit (the batch operators'
-        // host-buffer entry points take the 32-bit layout)
-        sb = parse_sync_file(a.fname, a.n_threads, pinned, known.at(a.analysis) >= 3);
+        // the analyses on the loaded matrix copy the counts themselves: 16-bit counts when they fit
+        sb = parse_sync_file(a.fname, a.n_threads, pinned, /*compact16=*/true);
         lap("parse sync");
     }
     if (sb.size() == 0) throw std::runtime_error("no loci in " + a.fname);
     if (sb.n != ph.n) throw std::runtime_error("the number of pools in the sync file and in the phenotype file differ");
     const int k = ph.k;
-    const int mode = known.at(a.analysis);
+    const bool popgen = analysis == Analysis::fst || analysis == Analysis::heterozygosity;
 
     // ---------------- the analyses on the loaded matrix (main.rs:280-298, :397-455) ---------------------------
-    const bool kpm1 = mode == 7 ? false : a.keep_p_minus_1; // heterozygosity: "we need all alleles in each locus" (main.rs:445)
+    const bool kpm1 = analysis == Analysis::heterozygosity ? false : a.keep_p_minus_1; // heterozygosity: "we need all alleles in each locus" (main.rs:445)
     GenotypesAndPhenotypes genotypes_and_phenotypes =
-        into_genotypes_and_phenotypes(gpu, sb, ph, flt, kpm1, /*remove_missing=*/mode < 6 || mode == 8, /*with_coverages=*/mode == 6 || mode == 7, lap);
+        into_genotypes_and_phenotypes(gpu, sb, ph, flt, kpm1, /*remove_missing=*/!popgen, /*with_coverages=*/popgen, lap);
     GenotypesAndPhenotypes &g = genotypes_and_phenotypes;
-    if (mode == 6 || mode == 7) // fst / heterozygosity use every pool (main.rs:427-455)
-        return run_popgen(a, mode == 6, gpu, g.intercept_and_allele_frequencies, g.coverages, g.p, g.n, g.ld, g.chromosome, g.position,
+    if (popgen) // fst / heterozygosity use every pool (main.rs:427-455)
+        return run_popgen(a, analysis == Analysis::fst, gpu, g.intercept_and_allele_frequencies.get(), g.coverages.get(), g.p, g.n, g.ld, g.chromosome, g.position,
                           g.pool_names, lap);
-    if (mode == 5) { // genomic_prediction_cross_validation (main.rs:397-426)
+    if (analysis == Analysis::genomic_prediction_cross_validation) { // genomic_prediction_cross_validation (main.rs:397-426)
         CvLabels labels{g.chromosome, g.allele, g.position};
         CvArgs ca;
         ca.k_folds = a.k_folds; ca.n_reps = a.n_reps; ca.seed = a.seed; ca.n_threads = a.n_threads;
         ca.fname_input = a.fname; ca.fname_output = a.output;
-        const std::string out = gp_cross_validate(gpu.c, g.intercept_and_allele_frequencies, g.p, g.n, g.ld, g.phenotypes, k, g.pool_names,
+        const std::string out = gp_cross_validate(gpu.c, g.intercept_and_allele_frequencies.get(), g.p, g.n, g.ld, g.phenotypes, k, g.pool_names,
                                                   labels, ca);
         lap("cross-validation");
         std::cout << out << "\n";
         return done_ok();
     }
-    const std::string out = ols_with_covariate(gpu, g, a.xxt, a.fname, a.output, a.n_threads, lap, /*mle=*/mode == 8);
+    const std::string out = ols_with_covariate(gpu, g, a.xxt, a.fname, a.output, a.n_threads, lap, /*mle=*/analysis == Analysis::mle_iter_with_kinship);
     std::cout << out << "\n";
     return done_ok();
 }

@@ -5,11 +5,11 @@
 
 namespace pgh {
 
-void format_locus_rows(int mode, const std::string &chromosome, uint64_t position, int n_out, const int32_t *ids, const double *mean_freq,
+void format_locus_rows(Analysis op, const std::string &chromosome, uint64_t position, int n_out, const int32_t *ids, const double *mean_freq,
                        const double *stat, const double *pval, int k, std::string &line, size_t slot_stride) {
     if (n_out <= 0) return;
     const size_t S = slot_stride; // the library's arrays are slot-major: slot i of this locus is S elements (S * k for stat / pval) further on
-    if (mode == 3) { // fisher_exact_test.rs:119-129: both numbers with to_string()
+    if (op == Analysis::fisher_exact_test) { // fisher_exact_test.rs:119-129: both numbers with to_string()
         line += chromosome; line.push_back(','); line += std::to_string(position); line.push_back(',');
         for (int j = 0; j < n_out && j < PG_MAX_OUT; ++j) line.push_back(ALLELES[ids[j * S]]);
         line.push_back(',');
@@ -17,7 +17,7 @@ void format_locus_rows(int mode, const std::string &chromosome, uint64_t positio
         append_rust_display(line, pval[0]); line.push_back('\n');
         return;
     }
-    if (mode == 0) { // chisq_test.rs:37-45
+    if (op == Analysis::chisq_test) { // chisq_test.rs:37-45
         line += chromosome; line.push_back(','); line += std::to_string(position); line.push_back(',');
         for (int j = 0; j < n_out && j < PG_MAX_OUT; ++j) line.push_back(ALLELES[ids[j * S]]);
         line.push_back(',');
@@ -30,17 +30,17 @@ void format_locus_rows(int mode, const std::string &chromosome, uint64_t positio
             const size_t e = (size_t)i * S * k + j;
             line += chromosome; line.push_back(','); line += std::to_string(position); line.push_back(',');
             line.push_back(ALLELES[ids[i * S]]); line.push_back(',');
-            if (mode == 2) append_roundup_own(line, mean_freq[i * S], 8); // ols.rs:263-271
+            if (op == Analysis::ols_iter) append_roundup_own(line, mean_freq[i * S], 8); // ols.rs:263-271
             else append_rust_display(line, mean_freq[i * S]);             // correlation_test.rs:117-124
             line += ",Pheno_"; line += std::to_string(j); line.push_back(',');
             append_roundup_own(line, stat[e], 6); line.push_back(',');
-            if (mode == 2) append_roundup_own(line, pval[e], 12);
+            if (op == Analysis::ols_iter) append_roundup_own(line, pval[e], 12);
             else append_rust_display(line, pval[e]);
             line.push_back('\n');
         }
 }
 
-std::optional<std::string> Operators::run(int mode, const LocusCounts &lc, const double *Y, int k, const FilterStats &f) const {
+std::optional<std::string> Operators::run(Analysis op, const LocusCounts &lc, const double *Y, int k, const FilterStats &f) const {
     const int a = (int)lc.alleles_vector.size();
     if (a == 0 || lc.matrix.size() % (size_t)a != 0) return std::nullopt;
     const int n = (int)(lc.matrix.size() / (size_t)a);
@@ -67,31 +67,31 @@ std::optional<std::string> Operators::run(int mode, const LocusCounts &lc, const
     double mf[PG_MAX_OUT] = {0};
     std::vector<double> stat((size_t)PG_MAX_OUT * (k > 0 ? k : 1)), pv(stat.size());
     int rc;
-    if (mode == 3) rc = pg_fisher_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, &n_out, ids, stat.data(), pv.data());
-    else if (mode == 0) rc = pg_chisq_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, &n_out, ids, stat.data(), pv.data());
-    else if (mode == 1) rc = pg_pearson_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, Y, k, &n_out, ids, mf, stat.data(), pv.data());
+    if (op == Analysis::fisher_exact_test) rc = pg_fisher_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, &n_out, ids, stat.data(), pv.data());
+    else if (op == Analysis::chisq_test) rc = pg_chisq_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, &n_out, ids, stat.data(), pv.data());
+    else if (op == Analysis::pearson_corr) rc = pg_pearson_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, Y, k, &n_out, ids, mf, stat.data(), pv.data());
     else rc = pg_ols_iter_batch(ctx_, counts.data(), 1, n, f.pool_sizes.data(), &flt, Y, k, &n_out, ids, mf, stat.data(), pv.data());
     if (rc != PG_OK) throw std::runtime_error(pg_last_error(ctx_)); // a broken device, not a property of the locus
     if (n_out <= 0) return std::nullopt;
     std::string out;
-    format_locus_rows(mode, lc.chromosome, lc.position, n_out, ids, mf, stat.data(), pv.data(), k, out);
+    format_locus_rows(op, lc.chromosome, lc.position, n_out, ids, mf, stat.data(), pv.data(), k, out);
     return out;
 }
 
-std::optional<std::string> Operators::chisq(LocusCounts &locus, const FilterStats &f) const { return run(0, locus, nullptr, 0, f); }
+std::optional<std::string> Operators::chisq(LocusCounts &locus, const FilterStats &f) const { return run(Analysis::chisq_test, locus, nullptr, 0, f); }
 
-std::optional<std::string> Operators::fisher(LocusCounts &locus, const FilterStats &f) const { return run(3, locus, nullptr, 0, f); }
+std::optional<std::string> Operators::fisher(LocusCounts &locus, const FilterStats &f) const { return run(Analysis::fisher_exact_test, locus, nullptr, 0, f); }
 
 std::optional<std::string> Operators::correlation(LocusCountsAndPhenotypes &l, const FilterStats &f) const {
     const size_t n = l.locus_counts.alleles_vector.empty() ? 0 : l.locus_counts.matrix.size() / l.locus_counts.alleles_vector.size();
     if (n == 0 || l.phenotypes.size() % n != 0) return std::nullopt;
-    return run(1, l.locus_counts, l.phenotypes.data(), (int)(l.phenotypes.size() / n), f);
+    return run(Analysis::pearson_corr, l.locus_counts, l.phenotypes.data(), (int)(l.phenotypes.size() / n), f);
 }
 
 std::optional<std::string> Operators::ols_iterate(LocusCountsAndPhenotypes &l, const FilterStats &f) const {
     const size_t n = l.locus_counts.alleles_vector.empty() ? 0 : l.locus_counts.matrix.size() / l.locus_counts.alleles_vector.size();
     if (n == 0 || l.phenotypes.size() % n != 0) return std::nullopt;
-    return run(2, l.locus_counts, l.phenotypes.data(), (int)(l.phenotypes.size() / n), f);
+    return run(Analysis::ols_iter, l.locus_counts, l.phenotypes.data(), (int)(l.phenotypes.size() / n), f);
 }
 
 } // namespace pgh

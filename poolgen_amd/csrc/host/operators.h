@@ -37,11 +37,19 @@ struct LocusCountsAndPhenotypes { // structs_and_traits.rs:131-136
     std::vector<std::string> pool_names;
 };
 
+// What the CLI can be asked for (main.rs:26-143); the first four are the per-locus operators.
+enum class Analysis {
+    chisq_test, pearson_corr, ols_iter, fisher_exact_test,
+    ols_iter_with_kinship, mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, pileup2sync
+};
+inline bool per_locus(Analysis a) { return a <= Analysis::fisher_exact_test; }
+inline bool counts_only(Analysis a) { return a == Analysis::chisq_test || a == Analysis::fisher_exact_test; } // one row per locus, no phenotype used
+
 // Formats the rows of one locus exactly as the reference's operators do; shared with the CLI's writer.
-// mode 0: chisq (tables/chisq_test.rs:37-45), 1: correlation (gwas/correlation_test.rs:113-127), 2: ols_iterate
-// (gwas/ols.rs:255-275), 3: fisher (tables/fisher_exact_test.rs:119-129).  n_out <= 0 appends nothing.  The pointers are those of the locus' slot 0 in the library's slot-major
-// arrays (include/poolgen_hip.h), slot_stride = the L of the call that filled them (1 for a single locus).
-void format_locus_rows(int mode, const std::string &chromosome, uint64_t position, int n_out, const int32_t *ids, const double *mean_freq,
+// chisq_test: tables/chisq_test.rs:37-45, pearson_corr: gwas/correlation_test.rs:113-127, ols_iter: gwas/ols.rs:255-275,
+// fisher_exact_test: tables/fisher_exact_test.rs:119-129.  n_out <= 0 appends nothing.  The pointers are those of the locus' slot 0 in the
+// library's slot-major arrays (include/poolgen_hip.h), slot_stride = the L of the call that filled them (1 for a single locus).
+void format_locus_rows(Analysis op, const std::string &chromosome, uint64_t position, int n_out, const int32_t *ids, const double *mean_freq,
                        const double *stat, const double *pval, int k, std::string &out, size_t slot_stride = 1);
 
 class Operators {
@@ -52,7 +60,7 @@ public:
     std::optional<std::string> correlation(LocusCountsAndPhenotypes &locus, const FilterStats &f) const;      // gwas::correlation
     std::optional<std::string> ols_iterate(LocusCountsAndPhenotypes &locus, const FilterStats &f) const;      // gwas::ols_iterate
 private:
-    std::optional<std::string> run(int mode, const LocusCounts &lc, const double *Y, int k, const FilterStats &f) const;
+    std::optional<std::string> run(Analysis op, const LocusCounts &lc, const double *Y, int k, const FilterStats &f) const;
     pg_ctx *ctx_;
 };
 

@@ -2560,6 +2560,34 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
     return PG_OK;
 }
 
+// pool weights exactly as the reference forms them: pool_sizes[i] / sum(pool_sizes), the sum left to right (sync.rs:266-268)
+inline std::vector<double> pool_weights(const double *pool_sizes, int n) {
+    std::vector<double> w(n);
+    double total = 0.0;
+    for (int i = 0; i < n; ++i) total = total + pool_sizes[i];
+    for (int i = 0; i < n; ++i) w[i] = pool_sizes[i] / total;
+    return w;
+}
+
+inline int no_complaint(pg_ctx *ctx, const char *who, bool complaint) { // the streaming pass' complaint flag, under the caller's name
+    PG_CHECK(ctx, !complaint, "%s: a count of 2^29 (536 870 912) reads or more: beyond what the streaming pass sums exactly", who);
+    return PG_OK;
+}
+
+// the filter part of LocusParams, everything else zero: the callers set k / k_total / t0 / sort_desc / y_complete / tdf / ... themselves
+inline LocusParams filter_params(int64_t L, int n, const pg_filter *flt) {
+    LocusParams P;
+    std::memset(&P, 0, sizeof P);
+    P.L = L; P.n = n;
+    P.remove_ns = flt->remove_ns ? 1 : 0;
+    P.pshift = 0; // records and flags are indexed by the locus
+    P.min_cov = (double)flt->min_coverage_depth;
+    P.maf = flt->min_allele_frequency;
+    P.max_miss = flt->max_missingness_rate;
+    P.qband = 8.0 * ((double)n + 16.0) * 2.220446049250313e-16;
+    return P;
+}
+
 template <int OP>
 int run_locus_op(pg_ctx *ctx, int kid, const uint32_t *counts_dev, int64_t L, int n,
                  const double *pool_sizes, const pg_filter *flt, const double *Y, int k,
@@ -2575,11 +2603,7 @@ int run_locus_op(pg_ctx *ctx, int kid, const uint32_t *counts_dev, int64_t L, in
         for (int i = 0; i < n * k; ++i)
             PG_CHECK(ctx, !std::isnan(Y[i]), "ols_iter: remove pools with missing phenotypes first "
                                              "(remove_missing, gwas/ols.rs:206)");
-    // pool weights exactly as the reference forms them: pool_sizes[i] / sum(pool_sizes) (sync.rs:266-268)
-    std::vector<double> w(n);
-    double total = 0.0;
-    for (int i = 0; i < n; ++i) total = total + pool_sizes[i];
-    for (int i = 0; i < n; ++i) w[i] = pool_sizes[i] / total;
+    const std::vector<double> w = pool_weights(pool_sizes, n);
     const int df = (OP == OP_OLS) ? n - 1 : n - 2; // ols.rs:139 / correlation_test.rs:65
     std::vector<double> tc = pg_tdist_coef(df < 1 ? 1 : df);
     const int M = stream_period(n);
@@ -2611,17 +2635,10 @@ int run_locus_op(pg_ctx *ctx, int kid, const uint32_t *counts_dev, int64_t L, in
     std::vector<double> Yd(ypad), tab((size_t)n * 3);
     for (int t0 = 0; t0 < k; t0 += kstep) { // the filter passes are recomputed per launch group
         const int kg = (k - t0) < kstep ? (k - t0) : kstep;
-        LocusParams P;
-        std::memset(&P, 0, sizeof P);
-        P.L = L; P.n = n; P.k = kg; P.k_total = k; P.t0 = t0;
-        P.remove_ns = flt->remove_ns ? 1 : 0;
-        P.pshift = 0; // records and flags are indexed by the locus
-        P.min_cov = (double)flt->min_coverage_depth;
-        P.maf = flt->min_allele_frequency;
-        P.max_miss = flt->max_missingness_rate;
+        LocusParams P = filter_params(L, n, flt);
+        P.k = kg; P.k_total = k; P.t0 = t0;
         P.tdf = df;
         P.ntcoef = (int)tc.size();
-        P.qband = 8.0 * ((double)n + 16.0) * 2.220446049250313e-16;
         std::fill(Yd.begin(), Yd.end(), 0.0);
         if (OP == OP_OLS) {
             for (int t = 0; t < kg; ++t) {
@@ -2667,48 +2684,57 @@ int run_locus_op(pg_ctx *ctx, int kid, const uint32_t *counts_dev, int64_t L, in
         int64_t listed = 0;
         bool complaint = false;
         rc = launch_passes<OP>(ctx, kid, counts_dev, W, O, P, kg, rns, &listed, &complaint); // (synchronises after the streaming pass: tab / Yd are free again)
+        if (!rc) rc = no_complaint(ctx, "locus op", complaint);
         if (rc) return rc;
-        PG_CHECK(ctx, !complaint, "locus op: a count of 2^29 (536 870 912) reads or more: beyond what the streaming pass sums exactly");
         if (t0 == 0) { ctx->lo_last_L = L; ctx->lo_last_listed = 0; }
         ctx->lo_last_listed += listed;
     }
     return PG_OK;
 }
 
-// host-buffer wrapper: H2D, run, D2H
+// host-buffer wrapper: one device block [counts | the outputs in list order, from the next 16-byte boundary], H2D of the counts,
+// run(counts_dev) -- the outputs' `dev` pointers are set by then --, D2H of every output with a host pointer, sync, free
+struct HostOut { void *host; size_t bytes; void *dev; };
+
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+template <size_t N, typename Run>
+int run_on_host_buffers(pg_ctx *ctx, const char *who, const uint32_t *counts, size_t cb, HostOut (&outs)[N], Run run) {
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    size_t total = up16(cb);
+    for (const HostOut &o : outs) total += o.bytes;
+    char *d = nullptr;
+    PG_HIP(ctx, hipMalloc((void **)&d, total + 256));
+    size_t off = up16(cb);
+    for (HostOut &o : outs) { o.dev = d + off; off += o.bytes; }
+    int rc = PG_OK;
+    if (hipMemcpyAsync(d, counts, cb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = pg_fail(ctx, PG_ERR_HIP, "%s: H2D failed", who);
+    if (!rc) rc = run(reinterpret_cast<const uint32_t *>(d));
+    if (!rc) {
+        bool okc = true;
+        for (const HostOut &o : outs)
+            if (o.host) okc = okc && hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        if (!okc) rc = pg_fail(ctx, PG_ERR_HIP, "%s: D2H failed", who);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
 template <int OP>
 int run_locus_op_host(pg_ctx *ctx, int kid, const uint32_t *counts, int64_t L, int n,
                       const double *pool_sizes, const pg_filter *flt, const double *Y, int k,
                       int32_t *n_out, int32_t *ids, double *mf, double *stat, double *pv) {
     PG_CHECK(ctx, counts && n_out && ids && stat && pv && L > 0 && n >= 1, "locus op: bad arguments");
-    PG_HIP(ctx, hipSetDevice(ctx->device));
     const int kk = (OP == OP_CHISQ) ? 1 : k;
-    const size_t cb = (size_t)L * n * 6 * sizeof(uint32_t);
     const size_t sb = (OP == OP_CHISQ) ? (size_t)L * sizeof(double) : (size_t)L * PG_MAX_OUT * kk * sizeof(double);
     const size_t ib = (size_t)L * PG_MAX_OUT * sizeof(int32_t), mb = (size_t)L * PG_MAX_OUT * sizeof(double);
-    char *d = nullptr;
-    PG_HIP(ctx, hipMalloc((void **)&d, cb + 2 * sb + ib + mb + (size_t)L * 4 + 256));
-    uint32_t *cd = reinterpret_cast<uint32_t *>(d);
-    double *sd = reinterpret_cast<double *>(d + ((cb + 15) & ~(size_t)15));
-    double *pd = sd + sb / 8;
-    double *md = pd + sb / 8;
-    int32_t *idd = reinterpret_cast<int32_t *>(md + mb / 8);
-    int32_t *nd = idd + ib / 4;
-    int rc = PG_OK;
-    if (hipMemcpyAsync(cd, counts, cb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        rc = pg_fail(ctx, PG_ERR_HIP, "locus op: H2D failed");
-    if (!rc) rc = run_locus_op<OP>(ctx, kid, cd, L, n, pool_sizes, flt, Y, k, nd, idd, md, sd, pd);
-    if (!rc) {
-        bool okc = hipMemcpyAsync(n_out, nd, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        okc = okc && hipMemcpyAsync(ids, idd, ib, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        if (mf) okc = okc && hipMemcpyAsync(mf, md, mb, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        okc = okc && hipMemcpyAsync(stat, sd, sb, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        okc = okc && hipMemcpyAsync(pv, pd, sb, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        if (!okc) rc = pg_fail(ctx, PG_ERR_HIP, "locus op: D2H failed");
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
+    HostOut o[] = {{stat, sb, nullptr}, {pv, sb, nullptr}, {mf, mb, nullptr}, {ids, ib, nullptr}, {n_out, (size_t)L * 4, nullptr}};
+    return run_on_host_buffers(ctx, "locus op", counts, (size_t)L * n * 6 * sizeof(uint32_t), o, [&](const uint32_t *cd) {
+        return run_locus_op<OP>(ctx, kid, cd, L, n, pool_sizes, flt, Y, k, (int32_t *)o[4].dev, (int32_t *)o[3].dev, (double *)o[2].dev,
+                                (double *)o[0].dev, (double *)o[1].dev);
+    });
 }
 
 // ---- loader: filter + frequencies for every locus, one column of G per surviving allele ---------------
@@ -2812,80 +2838,88 @@ __global__ __launch_bounds__(256) void k_load_emit(const uint32_t *__restrict__ 
     }
 }
 
-int load_plan(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const double *pool_sizes,
-              const pg_filter *flt, int keep_p_minus_1, const int64_t *order_dev, int64_t *p_out) {
-    PG_CHECK(ctx, counts_dev && pool_sizes && flt && p_out, "load: null pointer");
-    PG_CHECK(ctx, L > 0 && n >= 1, "load: bad shape L=%lld n=%d", (long long)L, n);
-    PG_CHECK(ctx, (reinterpret_cast<uintptr_t>(counts_dev) & 15) == 0, "load: counts must be 16-byte aligned");
+// The filter as the loader runs it (launch_passes<OP_LOAD>: one header word per locus in W.flags), for load_plan and fisher_dev:
+// the checks under the caller's name, the workspace [w][flags: i32 per locus][second list: L x i64][the same, grouped][its length]
+// [tail_bytes of the caller's own, at offset `tail`], the weights, the passes, the complaint.
+struct FilterPass {
+    StreamWs W;
+    int64_t listed = 0; // loci the second pass took
+    size_t tail = 0;
+};
+
+int filter_pass(pg_ctx *ctx, const char *who, int kid, bool args_ok, const uint32_t *counts_dev, int64_t L, int n, const double *pool_sizes,
+                const pg_filter *flt, int sort_desc, size_t tail_bytes, FilterPass *out) {
+    PG_CHECK(ctx, counts_dev && pool_sizes && flt && args_ok, "%s: null pointer", who);
+    PG_CHECK(ctx, L > 0 && n >= 1, "%s: bad shape L=%lld n=%d", who, (long long)L, n);
+    PG_CHECK(ctx, (reinterpret_cast<uintptr_t>(counts_dev) & 15) == 0, "%s: counts must be 16-byte aligned", who);
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<double> w(n);
-    double total = 0.0;
-    for (int i = 0; i < n; ++i) total = total + pool_sizes[i];
-    for (int i = 0; i < n; ++i) w[i] = pool_sizes[i] / total; // sync.rs:266-268
+    const std::vector<double> w = pool_weights(pool_sizes, n);
     const int M = stream_period(n);
-    PG_CHECK(ctx, (int64_t)64 * M * n * 24 < ((int64_t)1 << 31), "load: too many pools (%d) for one unit of loci", n);
+    PG_CHECK(ctx, (int64_t)64 * M * n * 24 < ((int64_t)1 << 31), "%s: too many pools (%d) for one unit of loci", who, n);
     const size_t slots = (size_t)((L + 63) / 64) * 64;
-    const int64_t nb = (L + 255) / 256;
-    // workspace: [w][flags: i32 per locus][second list: L x i64][its length][local: L x i32][blocksum][blockoff][total][pool map]
-    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     size_t off = 0;
-    const size_t o_w = off; off = al16(off + sizeof(double) * n);
-    const size_t o_flags = off; off = al16(off + sizeof(int32_t) * slots);
-    const size_t o_second = off; off = al16(off + sizeof(int64_t) * (size_t)L);
-    const size_t o_sorted = off; off = al16(off + sizeof(int64_t) * ((size_t)L + 64 * LO_NB));
-    const size_t o_count = off; off = al16(off + 8 * (SC_WORDS + 1));
-    const size_t o_local = off; off = al16(off + sizeof(int32_t) * (size_t)L);
-    const size_t o_bsum = off; off = al16(off + 8 * (size_t)nb);
-    const size_t o_boff = off; off = al16(off + 8 * (size_t)nb);
-    const size_t o_total = off; off = al16(off + 8);
-    const size_t o_pmap = off; off = al16(off + sizeof(int32_t) * (size_t)n);
-    int rc = pg_ws_reserve(ctx, off);
+    const size_t o_w = off; off = up16(off + sizeof(double) * n);
+    const size_t o_flags = off; off = up16(off + sizeof(int32_t) * slots);
+    const size_t o_second = off; off = up16(off + sizeof(int64_t) * (size_t)L);
+    const size_t o_sorted = off; off = up16(off + sizeof(int64_t) * ((size_t)L + 64 * LO_NB));
+    const size_t o_count = off; off = up16(off + 8 * (SC_WORDS + 1));
+    out->tail = off;
+    int rc = pg_ws_reserve(ctx, off + tail_bytes);
     if (rc) return rc;
     char *ws = static_cast<char *>(ctx->ws);
-    StreamWs W;
+    StreamWs &W = out->W;
     W.table = reinterpret_cast<double *>(ws + o_w);
     W.Y = nullptr; W.tcoef = nullptr; W.rec = nullptr;
     W.flags = reinterpret_cast<int32_t *>(ws + o_flags);
     W.second = reinterpret_cast<int64_t *>(ws + o_second);
     W.sorted = reinterpret_cast<int64_t *>(ws + o_sorted);
     W.second_count = reinterpret_cast<unsigned long long *>(ws + o_count);
-    int32_t *recf = W.flags;
-    int32_t *local = reinterpret_cast<int32_t *>(ws + o_local);
-    int64_t *bsum = reinterpret_cast<int64_t *>(ws + o_bsum), *boff = reinterpret_cast<int64_t *>(ws + o_boff);
-    int64_t *tot_dev = reinterpret_cast<int64_t *>(ws + o_total);
     PG_HIP(ctx, hipMemcpyAsync(W.table, w.data(), sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    LocusParams P;
-    std::memset(&P, 0, sizeof P);
-    P.L = L; P.n = n; P.k = 1; P.k_total = 1; P.t0 = 0;
-    P.remove_ns = flt->remove_ns ? 1 : 0;
-    P.pshift = 0; // flags are indexed by the locus
-    P.sort_desc = keep_p_minus_1 ? 1 : 0;
-    P.min_cov = (double)flt->min_coverage_depth;
-    P.maf = flt->min_allele_frequency;
-    P.max_miss = flt->max_missingness_rate;
-    P.qband = 8.0 * ((double)n + 16.0) * 2.220446049250313e-16;
+    LocusParams P = filter_params(L, n, flt);
+    P.k = 1; P.k_total = 1; P.t0 = 0;
+    P.sort_desc = sort_desc;
     P.y_complete = 1;
-    int64_t listed = 0;
     bool complaint = false;
-    rc = launch_passes<OP_LOAD>(ctx, -1, counts_dev, W, StreamOut{nullptr, nullptr, nullptr, nullptr, nullptr}, P, 1, flt->remove_ns != 0,
-                                &listed, &complaint);
+    // the streaming kernel whatever the context ran before (OP_LOAD never takes, and never updates, the kernel choice of
+    // ols_iter / chisq_test)
+    rc = launch_passes<OP_LOAD>(ctx, kid, counts_dev, W, StreamOut{nullptr, nullptr, nullptr, nullptr, nullptr}, P, 1, flt->remove_ns != 0,
+                                &out->listed, &complaint);
+    return rc ? rc : no_complaint(ctx, who, complaint);
+}
+
+int load_plan(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const double *pool_sizes,
+              const pg_filter *flt, int keep_p_minus_1, const int64_t *order_dev, int64_t *p_out) {
+    const int64_t nb = (L + 255) / 256;
+    // the tail of the workspace: [local: L x i32][blocksum][blockoff][total][pool map] (filter_pass checks L and n before it uses the size)
+    size_t off = 0;
+    const size_t t_local = off; off = up16(off + sizeof(int32_t) * (size_t)L);
+    const size_t t_bsum = off; off = up16(off + 8 * (size_t)nb);
+    const size_t t_boff = off; off = up16(off + 8 * (size_t)nb);
+    const size_t t_total = off; off = up16(off + 8);
+    const size_t t_pmap = off; off = up16(off + sizeof(int32_t) * (size_t)n);
+    FilterPass F;
+    const int kpm1 = keep_p_minus_1 ? 1 : 0, pshift = 0; // flags are indexed by the locus
+    int rc = filter_pass(ctx, "load", -1, p_out != nullptr, counts_dev, L, n, pool_sizes, flt, kpm1, off, &F);
     if (rc) return rc;
-    PG_CHECK(ctx, !complaint, "load: a count of 2^29 (536 870 912) reads or more: beyond what the streaming pass sums exactly");
-    hipLaunchKernelGGL(k_load_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, recf, order_dev, L, P.pshift,
-                       P.sort_desc, local, bsum);
+    const StreamWs &W = F.W;
+    char *ws = static_cast<char *>(ctx->ws), *tail = ws + F.tail;
+    int32_t *local = reinterpret_cast<int32_t *>(tail + t_local);
+    int64_t *bsum = reinterpret_cast<int64_t *>(tail + t_bsum), *boff = reinterpret_cast<int64_t *>(tail + t_boff);
+    int64_t *tot_dev = reinterpret_cast<int64_t *>(tail + t_total);
+    hipLaunchKernelGGL(k_load_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, W.flags, order_dev, L, pshift, kpm1, local, bsum);
     hipLaunchKernelGGL(k_load_scan, dim3(1), dim3(1024), 0, ctx->stream, bsum, nb, boff, tot_dev);
     PG_HIP(ctx, hipGetLastError());
     int64_t tot = 0;
     PG_HIP(ctx, hipMemcpyAsync(&tot, tot_dev, 8, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->lo_last_L = L; ctx->lo_last_listed = listed;
+    ctx->lo_last_L = L; ctx->lo_last_listed = F.listed;
     *p_out = tot;
     ctx->load_valid = true;
     ctx->load_counts = counts_dev; ctx->load_order = order_dev;
     ctx->load_L = L; ctx->load_total = tot; ctx->load_nunits = 0;
-    ctx->load_n = n; ctx->load_kpm1 = P.sort_desc; ctx->load_pshift = P.pshift;
-    ctx->load_off_flags = o_flags; ctx->load_off_local = o_local; ctx->load_off_blockoff = o_boff;
-    ctx->load_off_poolmap = o_pmap;
+    ctx->load_n = n; ctx->load_kpm1 = kpm1; ctx->load_pshift = pshift;
+    ctx->load_off_flags = (size_t)(reinterpret_cast<char *>(W.flags) - ws); ctx->load_off_local = F.tail + t_local;
+    ctx->load_off_blockoff = F.tail + t_boff; ctx->load_off_poolmap = F.tail + t_pmap;
     return PG_OK;
 }
 
@@ -3127,55 +3161,10 @@ __global__ __launch_bounds__(LO_THREADS) void k_fisher(const uint32_t *__restric
 
 int fisher_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const double *pool_sizes, const pg_filter *flt,
                int32_t *n_out, int32_t *ids, double *pobs, double *pval) {
-    PG_CHECK(ctx, counts_dev && pool_sizes && flt && n_out && ids && pobs && pval, "fisher: null pointer");
-    PG_CHECK(ctx, L > 0 && n >= 1, "fisher: bad shape L=%lld n=%d", (long long)L, n);
-    PG_CHECK(ctx, (reinterpret_cast<uintptr_t>(counts_dev) & 15) == 0, "fisher: counts must be 16-byte aligned");
-    PG_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<double> w(n);
-    double total = 0.0;
-    for (int i = 0; i < n; ++i) total = total + pool_sizes[i];
-    for (int i = 0; i < n; ++i) w[i] = pool_sizes[i] / total; // sync.rs:266-268
-    const int M = stream_period(n);
-    PG_CHECK(ctx, (int64_t)64 * M * n * 24 < ((int64_t)1 << 31), "fisher: too many pools (%d) for one unit of loci", n);
-    const size_t slots = (size_t)((L + 63) / 64) * 64;
-    // workspace: [w][flags: i32 per locus][second list: L x i64][the same, grouped][its length]
-    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t off = 0;
-    const size_t o_w = off; off = al16(off + sizeof(double) * n);
-    const size_t o_flags = off; off = al16(off + sizeof(int32_t) * slots);
-    const size_t o_second = off; off = al16(off + sizeof(int64_t) * (size_t)L);
-    const size_t o_sorted = off; off = al16(off + sizeof(int64_t) * ((size_t)L + 64 * LO_NB));
-    const size_t o_count = off; off = al16(off + 8 * (SC_WORDS + 1));
-    int rc = pg_ws_reserve(ctx, off);
+    FilterPass F;
+    int rc = filter_pass(ctx, "fisher", PG_K_FISHER, n_out && ids && pobs && pval, counts_dev, L, n, pool_sizes, flt, 0, 0, &F);
     if (rc) return rc;
-    char *ws = static_cast<char *>(ctx->ws);
-    StreamWs W;
-    W.table = reinterpret_cast<double *>(ws + o_w);
-    W.Y = nullptr; W.tcoef = nullptr; W.rec = nullptr;
-    W.flags = reinterpret_cast<int32_t *>(ws + o_flags);
-    W.second = reinterpret_cast<int64_t *>(ws + o_second);
-    W.sorted = reinterpret_cast<int64_t *>(ws + o_sorted);
-    W.second_count = reinterpret_cast<unsigned long long *>(ws + o_count);
-    PG_HIP(ctx, hipMemcpyAsync(W.table, w.data(), sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    LocusParams P;
-    std::memset(&P, 0, sizeof P);
-    P.L = L; P.n = n; P.k = 1; P.k_total = 1; P.t0 = 0;
-    P.remove_ns = flt->remove_ns ? 1 : 0;
-    P.pshift = 0; // flags are indexed by the locus
-    P.sort_desc = 0;
-    P.min_cov = (double)flt->min_coverage_depth;
-    P.maf = flt->min_allele_frequency;
-    P.max_miss = flt->max_missingness_rate;
-    P.qband = 8.0 * ((double)n + 16.0) * 2.220446049250313e-16;
-    P.y_complete = 1;
-    int64_t listed = 0;
-    bool complaint = false;
-    // the filter, exactly as the loader runs it: the streaming kernel whatever the context ran before (OP_LOAD never takes, and
-    // never updates, the kernel choice of ols_iter / chisq_test)
-    rc = launch_passes<OP_LOAD>(ctx, PG_K_FISHER, counts_dev, W, StreamOut{nullptr, nullptr, nullptr, nullptr, nullptr}, P, 1,
-                                flt->remove_ns != 0, &listed, &complaint);
-    if (rc) return rc;
-    PG_CHECK(ctx, !complaint, "fisher: a count of 2^29 (536 870 912) reads or more: beyond what the streaming pass sums exactly");
+    const StreamWs &W = F.W;
     FisherTab tab;
     for (int x = 0; x < 35; ++x) {
         double out = 0.0;
@@ -3194,37 +3183,18 @@ int fisher_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const 
         hipLaunchKernelGGL(k_fisher<64>, grid, block, 0, ctx->stream, counts_dev, (const int32_t *)W.flags, L, n, tab, n_out, ids, pobs, pval);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
-    ctx->lo_last_L = L; ctx->lo_last_listed = listed;
+    ctx->lo_last_L = L; ctx->lo_last_listed = F.listed;
     return PG_OK;
 }
 
 int fisher_host(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const double *pool_sizes, const pg_filter *flt,
                 int32_t *n_out, int32_t *ids, double *pobs, double *pval) {
     PG_CHECK(ctx, counts && n_out && ids && pobs && pval && L > 0 && n >= 1, "fisher: bad arguments");
-    PG_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t cb = ((size_t)L * n * 6 * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t sb = (size_t)L * sizeof(double), ib = (size_t)L * PG_MAX_OUT * sizeof(int32_t);
-    char *d = nullptr;
-    PG_HIP(ctx, hipMalloc((void **)&d, cb + 2 * sb + ib + (size_t)L * 4 + 256));
-    uint32_t *cd = reinterpret_cast<uint32_t *>(d);
-    double *od = reinterpret_cast<double *>(d + cb);
-    double *pd = od + L;
-    int32_t *idd = reinterpret_cast<int32_t *>(pd + L);
-    int32_t *nd = idd + (size_t)L * PG_MAX_OUT;
-    int rc = PG_OK;
-    if (hipMemcpyAsync(cd, counts, (size_t)L * n * 6 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        rc = pg_fail(ctx, PG_ERR_HIP, "fisher: H2D failed");
-    if (!rc) rc = fisher_dev(ctx, cd, L, n, pool_sizes, flt, nd, idd, od, pd);
-    if (!rc) {
-        bool okc = hipMemcpyAsync(n_out, nd, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        okc = okc && hipMemcpyAsync(ids, idd, ib, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        okc = okc && hipMemcpyAsync(pobs, od, sb, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        okc = okc && hipMemcpyAsync(pval, pd, sb, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-        if (!okc) rc = pg_fail(ctx, PG_ERR_HIP, "fisher: D2H failed");
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
+    HostOut o[] = {{pobs, sb, nullptr}, {pval, sb, nullptr}, {ids, ib, nullptr}, {n_out, (size_t)L * 4, nullptr}};
+    return run_on_host_buffers(ctx, "fisher", counts, (size_t)L * n * 6 * sizeof(uint32_t), o, [&](const uint32_t *cd) {
+        return fisher_dev(ctx, cd, L, n, pool_sizes, flt, (int32_t *)o[3].dev, (int32_t *)o[2].dev, (double *)o[0].dev, (double *)o[1].dev);
+    });
 }
 
 } // namespace
