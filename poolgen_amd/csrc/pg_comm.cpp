@@ -138,15 +138,9 @@ extern "C" int pg_ols_kinship_sharded_dev(pg_ctx *ctx, const double *G_dev, int6
         return pg_fail(ctx, PG_ERR_STATE, "ols_kinship_sharded: p_total (%lld) != p_local (%lld) on a context without a communicator "
                        "(pg_comm_init_rank first, or pass the whole matrix)", (long long)p_total, (long long)p_local);
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->S_n < n) {
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->S_dev) PG_HIP(ctx, hipFree(ctx->S_dev));
-        ctx->S_dev = nullptr;
-        ctx->S_n = 0;
-        PG_HIP(ctx, hipMalloc((void **)&ctx->S_dev, sizeof(double) * n * n));
-        ctx->S_n = n;
-    }
-    int rc = pg_set_phenotypes(ctx, force_m > 0 ? 0 : n, force_m > 0 ? nullptr : Y, force_m > 0 ? 0 : k);
+    int rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "ols_kinship_sharded");
+    if (rc) return rc;
+    rc = pg_set_phenotypes(ctx, force_m > 0 ? 0 : n, force_m > 0 ? nullptr : Y, force_m > 0 ? 0 : k);
     if (rc) return rc;
     rc = pg_kinship_partial_dev(ctx, G_dev, p_local, n, ld, ctx->S_dev);
     if (rc) return rc;

@@ -13,6 +13,51 @@
 
 struct pg_event_pair { hipEvent_t a, b; int kid; };
 
+int pg_fail(pg_ctx *ctx, int code, const char *fmt, ...);
+// every allocation and release of the library (pg_context.hip); `pinned` = page-locked host memory
+int pg_mem_alloc(pg_ctx *ctx, void **p, size_t bytes, bool pinned, const char *who);
+void pg_mem_free(void *p, bool pinned);
+// grow on demand: nothing if *cap >= bytes; else the context's stream is drained, the old block goes (pointer and capacity
+// cleared first, so a failed allocation leaves a consistent state) and a block of `bytes` takes its place
+int pg_mem_reserve(pg_ctx *ctx, void **p, size_t *cap, size_t bytes, bool pinned, const char *who);
+
+// Move-only owner of one block of device (or pinned host) memory.  A per-call temporary takes alloc() and is released on
+// every return, so PG_HIP / PG_CHECK may leave early behind it; a buffer the context keeps between calls takes reserve()
+// and goes with the context.
+template <typename T, bool Pinned = false>
+class DevBuf {
+    T *p_ = nullptr;
+    size_t bytes_ = 0;
+
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; bytes_ = o.bytes_; o.p_ = nullptr; o.bytes_ = 0; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    // exactly `bytes`, replacing what was held; 0 bytes succeed and leave it null
+    int alloc(pg_ctx *ctx, size_t bytes, const char *who) {
+        reset();
+        const int rc = pg_mem_alloc(ctx, reinterpret_cast<void **>(&p_), bytes, Pinned, who);
+        if (rc == PG_OK) bytes_ = bytes;
+        return rc;
+    }
+    int reserve(pg_ctx *ctx, size_t bytes, const char *who) {
+        return pg_mem_reserve(ctx, reinterpret_cast<void **>(&p_), &bytes_, bytes, Pinned, who);
+    }
+    void reset() {
+        if (p_) pg_mem_free(p_, Pinned);
+        p_ = nullptr;
+        bytes_ = 0;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; } // the context's buffers are read as the plain pointers they replace
+};
+
 struct pg_ctx {
     int device = -1;
     int cus = 256; // compute units of the device (cached at pg_create)
@@ -26,24 +71,20 @@ struct pg_ctx {
     double prof_ms[PG_K_COUNT] = {0};
     int64_t prof_n[PG_K_COUNT] = {0};
     // generic device workspace (grown on demand, reused between calls)
-    void *ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf<void> ws;
     // regression state set by pg_kinship_set / pg_covariates_set
     int st_n = 0, st_m = -1, st_k = 0, st_cols = 0;
-    double *W_dev = nullptr;     // n x st_cols row-major: [Q_0..Q_m | ytilde_0..ytilde_{k-1}]
-    double *syy_dev = nullptr;   // k
-    double *tcoef_dev = nullptr; // t-distribution series coefficients for df = n - 1
+    DevBuf<double> W_dev;     // n x st_cols row-major: [Q_0..Q_m | ytilde_0..ytilde_{k-1}]
+    DevBuf<double> syy_dev;   // 64 trait slots + 2 (pg_syy_reserve)
+    DevBuf<double> tcoef_dev; // t-distribution series coefficients for df = n - 1 (pg_tcoef_reserve)
     int tcoef_df = 0, tcoef_len = 0;
-    size_t W_cap = 0;
-    double *S_dev = nullptr;     // n x n kinship sum of the single-GPU convenience path
-    int S_n = 0;
+    DevBuf<double> S_dev;     // n x n kinship sum of the single-GPU convenience path
     // speculative intercept-only sums produced by the kinship pass (see pg_set_phenotypes)
     std::vector<double> ph_Y;    // n x k row-major copy of the phenotypes announced up front
     int ph_n = 0, ph_k = 0;
-    double *ph_ytil_dev = nullptr; // k x 256 centred phenotypes, zero padded
+    DevBuf<double> ph_ytil_dev; // k x 256 centred phenotypes, zero padded
     double ph_syy[4] = {0, 0, 0, 0};
-    double *spec_dev = nullptr;  // p x (2 + k): sum g', sum g'^2, sum g' ytil_t   (g' = g - g[0])
-    size_t spec_cap = 0;
+    DevBuf<double> spec_dev;  // p x (2 + k): sum g', sum g'^2, sum g' ytil_t   (g' = g - g[0])
     const double *spec_G = nullptr;
     int64_t spec_p = 0, spec_ld = 0;
     int spec_n = 0, spec_k = 0;
@@ -59,18 +100,16 @@ struct pg_ctx {
     int64_t lo_last_L = 0, lo_last_listed = 0; // pg_locus_op_stats
     bool rows_call[2] = {true, true};   // ... and what the current call's launch groups run
     bool rows_next[2] = {true, true}; // ols_iter, chisq_test: the next batch runs the order-free kernel (the last one looked error-bearing, or none has run)
-    double *lz_dev = nullptr;    // per-wave (1'S1, trace S) partials of the lazy-kinship sweep
+    DevBuf<double> lz_dev;    // per-wave (1'S1, trace S) partials of the lazy-kinship sweep
     bool lazy_taken = false;     // the last pg_ols_kinship_dev decided m = 0 without forming K
     std::vector<double> st_Y;    // phenotypes of the last m = 0 covariate state (lets an identical call skip the upload)
     // small pinned host staging
-    void *pin = nullptr;
-    size_t pin_bytes = 0;
+    DevBuf<void, true> pin;
     // RCCL communicator of the locus-sharded path (pg_comm.cpp); null = single GPU
     void *comm = nullptr;
     int comm_size = 1, comm_rank = 0;
 };
 
-int pg_fail(pg_ctx *ctx, int code, const char *fmt, ...);
 #define PG_HIP(ctx, call)                                                                     \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
@@ -85,6 +124,8 @@ int pg_fail(pg_ctx *ctx, int code, const char *fmt, ...);
 
 int pg_ws_reserve(pg_ctx *ctx, size_t bytes);
 int pg_pin_reserve(pg_ctx *ctx, size_t bytes);
+int pg_tcoef_reserve(pg_ctx *ctx, int df); // the t-distribution coefficients of `df` on the device (tcoef_dev, tcoef_df, tcoef_len)
+inline int pg_syy_reserve(pg_ctx *ctx) { return ctx->syy_dev.reserve(ctx, sizeof(double) * 66, "syy"); }
 constexpr int PG_PROF_CONT = 0x100; // pg_prof_begin(kid | PG_PROF_CONT): more device time of an operation already counted
 void pg_prof_begin(pg_ctx *ctx, int kid);
 void pg_prof_end(pg_ctx *ctx);

@@ -67,17 +67,8 @@ extern "C" void pg_destroy(pg_ctx *ctx) {
     if (ctx->comm) (void)pg_comm_destroy(ctx);
     for (auto &p : ctx->ev_pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto &p : ctx->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->W_dev) (void)hipFree(ctx->W_dev);
-    if (ctx->S_dev) (void)hipFree(ctx->S_dev);
-    if (ctx->lz_dev) (void)hipFree(ctx->lz_dev);
-    if (ctx->ph_ytil_dev) (void)hipFree(ctx->ph_ytil_dev);
-    if (ctx->spec_dev) (void)hipFree(ctx->spec_dev);
-    if (ctx->syy_dev) (void)hipFree(ctx->syy_dev);
-    if (ctx->tcoef_dev) (void)hipFree(ctx->tcoef_dev);
-    if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx; // (every buffer of the context is a DevBuf member: released here)
 }
 
 extern "C" int pg_synchronize(pg_ctx *ctx) {
@@ -86,26 +77,49 @@ extern "C" int pg_synchronize(pg_ctx *ctx) {
     return PG_OK;
 }
 
-int pg_ws_reserve(pg_ctx *ctx, size_t bytes) {
-    ctx->load_valid = false; // whoever asks for the workspace is about to overwrite it
-    if (bytes <= ctx->ws_bytes) return PG_OK;
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->ws) PG_HIP(ctx, hipFree(ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-    PG_HIP(ctx, hipMalloc(&ctx->ws, bytes));
-    ctx->ws_bytes = bytes;
-    return PG_OK;
+int pg_mem_alloc(pg_ctx *ctx, void **p, size_t bytes, bool pinned, const char *who) {
+    *p = nullptr;
+    if (bytes == 0) return PG_OK;
+    const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+    if (e == hipSuccess) return PG_OK;
+    *p = nullptr;
+    return pg_fail(ctx, PG_ERR_HIP, "%s: out of %s memory (%.1f MB: %s)", who, pinned ? "pinned host" : "device", bytes / 1e6,
+                   hipGetErrorString(e));
 }
 
-int pg_pin_reserve(pg_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->pin_bytes) return PG_OK;
+void pg_mem_free(void *p, bool pinned) {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+}
+
+int pg_mem_reserve(pg_ctx *ctx, void **p, size_t *cap, size_t bytes, bool pinned, const char *who) {
+    if (bytes <= *cap) return PG_OK;
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->pin) PG_HIP(ctx, hipHostFree(ctx->pin));
-    ctx->pin = nullptr;
-    ctx->pin_bytes = 0;
-    PG_HIP(ctx, hipHostMalloc(&ctx->pin, bytes, hipHostMallocDefault));
-    ctx->pin_bytes = bytes;
+    if (*p) PG_HIP(ctx, pinned ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    const int rc = pg_mem_alloc(ctx, p, bytes, pinned, who);
+    if (rc == PG_OK) *cap = bytes;
+    return rc;
+}
+
+int pg_ws_reserve(pg_ctx *ctx, size_t bytes) {
+    ctx->load_valid = false; // whoever asks for the workspace is about to overwrite it
+    return ctx->ws.reserve(ctx, bytes, "workspace");
+}
+
+int pg_pin_reserve(pg_ctx *ctx, size_t bytes) { return ctx->pin.reserve(ctx, bytes, "staging"); }
+
+int pg_tcoef_reserve(pg_ctx *ctx, int df) {
+    if (ctx->tcoef_df == df && ctx->tcoef_dev) return PG_OK;
+    const std::vector<double> tc = pg_tdist_coef(df);
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int rc = ctx->tcoef_dev.alloc(ctx, sizeof(double) * (tc.size() + 1), "t coefficients");
+    if (rc) return rc;
+    if (!tc.empty())
+        PG_HIP(ctx, hipMemcpyAsync(ctx->tcoef_dev, tc.data(), sizeof(double) * tc.size(), hipMemcpyHostToDevice, ctx->stream));
+    ctx->tcoef_df = df;
+    ctx->tcoef_len = (int)tc.size();
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // tc is stack-owned
     return PG_OK;
 }
 

@@ -607,14 +607,8 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
     std::vector<double> xxt((size_t)n * n);
     if (xxt_host_or_null) std::memcpy(xxt.data(), xxt_host_or_null, sizeof(double) * (size_t)n * n);
     else {
-        if (ctx->S_n < n) {
-            PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->S_dev) PG_HIP(ctx, hipFree(ctx->S_dev));
-            ctx->S_dev = nullptr; ctx->S_n = 0;
-            PG_HIP(ctx, hipMalloc((void **)&ctx->S_dev, sizeof(double) * n * n));
-            ctx->S_n = n;
-        }
-        int rc = pg_gp_xxt_dev(ctx, G_dev, p, n, ld, ctx->S_dev);
+        int rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "gp_ridge");
+        if (!rc) rc = pg_gp_xxt_dev(ctx, G_dev, p, n, ld, ctx->S_dev);
         if (rc) return rc;
         PG_HIP(ctx, hipMemcpyAsync(xxt.data(), ctx->S_dev, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream));
         PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -624,21 +618,25 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
     const int64_t lpb = (p + nblk - 1) / nblk;
     const int nblk2 = (int)((p + lpb - 1) / lpb);
     RidgeWork W;
-    const size_t part_doubles = std::max<size_t>((size_t)(n_folds * k + 1) * 1024 * 4 * GP_LMAX + (size_t)n_folds * k * 4 * GP_LMAX,
-                                                 (size_t)nblk2 * n * GP_LMAX * 4); // (x 4: the prediction pass' locus groups at n <= 256)
-    char *raw = nullptr;
-    PG_HIP(ctx, hipMalloc((void **)&raw, sizeof(double) * (part_doubles + (size_t)p * GP_LMAX + (size_t)n * GP_LMAX)));
-    W.part = reinterpret_cast<double *>(raw);
-    W.B = W.part + part_doubles;
-    W.yhat = W.B + (size_t)p * GP_LMAX;
-    auto fail = [&](int rc) { (void)hipFree(raw); return rc; };
-
+    // The host ends of the asynchronous copies below come BEFORE the device buffers: releasing those waits for the device, so
+    // on an early return no copy is still in flight when these go.
     // error indices (rep, fold, alpha, lambda, trait) as the reference's `performances` (:509)
     std::vector<double> perf((size_t)n_reps * n_folds * A * L * k, NAN), b0(k), yh((size_t)n * GP_LMAX);
+    std::vector<double> yh_in[2] = {std::vector<double>((size_t)n * GP_LMAX), std::vector<double>((size_t)n * GP_LMAX)};
+    std::vector<int32_t> colof_h[2];
+    std::vector<FoldMasses> fm_h[2];
+    const size_t part_doubles = std::max<size_t>((size_t)(n_folds * k + 1) * 1024 * 4 * GP_LMAX + (size_t)n_folds * k * 4 * GP_LMAX,
+                                                 (size_t)nblk2 * n * GP_LMAX * 4); // (x 4: the prediction pass' locus groups at n <= 256)
+    DevBuf<double> raw;
+    if (int rc = raw.alloc(ctx, sizeof(double) * (part_doubles + (size_t)p * GP_LMAX + (size_t)n * GP_LMAX), "gp_ridge")) return rc;
+    W.part = raw.get();
+    W.B = W.part + part_doubles;
+    W.yhat = W.B + (size_t)p * GP_LMAX;
+
     std::vector<int64_t> itr, iva;
     for (int i = 0; i < n_reps * n_rows; ++i)
         if (fold_of[i] < 0 || fold_of[i] > n_folds /* == n_folds: the left-over group of k_split (:444-448), never validated */) {
-            ctx->err = "gp_ridge: fold id out of range"; return fail(PG_ERR_INVALID);
+            ctx->err = "gp_ridge: fold id out of range"; return PG_ERR_INVALID;
         }
     // error_index (:359-426) of trait j on the validation pools `iva`, for every lambda, from yhat (n x GP_LMAX)
     auto score = [&](int rep, int fold, int a, int j, double b0j, const std::vector<int64_t> &iva_) {
@@ -668,9 +666,9 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
     // at most n - 1 loci) takes the other formula there, so it goes one fold at a time through pg_gp_ols_dev, which follows that rule.
     const int C = n_folds * k;
     const bool fused = C <= PG_MAX_SWEEP_COLS && (int64_t)n < p + 1 && !std::getenv("POOLGEN_RIDGE_PER_FOLD");
-    double *bf = nullptr;       // C x p (column-major) slopes of the folds' fits
-    FoldMasses *fm_dev = nullptr;
-    int32_t *colof_dev = nullptr;
+    DevBuf<double> bf_own;      // C x p (column-major) slopes of the folds' fits
+    DevBuf<FoldMasses> fm_own;
+    DevBuf<int32_t> colof_own;
     // The slopes of ALL repetitions' folds (and of the all-rows fit) are columns G Z of the same matrix: formed CP at a time,
     // whatever repetition they belong to, they take ceil((n_reps C + k) / CP) passes over G instead of n_reps + 1 (config 4:
     // 101 columns, 7 passes instead of 11).  Needs the n_reps C + k columns resident (config 4: 4 GB of the 288); otherwise,
@@ -684,16 +682,16 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
     }
     const auto t_alloc0 = std::chrono::steady_clock::now();
     if (fused) {
-        if (hipMalloc((void **)&bf, sizeof(double) * (size_t)p * (batched ? ncols_all : (size_t)C)) != hipSuccess ||
-            hipMalloc((void **)&fm_dev, sizeof(FoldMasses) * C) != hipSuccess ||
-            hipMalloc((void **)&colof_dev, sizeof(int32_t) * n) != hipSuccess) {
-            (void)hipFree(bf); (void)hipFree(fm_dev); (void)hipFree(colof_dev);
-            return fail(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: out of device memory"));
-        }
+        int rc = bf_own.alloc(ctx, sizeof(double) * (size_t)p * (batched ? ncols_all : (size_t)C), "gp_ridge");
+        if (!rc) rc = fm_own.alloc(ctx, sizeof(FoldMasses) * C, "gp_ridge");
+        if (!rc) rc = colof_own.alloc(ctx, sizeof(int32_t) * n, "gp_ridge");
+        if (rc) return rc;
     }
+    double *const bf = bf_own.get();
+    FoldMasses *const fm_dev = fm_own.get();
+    int32_t *const colof_dev = colof_own.get();
     const double t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
     const double t_before = std::chrono::duration<double>(t_alloc0 - t_entry).count(); // X X^T, its copy to the host, the work buffers
-    auto fail2 = [&](int rc) { (void)hipFree(bf); (void)hipFree(fm_dev); (void)hipFree(colof_dev); return fail(rc); };
     // POOLGEN_GP_TIMING=1: host-side phase times of the repetitions on stderr
     const bool timing = std::getenv("POOLGEN_GP_TIMING") != nullptr;
     double t_solve = 0, t_beta = 0, t_params = 0, t_predict = 0;
@@ -762,9 +760,6 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
     // scores of the pass before): its predictions land in yh_in[buf], the small host arrays its copies read stay alive in turn.
     struct Pending { bool on; int rep, a, j, buf; };
     Pending pend{false, 0, 0, 0, 0};
-    std::vector<double> yh_in[2] = {std::vector<double>((size_t)n * GP_LMAX), std::vector<double>((size_t)n * GP_LMAX)};
-    std::vector<int32_t> colof_h[2];
-    std::vector<FoldMasses> fm_h[2];
     int fm_turn = 0;
     auto score_pending = [&](const Pending &q) {
         const RepSolve &R = solves[q.rep];
@@ -796,7 +791,7 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
         double t0 = now();
         readyf[rep].wait();
         RepSolve &R = solves[rep];
-        if (R.bad) return fail2(pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: pinv failed"));
+        if (R.bad) return pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: pinv failed");
         const std::vector<std::vector<int64_t>> &tr = R.tr, &va = R.va;
         const std::vector<double> &Z = R.Z;
         t_solve += now() - t0; t0 = now();
@@ -815,7 +810,7 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
             rc = pg_gp_beta_cols(ctx, G_dev, p, n, ld, Z.data(), C, bf, 1); // :526 for every fold at once, column-major
             t_beta += now() - t0;
         }
-        if (rc) return fail2(rc);
+        if (rc) return rc;
         const double *bfr = batched ? bf + (size_t)rep * C * (size_t)p : bf; // this repetition's C columns
         for (int a = 0; a < A; ++a) {
             t0 = now();
@@ -830,7 +825,7 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
                 for (int j = 0; j < k; ++j) skip[f * k + j] = va[f].empty() || tr[f].empty();
             std::vector<PathParams> PP;
             rc = ridge_path_params_cols(ctx, bfr, p, C, k, alpha_at(a), path, W, proxy_dev, skip, PP);
-            if (rc) return fail2(rc);
+            if (rc) return rc;
             for (int c = 0; c < C; ++c) {
                 if (skip[c]) { std::memset(&fm[c], 0, sizeof(FoldMasses)); fm[c].nmax = 1.0; continue; }
                 fm[c].nmax = PP[c].nmax;
@@ -839,7 +834,7 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
             P0 = PP[0]; // alpha, lambda[], L are the same for every column
             P0.nmax = 0.0;
             if (hipMemcpyAsync(fm_dev, fm.data(), sizeof(FoldMasses) * C, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                return fail2(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed"));
+                return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed");
             t_params += now() - t0; t0 = now();
             for (int j = 0; j < k; ++j) {
                 // (the masses' synchronisation has seen the pass that was out: its predictions are on the host)
@@ -851,9 +846,9 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
                     if (!va[f].empty() && !tr[f].empty())
                         for (int64_t pool : va[f]) colof[pool] = f * k + j;
                 if (prev.on && hipStreamSynchronize(ctx->stream) != hipSuccess) // (a no-op after the masses' own; the k > 1 traits of one alpha need it)
-                    return fail2(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed"));
+                    return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
                 if (hipMemcpyAsync(colof_dev, colof.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                    return fail2(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed"));
+                    return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed");
                 const int LP = (P0.L + 1) & ~1;
                 const size_t masses_b = sizeof(double) * n_folds * (2 * GP_LMAX + 1);
                 const int chunk = std::max(4, std::min(64, (int)((49152 - masses_b) / (sizeof(double) * n_folds * (LP + 2)))));
@@ -884,7 +879,7 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
                 hipLaunchKernelGGL(k_gp_predict_reduce, dim3((n * GP_LMAX + 63) / 64), dim3(512), 0, ctx->stream, W.part, nblk2 * groups, n, W.yhat);
                 if (hipGetLastError() != hipSuccess ||
                     hipMemcpyAsync(yh_in[turn].data(), W.yhat, sizeof(double) * n * GP_LMAX, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-                    return fail2(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed"));
+                    return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
                 pend = Pending{true, rep, a, j, turn};
                 // ... and while this pass runs, the host scores the one before it
                 if (prev.on) score_pending(prev);
@@ -893,7 +888,7 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
         }
     }
     if (pend.on) { // the last pass out
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail2(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed"));
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
         score_pending(pend);
         pend.on = false;
     }
@@ -904,17 +899,17 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
             rc = form_cols(formed, c1);
             formed = c1;
         }
-        if (rc) return fail2(rc);
+        if (rc) return rc;
         if (hipMemcpyAsync(beta_dev, b0all.data(), sizeof(double) * k, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return fail2(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed"));
+            return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed");
         hipLaunchKernelGGL(k_gp_cols_to_rows, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, bf + (size_t)n_reps * C * (size_t)p, p, k, beta_dev + k);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) // (b0all is read by the copy)
-            return fail2(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: the all-rows fit failed"));
+            return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: the all-rows fit failed");
     }
     const double t_free0 = now();
-    (void)hipFree(bf); (void)hipFree(fm_dev); (void)hipFree(colof_dev);
+    bf_own.reset(); fm_own.reset(); colof_own.reset(); // (here, not at scope end: the report below times them)
     if (timing)
-        std::fprintf(stderr, "gp path: before the repetitions %.1f ms; fold solves %.1f ms, coefficient passes %.1f ms, masses %.1f ms, prediction + scores %.1f ms; the columns' memory: hipMalloc %.1f ms, hipFree %.1f ms; since entry %.1f ms\n",
+        std::fprintf(stderr, "gp path: before the repetitions %.1f ms; fold solves %.1f ms, coefficient passes %.1f ms, masses %.1f ms, prediction + scores %.1f ms; the columns' memory: allocation %.1f ms, release %.1f ms; since entry %.1f ms\n",
                      1e3 * t_before, 1e3 * t_solve, 1e3 * t_beta, 1e3 * t_params, 1e3 * t_predict, 1e3 * t_alloc, 1e3 * (now() - t_free0),
                      1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count());
     for (int rep = 0; rep < n_reps && !fused; ++rep)
@@ -926,28 +921,28 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
             }
             if (iva.empty() || itr.empty()) continue; // an empty fold leaves NaN, as an empty slice would
             int rc = pg_gp_ols_dev(ctx, G_dev, p, n, ld, Y, k, itr.data(), (int)itr.size(), xxt.data(), beta_dev); // :526
-            if (rc) return fail(rc);
+            if (rc) return rc;
             if (hipMemcpyAsync(b0.data(), beta_dev, sizeof(double) * k, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-                return fail(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: D2H failed"));
+                return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: D2H failed");
             for (int a = 0; a < A; ++a)
                 for (int j = 0; j < k; ++j) {
                     PathParams P;
                     const Proxy X{proxy_dev, k, j};
                     rc = ridge_path_params(ctx, beta_dev, p, k, j, alpha_at(a), path, W, P, 1, X);
-                    if (rc) return fail(rc);
+                    if (rc) return rc;
                     hipLaunchKernelGGL(k_gp_blambda, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, beta_dev, p, k, j, P, X, W.B);
                     hipLaunchKernelGGL(k_gp_predict, dim3(nblk2, (n + 255) / 256), dim3(256), 0, ctx->stream, G_dev, W.B, p, n, ld, lpb, W.part);
                     hipLaunchKernelGGL(k_gp_predict_reduce, dim3((n * GP_LMAX + 63) / 64), dim3(512), 0, ctx->stream, W.part, nblk2, n, W.yhat);
                     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(yh.data(), W.yhat, sizeof(double) * n * GP_LMAX, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                         hipStreamSynchronize(ctx->stream) != hipSuccess)
-                        return fail(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed"));
+                        return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
                     score(rep, fold, a, j, b0[j], iva);
                 }
         }
     // all-rows fit; per trait the mode over repetitions of the per-repetition arg-min over the (alpha, lambda) grid
     // (:573-627): alpha and lambda are counted separately, each against the path values
     int rc = batched ? PG_OK : pg_gp_ols_dev(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, xxt.data(), beta_dev); // (batched: already in beta_dev)
-    if (rc) return fail(rc);
+    if (rc) return rc;
     for (int j = 0; j < k; ++j) {
         std::vector<int> acount(L, 0), lcount(L, 0);
         for (int rep = 0; rep < n_reps; ++rep) {
@@ -979,13 +974,13 @@ int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t l
         PathParams P;
         const Proxy X{proxy_dev, k, j};
         rc = ridge_path_params(ctx, beta_dev, p, k, j, afinal, path, W, P, 1, X);
-        if (rc) return fail(rc);
+        if (rc) return rc;
         hipLaunchKernelGGL(k_gp_apply, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, beta_dev, p, k, j, P, X, lbest);
-        if (hipGetLastError() != hipSuccess) return fail(pg_fail(ctx, PG_ERR_HIP, "gp_ridge: apply failed"));
+        if (hipGetLastError() != hipSuccess) return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: apply failed");
     }
     if (perf_out) std::memcpy(perf_out, perf.data(), sizeof(double) * perf.size());
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(raw);
+    raw.reset(); // (inside the whole-call time)
     if (std::getenv("POOLGEN_GP_TIMING"))
         std::fprintf(stderr, "gp path: whole call %.1f ms\n", 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count());
     return PG_OK;
@@ -1015,17 +1010,15 @@ extern "C" int pg_gp_penalised_dev(pg_ctx *ctx, const double *G_dev, int64_t p, 
     PG_CHECK(ctx, p > 0 && n >= 3 && k >= 1 && k <= 8 && n_rows >= 3 && n_rows <= n && n_reps >= 1 && n_folds >= 2,
              "gp_penalised: bad shape");
     PG_CHECK(ctx, alpha <= 1.0 && lambda_step > 0.0 && lambda_step <= 1.0, "gp_penalised: bad alpha / lambda step");
-    double *proxy = nullptr;
+    DevBuf<double> proxy;
     if (iterative_proxy) { // the same proxy serves every fold and the final fit (:543, :656: always on `row_idx`)
         PG_HIP(ctx, hipSetDevice(ctx->device));
-        PG_HIP(ctx, hipMalloc((void **)&proxy, sizeof(double) * (size_t)(p + 1) * k));
-        const int rc = pg_gp_proxy_dev(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, XXt_host_or_null, proxy);
-        if (rc) { (void)hipFree(proxy); return rc; }
+        int rc = proxy.alloc(ctx, sizeof(double) * (size_t)(p + 1) * k, "gp_penalised");
+        if (!rc) rc = pg_gp_proxy_dev(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, XXt_host_or_null, proxy.get());
+        if (rc) return rc;
     }
-    const int rc = penalised_path(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, fold_of, n_reps, n_folds, alpha, proxy, lambda_step,
-                                  beta_dev, alphas_out, lambdas_out, perf_out, XXt_host_or_null);
-    if (proxy) (void)hipFree(proxy);
-    return rc;
+    return penalised_path(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, fold_of, n_reps, n_folds, alpha, proxy.get(), lambda_step,
+                          beta_dev, alphas_out, lambdas_out, perf_out, XXt_host_or_null);
 }
 
 namespace {
@@ -1044,7 +1037,7 @@ extern "C" int pg_gp_predict_dev(pg_ctx *ctx, const double *G_dev, int64_t p, in
     const size_t need = sizeof(double) * ((size_t)nblk2 * n * 8 + (size_t)n * 8);
     int rc = pg_ws_reserve(ctx, need);
     if (rc) return rc;
-    double *part = static_cast<double *>(ctx->ws);
+    double *part = static_cast<double *>(ctx->ws.get());
     double *out = part + (size_t)nblk2 * n * 8;
     hipLaunchKernelGGL(k_gp_predict_beta, dim3(nblk2, (n + 255) / 256), dim3(256), 0, ctx->stream, G_dev, beta_dev, k, p, n, ld, lpb, part);
     hipLaunchKernelGGL(k_gp_predict_beta_reduce, dim3((n * 8 + 255) / 256), dim3(256), 0, ctx->stream, part, nblk2, n, out);

@@ -789,7 +789,7 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     const size_t slab_bytes = (size_t)nslab * P.npad * P.npad * sizeof(double);
     int rc = pg_ws_reserve(ctx, slab_bytes);
     if (rc) return rc;
-    P.slabs = static_cast<double *>(ctx->ws);
+    P.slabs = static_cast<double *>(ctx->ws.get());
 
     // worst-case LDS row: two blocks of Tb tiles (+16 pad)
     int ldsld = (P.nb == 1) ? P.Tb * 16 : 2 * P.Tb * 16;
@@ -802,13 +802,8 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     ctx->spec_valid = false;
     if (fuse) {
         const size_t need = (size_t)p * (2 + ctx->ph_k) * sizeof(double);
-        if (need > ctx->spec_cap) {
-            PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->spec_dev) PG_HIP(ctx, hipFree(ctx->spec_dev));
-            ctx->spec_dev = nullptr; ctx->spec_cap = 0;
-            PG_HIP(ctx, hipMalloc((void **)&ctx->spec_dev, need));
-            ctx->spec_cap = need;
-        }
+        const int rrc = ctx->spec_dev.reserve(ctx, need, "kinship");
+        if (rrc) return rrc;
         P.ytil = ctx->ph_ytil_dev; P.spec = ctx->spec_dev; P.k = ctx->ph_k;
     }
     const size_t shmem = (size_t)2 * KIN_KC * ldsld * sizeof(double) + (fuse ? ((size_t)KIN_FUSE_MAXK * 256 + (size_t)KIN_WAVES * 4 * 64) * sizeof(double) : 0);
@@ -903,7 +898,8 @@ extern "C" int pg_set_phenotypes(pg_ctx *ctx, int n, const double *Y, int k) {
         }
         ctx->ph_syy[t] = syy;
     }
-    if (!ctx->ph_ytil_dev) PG_HIP(ctx, hipMalloc((void **)&ctx->ph_ytil_dev, sizeof(double) * 4 * 256));
+    const int rc = ctx->ph_ytil_dev.reserve(ctx, sizeof(double) * 4 * 256, "set_phenotypes");
+    if (rc) return rc;
     PG_HIP(ctx, hipMemcpyAsync(ctx->ph_ytil_dev, yt.data(), sizeof(double) * k * 256, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->ph_Y.assign(Y, Y + (size_t)n * k);

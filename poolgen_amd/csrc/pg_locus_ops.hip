@@ -2618,7 +2618,7 @@ int run_locus_op(pg_ctx *ctx, int kid, const uint32_t *counts_dev, int64_t L, in
     int rc = pg_ws_reserve(ctx, need);
     if (rc) return rc;
     StreamWs W;
-    W.table = static_cast<double *>(ctx->ws);
+    W.table = static_cast<double *>(ctx->ws.get());
     W.Y = W.table + (size_t)n * 3;
     W.tcoef = W.Y + ypad;
     W.rec = W.table + side;
@@ -2703,11 +2703,12 @@ int run_on_host_buffers(pg_ctx *ctx, const char *who, const uint32_t *counts, si
     PG_HIP(ctx, hipSetDevice(ctx->device));
     size_t total = up16(cb);
     for (const HostOut &o : outs) total += o.bytes;
-    char *d = nullptr;
-    PG_HIP(ctx, hipMalloc((void **)&d, total + 256));
+    DevBuf<char> block;
+    int rc = block.alloc(ctx, total + 256, who);
+    if (rc) return rc;
+    char *const d = block.get();
     size_t off = up16(cb);
     for (HostOut &o : outs) { o.dev = d + off; off += o.bytes; }
-    int rc = PG_OK;
     if (hipMemcpyAsync(d, counts, cb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         rc = pg_fail(ctx, PG_ERR_HIP, "%s: H2D failed", who);
     if (!rc) rc = run(reinterpret_cast<const uint32_t *>(d));
@@ -2717,8 +2718,7 @@ int run_on_host_buffers(pg_ctx *ctx, const char *who, const uint32_t *counts, si
             if (o.host) okc = okc && hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
         if (!okc) rc = pg_fail(ctx, PG_ERR_HIP, "%s: D2H failed", who);
     }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
+    (void)hipStreamSynchronize(ctx->stream); // on every path: the copies above read and write the caller's host buffers
     return rc;
 }
 
@@ -2866,7 +2866,7 @@ int filter_pass(pg_ctx *ctx, const char *who, int kid, bool args_ok, const uint3
     out->tail = off;
     int rc = pg_ws_reserve(ctx, off + tail_bytes);
     if (rc) return rc;
-    char *ws = static_cast<char *>(ctx->ws);
+    char *ws = static_cast<char *>(ctx->ws.get());
     StreamWs &W = out->W;
     W.table = reinterpret_cast<double *>(ws + o_w);
     W.Y = nullptr; W.tcoef = nullptr; W.rec = nullptr;
@@ -2902,7 +2902,7 @@ int load_plan(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const d
     int rc = filter_pass(ctx, "load", -1, p_out != nullptr, counts_dev, L, n, pool_sizes, flt, kpm1, off, &F);
     if (rc) return rc;
     const StreamWs &W = F.W;
-    char *ws = static_cast<char *>(ctx->ws), *tail = ws + F.tail;
+    char *ws = static_cast<char *>(ctx->ws.get()), *tail = ws + F.tail;
     int32_t *local = reinterpret_cast<int32_t *>(tail + t_local);
     int64_t *bsum = reinterpret_cast<int64_t *>(tail + t_bsum), *boff = reinterpret_cast<int64_t *>(tail + t_boff);
     int64_t *tot_dev = reinterpret_cast<int64_t *>(tail + t_total);
@@ -2935,7 +2935,7 @@ int load_emit(pg_ctx *ctx, const int32_t *pool_map, int n_out, double *G_dev, in
         for (int i = 0; i < n; ++i) PG_CHECK(ctx, pool_map[i] >= -1 && pool_map[i] < n_out, "load_emit: pool_map[%d] out of range", i);
     if (ctx->load_total == 0) return PG_OK;
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    char *ws = static_cast<char *>(ctx->ws);
+    char *ws = static_cast<char *>(ctx->ws.get());
     int32_t *pmap_dev = nullptr;
     if (pool_map) {
         pmap_dev = reinterpret_cast<int32_t *>(ws + ctx->load_off_poolmap);

@@ -395,17 +395,18 @@ extern "C" int pg_mle_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
         PG_CHECK(ctx, !std::isnan(Y[i]), "mle_kinship: phenotype matrix contains NaN (the reference propagates it into every fit, mle.rs:345-360)");
     PG_HIP(ctx, hipSetDevice(ctx->device));
     // ---- kinship, eigen rule (mle.rs:317-343 = gwas/ols.rs:291-315): the very code of ols_iter_with_kinship ----------------
-    double *S = nullptr;
-    PG_HIP(ctx, hipMalloc((void **)&S, sizeof(double) * n * n));
     std::vector<double> Kh((size_t)n * n), ev(n);
     int m = 0;
-    int rc = pg_set_phenotypes(ctx, 0, nullptr, 0);
-    if (!rc) rc = pg_kinship_partial_dev(ctx, G_dev, p, n, ld, S);
-    if (!rc && (hipMemcpyAsync(Kh.data(), S, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess))
-        rc = pg_fail(ctx, PG_ERR_HIP, "mle_kinship: D2H failed");
-    (void)hipFree(S);
-    if (rc) return rc;
+    {
+        DevBuf<double> S; // (gone before the sums below are allocated)
+        int rc = S.alloc(ctx, sizeof(double) * n * n, "mle_kinship");
+        if (!rc) rc = pg_set_phenotypes(ctx, 0, nullptr, 0);
+        if (!rc) rc = pg_kinship_partial_dev(ctx, G_dev, p, n, ld, S.get());
+        if (rc) return rc;
+        if (hipMemcpyAsync(Kh.data(), S.get(), sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            return pg_fail(ctx, PG_ERR_HIP, "mle_kinship: D2H failed");
+    }
     for (auto &x : Kh) x = x / (double)p;
     std::vector<double> V;
     if (force_m >= 0) m = force_m;
@@ -457,56 +458,41 @@ extern "C" int pg_mle_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
     }
     H.n = n; H.m1 = m1; H.k = k;
     HB.n = n; HB.m1 = m1; HB.k = k;
-    double *sums = nullptr, *gg = nullptr;
-    if (hipMalloc((void **)&sums, sizeof(double) * (size_t)p * ncol) != hipSuccess || hipMalloc((void **)&gg, sizeof(double) * (size_t)p) != hipSuccess) {
-        (void)hipFree(sums);
-        return pg_fail(ctx, PG_ERR_HIP, "mle_kinship: out of device memory");
-    }
-    rc = pg_gp_beta_cols(ctx, G_dev, p, n, ld, Z.data(), ncol, sums, 0, gg);
+    DevBuf<double> sums, gg;
+    int rc = sums.alloc(ctx, sizeof(double) * (size_t)p * ncol, "mle_kinship");
+    if (!rc) rc = gg.alloc(ctx, sizeof(double) * (size_t)p, "mle_kinship");
+    if (!rc) rc = pg_gp_beta_cols(ctx, G_dev, p, n, ld, Z.data(), ncol, sums.get(), 0, gg.get());
     // ---- the fits -------------------------------------------------------------------------------------------------------------
-    if (!rc) {
-        const int df = n - 1;
-        if (ctx->tcoef_df != df || !ctx->tcoef_dev) {
-            std::vector<double> tc = pg_tdist_coef(df);
-            if (ctx->tcoef_dev) (void)hipFree(ctx->tcoef_dev);
-            ctx->tcoef_dev = nullptr;
-            if (hipMalloc((void **)&ctx->tcoef_dev, sizeof(double) * (tc.size() + 1)) != hipSuccess ||
-                (!tc.empty() && hipMemcpy(ctx->tcoef_dev, tc.data(), sizeof(double) * tc.size(), hipMemcpyHostToDevice) != hipSuccess))
-                rc = pg_fail(ctx, PG_ERR_HIP, "mle_kinship: t-coefficient upload failed");
-            ctx->tcoef_df = df;
-            ctx->tcoef_len = (int)tc.size();
-        }
-        H.tdf = ctx->tcoef_df; H.ntcoef = ctx->tcoef_len;
-        HB.tdf = ctx->tcoef_df; HB.ntcoef = ctx->tcoef_len;
+    if (!rc) rc = pg_tcoef_reserve(ctx, n - 1);
+    if (rc) return rc;
+    H.tdf = ctx->tcoef_df; H.ntcoef = ctx->tcoef_len;
+    HB.tdf = ctx->tcoef_df; HB.ntcoef = ctx->tcoef_len;
+    const int64_t cells = p * k;
+    const unsigned grid = (unsigned)((cells + 63) / 64);
+    DevBuf<MleSharedBig> HBd;
+    if (big) {
+        rc = HBd.alloc(ctx, sizeof HB, "mle_kinship");
+        if (rc) return rc;
+        if (hipMemcpyAsync(HBd.get(), &HB, sizeof HB, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            return pg_fail(ctx, PG_ERR_HIP, "mle_kinship: upload of the shared statistics failed");
     }
-    if (!rc) {
-        const int64_t cells = p * k;
-        const unsigned grid = (unsigned)((cells + 63) / 64);
-        MleSharedBig *HBd = nullptr;
-        if (big) {
-            if (hipMalloc((void **)&HBd, sizeof HB) != hipSuccess || hipMemcpyAsync(HBd, &HB, sizeof HB, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                rc = pg_fail(ctx, PG_ERR_HIP, "mle_kinship: upload of the shared statistics failed");
-        }
 #define PG_MLE_LDS(PV)                                                                                                              \
     case PV: {                                                                                                                     \
         const size_t lds = sizeof(double) * 64 * ((size_t)(PV + 2) * (PV + 1) + (PV + 2));                                        \
         if (hipFuncSetAttribute((const void *)k_mle_nm_lds<PV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
             rc = pg_fail(ctx, PG_ERR_HIP, "mle_kinship: LDS attribute");                                                           \
-        else hipLaunchKernelGGL(k_mle_nm_lds<PV>, dim3(grid), dim3(64), lds, ctx->stream, sums, gg, ctx->tcoef_dev, p, HBd, beta_dev, var_dev, pval_dev); \
+        else hipLaunchKernelGGL(k_mle_nm_lds<PV>, dim3(grid), dim3(64), lds, ctx->stream, sums.get(), gg.get(), ctx->tcoef_dev.get(), p, HBd.get(), beta_dev, var_dev, pval_dev); \
     } break;
-        if (!rc && big) switch (m + 2) {
-        PG_MLE_LDS(2) PG_MLE_LDS(3) PG_MLE_LDS(4) PG_MLE_LDS(5) PG_MLE_LDS(6) PG_MLE_LDS(7) PG_MLE_LDS(8) PG_MLE_LDS(9) PG_MLE_LDS(10)
-        }
-        else if (!rc) switch (m + 2) {
-        case 2: hipLaunchKernelGGL(k_mle_nm<2>, dim3(grid), dim3(64), 0, ctx->stream, sums, gg, ctx->tcoef_dev, p, H, beta_dev, var_dev, pval_dev); break;
-        case 3: hipLaunchKernelGGL(k_mle_nm<3>, dim3(grid), dim3(64), 0, ctx->stream, sums, gg, ctx->tcoef_dev, p, H, beta_dev, var_dev, pval_dev); break;
-        default: hipLaunchKernelGGL(k_mle_nm<4>, dim3(grid), dim3(64), 0, ctx->stream, sums, gg, ctx->tcoef_dev, p, H, beta_dev, var_dev, pval_dev); break;
-        }
-#undef PG_MLE_LDS
-        if (!rc && (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = pg_fail(ctx, PG_ERR_HIP, "mle_kinship: simplex kernel failed");
-        if (HBd) (void)hipFree(HBd);
+    if (big) switch (m + 2) {
+    PG_MLE_LDS(2) PG_MLE_LDS(3) PG_MLE_LDS(4) PG_MLE_LDS(5) PG_MLE_LDS(6) PG_MLE_LDS(7) PG_MLE_LDS(8) PG_MLE_LDS(9) PG_MLE_LDS(10)
     }
-    (void)hipFree(sums);
-    (void)hipFree(gg);
-    return rc;
+    else switch (m + 2) {
+    case 2: hipLaunchKernelGGL(k_mle_nm<2>, dim3(grid), dim3(64), 0, ctx->stream, sums.get(), gg.get(), ctx->tcoef_dev.get(), p, H, beta_dev, var_dev, pval_dev); break;
+    case 3: hipLaunchKernelGGL(k_mle_nm<3>, dim3(grid), dim3(64), 0, ctx->stream, sums.get(), gg.get(), ctx->tcoef_dev.get(), p, H, beta_dev, var_dev, pval_dev); break;
+    default: hipLaunchKernelGGL(k_mle_nm<4>, dim3(grid), dim3(64), 0, ctx->stream, sums.get(), gg.get(), ctx->tcoef_dev.get(), p, H, beta_dev, var_dev, pval_dev); break;
+    }
+#undef PG_MLE_LDS
+    if (rc) return rc;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return pg_fail(ctx, PG_ERR_HIP, "mle_kinship: simplex kernel failed");
+    return PG_OK;
 }

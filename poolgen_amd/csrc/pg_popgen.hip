@@ -180,12 +180,6 @@ __global__ __launch_bounds__(256) void k_chunk_reduce(const double *__restrict__
     out[i] = s / denom;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T *as() { return static_cast<T *>(p); }
-};
-
 int check_shape(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                 const int64_t *locus_col, int64_t L, const int64_t *wh, const int64_t *wt, int64_t nw, const char *who) {
     PG_CHECK(ctx, G_dev && cov_dev && locus_col && p > 0 && n >= 1 && ld >= n && L >= 1, "%s: bad arguments", who);
@@ -235,22 +229,23 @@ extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev
     if (rc) return rc;
     PG_CHECK(ctx, n_windows >= 1 && pi_win && pi_mean, "pi: There were no windows defined."); // pi.rs:81
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf lc, q1, pi, wh, wt, out;
-    PG_HIP(ctx, hipMalloc(&lc.p, sizeof(int64_t) * (L + 1)));
-    PG_HIP(ctx, hipMalloc(&q1.p, sizeof(double) * (size_t)L * n));
-    PG_HIP(ctx, hipMalloc(&pi.p, sizeof(double) * (size_t)L * n));
-    PG_HIP(ctx, hipMalloc(&wh.p, sizeof(int64_t) * n_windows));
-    PG_HIP(ctx, hipMalloc(&wt.p, sizeof(int64_t) * n_windows));
-    PG_HIP(ctx, hipMalloc(&out.p, sizeof(double) * (size_t)n_windows * n));
-    PG_HIP(ctx, hipMemcpyAsync(lc.p, locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(wh.p, win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(wt.p, win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
+    DevBuf<int64_t> lc, wh, wt;
+    DevBuf<double> q1, pi, out;
+    if ((rc = lc.alloc(ctx, sizeof(int64_t) * (L + 1), "pi"))) return rc;
+    if ((rc = q1.alloc(ctx, sizeof(double) * (size_t)L * n, "pi"))) return rc;
+    if ((rc = pi.alloc(ctx, sizeof(double) * (size_t)L * n, "pi"))) return rc;
+    if ((rc = wh.alloc(ctx, sizeof(int64_t) * n_windows, "pi"))) return rc;
+    if ((rc = wt.alloc(ctx, sizeof(int64_t) * n_windows, "pi"))) return rc;
+    if ((rc = out.alloc(ctx, sizeof(double) * (size_t)n_windows * n, "pi"))) return rc;
+    PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(wh.get(), win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(wt.get(), win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_pop_locus, dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, cov_dev,
-                       lc.as<int64_t>(), L, n, ld, q1.as<double>(), pi.as<double>());
+                       lc.get(), L, n, ld, q1.get(), pi.get());
     hipLaunchKernelGGL(k_range_mean_1d, dim3((unsigned)(((size_t)n_windows * n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       pi.as<double>(), wh.as<int64_t>(), wt.as<int64_t>(), n_windows, n, out.as<double>());
+                       pi.get(), wh.get(), wt.get(), n_windows, n, out.get());
     PG_HIP(ctx, hipGetLastError());
-    PG_HIP(ctx, hipMemcpyAsync(pi_win, out.p, sizeof(double) * (size_t)n_windows * n, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(pi_win, out.get(), sizeof(double) * (size_t)n_windows * n, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int j = 0; j < n; ++j) { // mean_axis(Axis(0)) over the windows (pi.rs:133): left to right
         double s = 0.0;
@@ -274,50 +269,52 @@ extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_de
     const int64_t nchunks = (L + chunk - 1) / chunk;
     std::vector<int64_t> ch(nchunks), ct(nchunks);
     for (int64_t c = 0; c < nchunks; ++c) { ch[c] = c * chunk; ct[c] = std::min<int64_t>(L, (c + 1) * chunk) - 1; }
-    DevBuf lc, q1, pi, wh, wt, chh, cht, part, mean, out, bad;
-    PG_HIP(ctx, hipMalloc(&lc.p, sizeof(int64_t) * (L + 1)));
-    PG_HIP(ctx, hipMalloc(&q1.p, sizeof(double) * (size_t)L * n));
-    PG_HIP(ctx, hipMalloc(&pi.p, sizeof(double) * (size_t)L * n));
-    PG_HIP(ctx, hipMalloc(&chh.p, sizeof(int64_t) * nchunks));
-    PG_HIP(ctx, hipMalloc(&cht.p, sizeof(int64_t) * nchunks));
-    PG_HIP(ctx, hipMalloc(&part.p, sizeof(double) * nchunks * nn));
-    PG_HIP(ctx, hipMalloc(&mean.p, sizeof(double) * nn));
-    PG_HIP(ctx, hipMalloc(&bad.p, sizeof(int)));
-    PG_HIP(ctx, hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(lc.p, locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(chh.p, ch.data(), sizeof(int64_t) * nchunks, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(cht.p, ct.data(), sizeof(int64_t) * nchunks, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_pop_check, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, lc.as<int64_t>(), L, n,
-                       ld, bad.as<int>());
+    DevBuf<int64_t> lc, wh, wt, chh, cht;
+    DevBuf<double> q1, pi, part, mean, out;
+    DevBuf<int> bad;
+    if ((rc = lc.alloc(ctx, sizeof(int64_t) * (L + 1), "fst"))) return rc;
+    if ((rc = q1.alloc(ctx, sizeof(double) * (size_t)L * n, "fst"))) return rc;
+    if ((rc = pi.alloc(ctx, sizeof(double) * (size_t)L * n, "fst"))) return rc;
+    if ((rc = chh.alloc(ctx, sizeof(int64_t) * nchunks, "fst"))) return rc;
+    if ((rc = cht.alloc(ctx, sizeof(int64_t) * nchunks, "fst"))) return rc;
+    if ((rc = part.alloc(ctx, sizeof(double) * nchunks * nn, "fst"))) return rc;
+    if ((rc = mean.alloc(ctx, sizeof(double) * nn, "fst"))) return rc;
+    if ((rc = bad.alloc(ctx, sizeof(int), "fst"))) return rc;
+    PG_HIP(ctx, hipMemsetAsync(bad.get(), 0, sizeof(int), ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(chh.get(), ch.data(), sizeof(int64_t) * nchunks, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(cht.get(), ct.data(), sizeof(int64_t) * nchunks, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_pop_check, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, lc.get(), L, n,
+                       ld, bad.get());
     hipLaunchKernelGGL(k_pop_locus, dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, cov_dev,
-                       lc.as<int64_t>(), L, n, ld, q1.as<double>(), pi.as<double>());
+                       lc.get(), L, n, ld, q1.get(), pi.get());
     int hbad = 0;
-    PG_HIP(ctx, hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (hbad) // the reference's assert!((g.sum_axis(Axis(1)).sum() - n as f64).abs() <= f64::EPSILON) (fst.rs:66)
         return pg_fail(ctx, PG_ERR_INVALID, "fst: the allele frequencies of a locus do not sum up to one in every pool");
     const int ntile = (n + FTILE - 1) / FTILE;
     const int ntri = ntile * (ntile + 1) / 2;
-    hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nchunks, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.as<double>(),
-                       lc.as<int64_t>(), chh.as<int64_t>(), cht.as<int64_t>(), n, ld, ntile, 0, part.as<double>());
-    hipLaunchKernelGGL(k_chunk_reduce, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, ctx->stream, part.as<double>(), nchunks,
-                       (int64_t)nn, (double)L, mean.as<double>());
+    hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nchunks, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.get(),
+                       lc.get(), chh.get(), cht.get(), n, ld, ntile, 0, part.get());
+    hipLaunchKernelGGL(k_chunk_reduce, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, ctx->stream, part.get(), nchunks,
+                       (int64_t)nn, (double)L, mean.get());
     PG_HIP(ctx, hipGetLastError());
-    PG_HIP(ctx, hipMemcpyAsync(fst_mean, mean.p, sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(fst_mean, mean.get(), sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
     if (n_windows > 0) {
-        PG_HIP(ctx, hipMalloc(&wh.p, sizeof(int64_t) * n_windows));
-        PG_HIP(ctx, hipMalloc(&wt.p, sizeof(int64_t) * n_windows));
-        PG_HIP(ctx, hipMemcpyAsync(wh.p, win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
-        PG_HIP(ctx, hipMemcpyAsync(wt.p, win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = wh.alloc(ctx, sizeof(int64_t) * n_windows, "fst"))) return rc;
+        if ((rc = wt.alloc(ctx, sizeof(int64_t) * n_windows, "fst"))) return rc;
+        PG_HIP(ctx, hipMemcpyAsync(wh.get(), win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
+        PG_HIP(ctx, hipMemcpyAsync(wt.get(), win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
         // the per-window table in slabs of windows (it is n^2 doubles per window)
         const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(n_windows, (int64_t)(((size_t)1 << 30) / (nn * sizeof(double)))));
-        PG_HIP(ctx, hipMalloc(&out.p, sizeof(double) * slab * nn));
+        if ((rc = out.alloc(ctx, sizeof(double) * slab * nn, "fst"))) return rc;
         for (int64_t w0 = 0; w0 < n_windows; w0 += slab) {
             const int64_t nwb = std::min<int64_t>(slab, n_windows - w0);
-            hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nwb, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.as<double>(),
-                               lc.as<int64_t>(), wh.as<int64_t>() + w0, wt.as<int64_t>() + w0, n, ld, ntile, 1, out.as<double>());
+            hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nwb, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.get(),
+                               lc.get(), wh.get() + w0, wt.get() + w0, n, ld, ntile, 1, out.get());
             PG_HIP(ctx, hipGetLastError());
-            PG_HIP(ctx, hipMemcpyAsync(fst_win + (size_t)w0 * nn, out.p, sizeof(double) * nwb * nn, hipMemcpyDeviceToHost, ctx->stream));
+            PG_HIP(ctx, hipMemcpyAsync(fst_win + (size_t)w0 * nn, out.get(), sizeof(double) * nwb * nn, hipMemcpyDeviceToHost, ctx->stream));
             PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
     }

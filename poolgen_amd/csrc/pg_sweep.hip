@@ -1052,6 +1052,32 @@ int round_cols(int c) {
     return -1;
 }
 
+// f(std::integral_constant<int, C>{}) for the C of `Cs` that equals cols: the widths a kernel is compiled for.  The callers list
+// them downwards: the compiler emits the instantiations in the reverse of the listed order, and upwards is how the kernels
+// have always been laid out in the code object.
+template <int... Cs, typename F>
+int with_cols_in(pg_ctx *ctx, int cols, F f) {
+    int rc = PG_OK;
+    const bool hit = ((cols == Cs && ((rc = f(std::integral_constant<int, Cs>{})), true)) || ...);
+    return hit ? rc : pg_fail(ctx, PG_ERR_STATE, "sweep: unexpected column count %d", cols);
+}
+template <typename F>
+int with_cols(pg_ctx *ctx, int cols, F f) { // (the sizes of round_cols)
+    return with_cols_in<PG_MAX_SWEEP_COLS, 24, 16, 12, 8, 6, 4, 3, 2>(ctx, cols, f);
+}
+
+// What every launch of the sweep family starts from: all zero (no ss, no lz, row-major, no geometry), then the shape, the
+// singularity threshold, and the context's W / syy / t coefficients.  A caller sets only what differs.
+SweepArgs sweep_args(const pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld) {
+    SweepArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.G = G; A.W = ctx->W_dev; A.syy = ctx->syy_dev; A.tcoef = ctx->tcoef_dev;
+    A.D.p = p; A.D.n = n; A.D.ld = ld;
+    A.D.tdf = ctx->tcoef_df; A.D.ntcoef = ctx->tcoef_len;
+    A.D.tau = 1e-12;
+    return A;
+}
+
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1113,32 +1139,15 @@ extern "C" int pg_covariates_set(pg_ctx *ctx, int n, const double *Cmat, int m, 
         syy[j] = s;
     }
     const size_t wbytes = W.size() * sizeof(double);
-    if (wbytes > ctx->W_cap) {
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->W_dev) PG_HIP(ctx, hipFree(ctx->W_dev));
-        ctx->W_dev = nullptr;
-        ctx->W_cap = 0;
-        PG_HIP(ctx, hipMalloc((void **)&ctx->W_dev, wbytes));
-        ctx->W_cap = wbytes;
-    }
-    if (!ctx->syy_dev) PG_HIP(ctx, hipMalloc((void **)&ctx->syy_dev, sizeof(double) * 66));
+    int rc = ctx->W_dev.reserve(ctx, wbytes, "covariates");
+    if (!rc) rc = pg_syy_reserve(ctx);
+    if (rc) return rc;
     PG_CHECK(ctx, k <= 64, "covariates: at most 64 traits per call");
     PG_HIP(ctx, hipMemcpyAsync(ctx->W_dev, W.data(), wbytes, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(ctx, hipMemcpyAsync(ctx->syy_dev, syy.data(), sizeof(double) * k, hipMemcpyHostToDevice,
                                ctx->stream));
-    const int df = n - 1; // StudentsT::new(0, 1, n - 1), gwas/ols.rs:139
-    if (ctx->tcoef_df != df || !ctx->tcoef_dev) {
-        std::vector<double> tc = pg_tdist_coef(df);
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->tcoef_dev) PG_HIP(ctx, hipFree(ctx->tcoef_dev));
-        ctx->tcoef_dev = nullptr;
-        PG_HIP(ctx, hipMalloc((void **)&ctx->tcoef_dev, sizeof(double) * (tc.size() + 1)));
-        if (!tc.empty())
-            PG_HIP(ctx, hipMemcpyAsync(ctx->tcoef_dev, tc.data(), sizeof(double) * tc.size(),
-                                       hipMemcpyHostToDevice, ctx->stream));
-        ctx->tcoef_df = df;
-        ctx->tcoef_len = (int)tc.size();
-    }
+    rc = pg_tcoef_reserve(ctx, n - 1); // StudentsT::new(0, 1, n - 1), gwas/ols.rs:139
+    if (rc) return rc;
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // W/syy are stack-owned vectors
     ctx->st_n = n;
     ctx->st_m = m;
@@ -1183,11 +1192,12 @@ extern "C" int pg_kinship_set(pg_ctx *ctx, const double *S_dev, int64_t p_total,
         if (force_m < 0 && !evals_out && !K_out) {
             // the common outcome (m = 0 by the Rayleigh quotient of the ones vector, see below) is decided from two numbers
             // formed on the device; only when that test does not settle it does the matrix come over
-            if (!ctx->syy_dev) PG_HIP(ctx, hipMalloc((void **)&ctx->syy_dev, sizeof(double) * 66));
+            prc = pg_syy_reserve(ctx);
+            if (prc) return prc;
             double *two = ctx->syy_dev + 64; // behind the 64 trait slots
             hipLaunchKernelGGL(k_sum_trace, dim3(1), dim3(1024), 0, ctx->stream, S_dev, n, two);
             PG_HIP(ctx, hipGetLastError());
-            double *hp = static_cast<double *>(ctx->pin) + (size_t)n * n;
+            double *hp = static_cast<double *>(ctx->pin.get()) + (size_t)n * n;
             PG_HIP(ctx, hipMemcpyAsync(hp, two, sizeof(double) * 2, hipMemcpyDeviceToHost, ctx->stream));
             PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
             const double tot = hp[0], tr = hp[1];
@@ -1304,8 +1314,7 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
     PG_CHECK(ctx, (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0, "sweep: G must be 16-byte aligned");
     PG_HIP(ctx, hipSetDevice(ctx->device));
     const int cus = ctx->cus;
-    SweepArgs P;
-    P.G = G_dev; P.W = ctx->W_dev; P.syy = ctx->syy_dev; P.tcoef = ctx->tcoef_dev;
+    SweepArgs P = sweep_args(ctx, G_dev, p, n, ld);
     P.beta = beta_dev; P.var = var_dev; P.pval = pval_dev;
     // super-rows: g consecutive loci whose g * ld doubles start and end on a 128-byte line (see k_ols_sweep)
     {
@@ -1319,14 +1328,9 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
         if (const char *e = std::getenv("POOLGEN_SWEEP_MODE")) P.Q.prefetch = std::atoi(e); // 3: compute only, 5: memory only (wrong results)
     }
     const int64_t nsr = (p + P.Q.g - 1) / P.Q.g;
-    P.D.p = p; P.D.ld = ld; P.D.ntiles = (nsr + 63) / 64;
-    P.D.n = n; P.D.m1 = ctx->st_m + 1; P.D.k = ctx->st_k;
-    P.D.tdf = ctx->tcoef_df; P.D.ntcoef = ctx->tcoef_len;
+    P.D.ntiles = (nsr + 63) / 64;
+    P.D.m1 = ctx->st_m + 1; P.D.k = ctx->st_k;
     P.D.dfe = (double)n - (double)(ctx->st_m + 2);
-    P.D.tau = 1e-12;
-    P.D.colmajor = 0;
-    P.D.ss = nullptr;
-    P.D.lz = nullptr;
     if (ctx->st_m == 0 && ctx->spec_valid && ctx->spec_G == G_dev && ctx->spec_p == p && ctx->spec_n == n &&
         ctx->spec_ld == ld && ctx->spec_k == ctx->st_k && ctx->ph_n == n && ctx->st_Y_matches_ph) {
         // m = 0: the kinship pass already formed the sums of the intercept-only fits from its read of G
@@ -1351,18 +1355,7 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
     if (const char *e = std::getenv("POOLGEN_SWEEP_GRID_MULT")) mult = std::max(1, std::atoi(e)); // experiments
     const int64_t cap = (int64_t)cus * mult;
     const int grid = (int)(blocks < cap ? blocks : cap);
-    switch (ctx->st_cols) {
-    case 2: return launch_sweep<2>(ctx, P, grid);
-    case 3: return launch_sweep<3>(ctx, P, grid);
-    case 4: return launch_sweep<4>(ctx, P, grid);
-    case 6: return launch_sweep<6>(ctx, P, grid);
-    case 8: return launch_sweep<8>(ctx, P, grid);
-    case 12: return launch_sweep<12>(ctx, P, grid);
-    case 16: return launch_sweep<16>(ctx, P, grid);
-    case 24: return launch_sweep<24>(ctx, P, grid);
-    case PG_MAX_SWEEP_COLS: return launch_sweep<PG_MAX_SWEEP_COLS>(ctx, P, grid);
-    }
-    return pg_fail(ctx, PG_ERR_STATE, "sweep: unexpected column count %d", ctx->st_cols);
+    return with_cols(ctx, ctx->st_cols, [&](auto c) { return launch_sweep<decltype(c)::value>(ctx, P, grid); });
 }
 
 extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld,
@@ -1382,19 +1375,13 @@ extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
         rc = pg_covariates_set(ctx, n, nullptr, 0, Y, k);
         if (rc) return rc;
         const size_t lzbytes = sizeof(double) * 2 * (size_t)ctx->cus * (ms_threads(1) / 64) * MS_LZ_PER_CU; // the MODE-2 grid is clamped to it
-        if (!ctx->lz_dev) PG_HIP(ctx, hipMalloc((void **)&ctx->lz_dev, lzbytes));
+        rc = ctx->lz_dev.reserve(ctx, lzbytes, "ols_kinship");
+        if (rc) return rc;
         PG_HIP(ctx, hipMemsetAsync(ctx->lz_dev, 0, lzbytes, ctx->stream));
-        SweepArgs P;
-        P.G = G_dev; P.W = ctx->W_dev; P.syy = ctx->syy_dev; P.tcoef = ctx->tcoef_dev;
+        SweepArgs P = sweep_args(ctx, G_dev, p, n, ld);
         P.beta = beta_dev; P.var = var_dev; P.pval = pval_dev;
-        std::memset(&P.Q, 0, sizeof P.Q);
-        P.D.p = p; P.D.ld = ld; P.D.ntiles = 0;
-        P.D.n = n; P.D.m1 = 1; P.D.k = k;
-        P.D.tdf = ctx->tcoef_df; P.D.ntcoef = ctx->tcoef_len;
+        P.D.m1 = 1; P.D.k = k;
         P.D.dfe = (double)n - 2.0;
-        P.D.tau = 1e-12;
-        P.D.colmajor = 0;
-        P.D.ss = nullptr;
         P.D.lz = ctx->lz_dev;
         rc = launch_sweep_mfma<2>(ctx, P, ctx->st_cols, 1 + k, PG_K_SWEEP);
         if (rc == PG_OK) {
@@ -1402,7 +1389,7 @@ extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
             if (rc) return rc;
             PG_HIP(ctx, hipMemcpyAsync(ctx->pin, ctx->lz_dev, lzbytes, hipMemcpyDeviceToHost, ctx->stream));
             PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const double *hp = static_cast<const double *>(ctx->pin);
+            const double *hp = static_cast<const double *>(ctx->pin.get());
             double tot = 0.0, tr = 0.0;
             for (size_t w = 0; w < lzbytes / 16; ++w) { tot += hp[2 * w]; tr += hp[2 * w + 1]; }
             if (tr > 0.0 && std::isfinite(tot) && (tot / n) / tr >= var_explained + 1e-9) {
@@ -1417,14 +1404,8 @@ extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
         // what the reference says)
     }
     ctx->lazy_taken = false;
-    if (ctx->S_n < n) {
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->S_dev) PG_HIP(ctx, hipFree(ctx->S_dev));
-        ctx->S_dev = nullptr;
-        ctx->S_n = 0;
-        PG_HIP(ctx, hipMalloc((void **)&ctx->S_dev, sizeof(double) * n * n));
-        ctx->S_n = n;
-    }
+    rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "ols_kinship");
+    if (rc) return rc;
     double *S_dev = ctx->S_dev;
     rc = pg_set_phenotypes(ctx, n, Y, k);
     if (rc) return rc;
@@ -1440,14 +1421,12 @@ __global__ void k_accumulate(double *__restrict__ acc, const double *__restrict_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) acc[i] += x[i];
 }
-struct HostPathRes { // whatever pg_ols_kinship holds while it runs; released on every exit path
-    double *Gd = nullptr, *out = nullptr, *S_acc = nullptr, *S_slab = nullptr;
+struct HostPathRes { // the copy stream and the events pg_ols_kinship holds while it runs; released on every exit path
     hipStream_t copy = nullptr;
     std::vector<hipEvent_t> ev;
     ~HostPathRes() {
         if (copy) { (void)hipStreamSynchronize(copy); (void)hipStreamDestroy(copy); }
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        (void)hipFree(Gd); (void)hipFree(out); (void)hipFree(S_acc); (void)hipFree(S_slab);
     }
 };
 } // namespace
@@ -1475,22 +1454,25 @@ extern "C" int pg_ols_kinship(pg_ctx *ctx, const double *G, int64_t p, int n, in
     int64_t slab_loci = ((int64_t)slab_mb << 20) / (ld * 8);
     slab_loci = std::max<int64_t>(1024, slab_loci / 1024 * 1024); // a multiple of the sweep's super-row tiles
     const int nslab = (int)((p + slab_loci - 1) / slab_loci);
-    HostPathRes R;
     const size_t gbytes = (size_t)p * ld * sizeof(double);
     const size_t ocnt = (size_t)p * k;
-    if (hipMalloc((void **)&R.Gd, gbytes) != hipSuccess || hipMalloc((void **)&R.out, 3 * ocnt * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&R.S_acc, sizeof(double) * n * n) != hipSuccess || hipMalloc((void **)&R.S_slab, sizeof(double) * n * n) != hipSuccess)
-        return pg_fail(ctx, PG_ERR_HIP, "ols_kinship: out of device memory (%.1f GB for the matrix)", gbytes / 1e9);
+    DevBuf<double> Gd, out, S_acc, S_slab; // (declared before R: the copy stream is drained before they go)
+    HostPathRes R;
+    int rc = Gd.alloc(ctx, gbytes, "ols_kinship");
+    if (!rc) rc = out.alloc(ctx, 3 * ocnt * sizeof(double), "ols_kinship");
+    if (!rc) rc = S_acc.alloc(ctx, sizeof(double) * n * n, "ols_kinship");
+    if (!rc) rc = S_slab.alloc(ctx, sizeof(double) * n * n, "ols_kinship");
+    if (rc) return rc;
     PG_HIP(ctx, hipStreamCreateWithFlags(&R.copy, hipStreamNonBlocking));
     R.ev.resize((size_t)2 * nslab + 1, nullptr);
     for (auto &e : R.ev) PG_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    PG_HIP(ctx, hipMemsetAsync(R.S_acc, 0, sizeof(double) * n * n, ctx->stream));
-    int rc = pg_set_phenotypes(ctx, 0, nullptr, 0); // the fused intercept-only sums belong to the resident path
+    PG_HIP(ctx, hipMemsetAsync(S_acc, 0, sizeof(double) * n * n, ctx->stream));
+    rc = pg_set_phenotypes(ctx, 0, nullptr, 0); // the fused intercept-only sums belong to the resident path
     if (rc) return rc;
     // ---- phase 1: H2D of slab s + 1 || partial kinship of slab s ------------------------------------------------
     auto h2d = [&](int sidx) -> hipError_t {
         const int64_t lo = (int64_t)sidx * slab_loci, cnt = std::min(slab_loci, p - lo);
-        hipError_t e = hipMemcpyAsync(R.Gd + lo * ld, G + lo * ld, (size_t)cnt * ld * sizeof(double), hipMemcpyHostToDevice, R.copy);
+        hipError_t e = hipMemcpyAsync(Gd + lo * ld, G + lo * ld, (size_t)cnt * ld * sizeof(double), hipMemcpyHostToDevice, R.copy);
         if (e != hipSuccess) return e;
         return hipEventRecord(R.ev[sidx], R.copy);
     };
@@ -1498,20 +1480,20 @@ extern "C" int pg_ols_kinship(pg_ctx *ctx, const double *G, int64_t p, int n, in
     for (int sidx = 0; sidx < nslab; ++sidx) {
         const int64_t lo = (int64_t)sidx * slab_loci, cnt = std::min(slab_loci, p - lo);
         PG_HIP(ctx, hipStreamWaitEvent(ctx->stream, R.ev[sidx], 0));
-        rc = pg_launch_kinship(ctx, R.Gd + lo * ld, cnt, n, ld, R.S_slab, false, PG_K_KINSHIP, false);
+        rc = pg_launch_kinship(ctx, Gd + lo * ld, cnt, n, ld, S_slab, false, PG_K_KINSHIP, false);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_accumulate, dim3((n * n + 255) / 256), dim3(256), 0, ctx->stream, R.S_acc, R.S_slab, n * n);
+        hipLaunchKernelGGL(k_accumulate, dim3((n * n + 255) / 256), dim3(256), 0, ctx->stream, S_acc, S_slab, n * n);
         PG_HIP(ctx, hipGetLastError());
         if (sidx + 1 < nslab) PG_HIP(ctx, h2d(sidx + 1)); // queued behind nothing but the previous slab's copy
     }
     // ---- the n x n step ---------------------------------------------------------------------------------------------
-    rc = pg_kinship_set(ctx, R.S_acc, p, n, Y, k, var_explained, force_m, m_out, K_out, nullptr);
+    rc = pg_kinship_set(ctx, S_acc, p, n, Y, k, var_explained, force_m, m_out, K_out, nullptr);
     if (rc) return rc;
     // ---- phase 2: sweep of slab s + 1 || D2H of the results of slab s -------------------------------------------
-    double *ob = R.out, *ov = R.out + ocnt, *op = R.out + 2 * ocnt;
+    double *ob = out, *ov = out + ocnt, *op = out + 2 * ocnt;
     for (int sidx = 0; sidx < nslab; ++sidx) {
         const int64_t lo = (int64_t)sidx * slab_loci, cnt = std::min(slab_loci, p - lo);
-        rc = pg_ols_sweep_dev(ctx, R.Gd + lo * ld, cnt, n, ld, ob + lo * k, ov + lo * k, op + lo * k);
+        rc = pg_ols_sweep_dev(ctx, Gd + lo * ld, cnt, n, ld, ob + lo * k, ov + lo * k, op + lo * k);
         if (rc) return rc;
         hipEvent_t done = R.ev[(size_t)nslab + sidx];
         PG_HIP(ctx, hipEventRecord(done, ctx->stream));
@@ -1572,35 +1554,32 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
     const int cols = round_cols(ncol);
     if (cols < 0) return pg_fail(ctx, PG_ERR_UNSUPPORTED, "gp: at most %d coefficient columns per pass", PG_MAX_SWEEP_COLS);
     const int n_even = (n + 1) & ~1;
-    std::vector<double> Z((size_t)n_even * cols, 0.0);
-    for (int i = 0; i < n; ++i)
-        for (int c = 0; c < ncol; ++c) Z[(size_t)i * cols + c] = Z_host[(size_t)i * ncol + c];
-    const size_t zbytes = Z.size() * sizeof(double);
-    if (zbytes > ctx->W_cap) {
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->W_dev) PG_HIP(ctx, hipFree(ctx->W_dev));
-        ctx->W_dev = nullptr; ctx->W_cap = 0;
-        PG_HIP(ctx, hipMalloc((void **)&ctx->W_dev, zbytes));
-        ctx->W_cap = zbytes;
-    }
-    ctx->st_m = -1; // the regression state in W_dev is gone
-    ctx->st_Y.clear();
-    PG_HIP(ctx, hipMemcpyAsync(ctx->W_dev, Z.data(), zbytes, hipMemcpyHostToDevice, ctx->stream));
-    SweepDims D;
-    std::memset(&D, 0, sizeof D);
-    D.p = p; D.ld = ld; D.ntiles = (p + 63) / 64; D.n = n; D.k = ncol; D.colmajor = colmajor;
+    // W_dev = Z_host zero-padded to `rows` x `pitch`; Zp has to outlive the copy (the callers synchronise after their launch)
+    auto upload_Z = [&](std::vector<double> &Zp, int rows, int pitch) -> int {
+        Zp.assign((size_t)rows * pitch, 0.0);
+        for (int i = 0; i < n; ++i)
+            for (int c = 0; c < ncol; ++c) Zp[(size_t)i * pitch + c] = Z_host[(size_t)i * ncol + c];
+        const size_t zbytes = Zp.size() * sizeof(double);
+        const int rc = ctx->W_dev.reserve(ctx, zbytes, "gp");
+        if (rc) return rc;
+        ctx->st_m = -1; // the regression state in W_dev is gone
+        ctx->st_Y.clear();
+        PG_HIP(ctx, hipMemcpyAsync(ctx->W_dev, Zp.data(), zbytes, hipMemcpyHostToDevice, ctx->stream));
+        return PG_OK;
+    };
+    std::vector<double> Z, Z16;
+    int rc = upload_Z(Z, n_even, cols);
+    if (rc) return rc;
+    SweepArgs P = sweep_args(ctx, G_dev, p, n, ld);
+    P.beta = out_dev;
+    SweepDims &D = P.D;
+    D.ntiles = (p + 63) / 64; D.k = ncol; D.colmajor = colmajor;
     D.ss = ss_out_dev; // (only the scalar-operand kernel below writes it)
-    D.lz = nullptr;
     int64_t blocks = (D.ntiles + SW_WAVES - 1) / SW_WAVES;
     const int64_t cap = (int64_t)ctx->cus * 8;
     const int grid = (int)(blocks < cap ? blocks : cap);
-    int rc;
     // the matrix-core kernel of the sweep in its products-only mode: every shape, one read of G at the sweep's rate
     if (ms_fits(n, ncol, 1) && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && !std::getenv("POOLGEN_GP_BETA_OLD")) {
-        SweepArgs P;
-        P.G = G_dev; P.W = ctx->W_dev; P.syy = nullptr; P.tcoef = nullptr;
-        P.beta = out_dev; P.var = nullptr; P.pval = nullptr;
-        P.D = D;
         rc = launch_sweep_mfma<1>(ctx, P, cols, ncol, PG_K_GP_BETA);
         if (rc) return rc;
         PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z is stack-owned
@@ -1611,18 +1590,8 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
     const int zrows = (n + SW_CH - 1) / SW_CH * SW_CH;
     const size_t mfma_lds = ((size_t)zrows * 16 + (size_t)SW_WAVES * MB_TILE) * sizeof(double);
     if (!ss_out_dev && colmajor && ncol >= 5 && ncol <= 16 && mfma_lds <= 150 * 1024 && !std::getenv("POOLGEN_GP_BETA_VALU")) {
-        std::vector<double> Z16((size_t)zrows * 16, 0.0);
-        for (int i = 0; i < n; ++i)
-            for (int c = 0; c < ncol; ++c) Z16[(size_t)i * 16 + c] = Z_host[(size_t)i * ncol + c];
-        const size_t zb = Z16.size() * sizeof(double);
-        if (zb > ctx->W_cap) {
-            PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->W_dev) PG_HIP(ctx, hipFree(ctx->W_dev));
-            ctx->W_dev = nullptr; ctx->W_cap = 0;
-            PG_HIP(ctx, hipMalloc((void **)&ctx->W_dev, zb));
-            ctx->W_cap = zb;
-        }
-        PG_HIP(ctx, hipMemcpyAsync(ctx->W_dev, Z16.data(), zb, hipMemcpyHostToDevice, ctx->stream));
+        rc = upload_Z(Z16, zrows, 16);
+        if (rc) return rc;
         PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_gp_beta_mfma), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)mfma_lds));
         const int64_t nblocks = (D.ntiles + SW_WAVES - 1) / SW_WAVES;
@@ -1639,28 +1608,14 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
     const size_t lds_need = ((size_t)wdoubles + (size_t)SW_WAVES * SW_TILE) * sizeof(double);
     if (!ss_out_dev && cols >= 6 && (cols % 2) == 0 && cols <= 24 && (size_t)wdoubles * sizeof(double) > 12288 && lds_need <= 150 * 1024 &&
         !std::getenv("POOLGEN_GP_BETA_SCALAR")) {
-        switch (cols) {
-        case 6: rc = launch_gp_beta_lds<6>(ctx, G_dev, ctx->W_dev, out_dev, D, wdoubles); break;
-        case 8: rc = launch_gp_beta_lds<8>(ctx, G_dev, ctx->W_dev, out_dev, D, wdoubles); break;
-        case 12: rc = launch_gp_beta_lds<12>(ctx, G_dev, ctx->W_dev, out_dev, D, wdoubles); break;
-        case 16: rc = launch_gp_beta_lds<16>(ctx, G_dev, ctx->W_dev, out_dev, D, wdoubles); break;
-        default: rc = launch_gp_beta_lds<24>(ctx, G_dev, ctx->W_dev, out_dev, D, wdoubles); break;
-        }
+        rc = with_cols_in<24, 16, 12, 8, 6>(ctx, cols, [&](auto c) {
+            return launch_gp_beta_lds<decltype(c)::value>(ctx, G_dev, ctx->W_dev, out_dev, D, wdoubles);
+        });
         if (rc) return rc;
         PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z is stack-owned
         return PG_OK;
     }
-    switch (cols) {
-    case 2: rc = launch_gp_beta<2>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    case 3: rc = launch_gp_beta<3>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    case 4: rc = launch_gp_beta<4>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    case 6: rc = launch_gp_beta<6>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    case 8: rc = launch_gp_beta<8>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    case 12: rc = launch_gp_beta<12>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    case 16: rc = launch_gp_beta<16>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    case 24: rc = launch_gp_beta<24>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    default: rc = launch_gp_beta<PG_MAX_SWEEP_COLS>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); break;
-    }
+    rc = with_cols(ctx, cols, [&](auto c) { return launch_gp_beta<decltype(c)::value>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); });
     if (rc) return rc;
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z is stack-owned
     return PG_OK;
@@ -1713,14 +1668,8 @@ extern "C" int pg_gp_ols_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n,
     if (XXt_host_or_null) {
         std::memcpy(full.data(), XXt_host_or_null, sizeof(double) * n * n);
     } else {
-        if (ctx->S_n < n) {
-            PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->S_dev) PG_HIP(ctx, hipFree(ctx->S_dev));
-            ctx->S_dev = nullptr; ctx->S_n = 0;
-            PG_HIP(ctx, hipMalloc((void **)&ctx->S_dev, sizeof(double) * n * n));
-            ctx->S_n = n;
-        }
-        int rc = pg_launch_kinship(ctx, G_dev, p, n, ld, ctx->S_dev, true, PG_K_GP_XXT);
+        int rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "gp_ols");
+        if (!rc) rc = pg_launch_kinship(ctx, G_dev, p, n, ld, ctx->S_dev, true, PG_K_GP_XXT);
         if (rc) return rc;
         PG_HIP(ctx, hipMemcpyAsync(full.data(), ctx->S_dev, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream));
         PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1787,14 +1736,13 @@ extern "C" int pg_gp_proxy_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int 
     std::vector<double> T((size_t)n * n), glast(n);
     if (XXt_host_or_null) std::memcpy(T.data(), XXt_host_or_null, sizeof(double) * n * n);
     else {
-        double *S = nullptr;
-        PG_HIP(ctx, hipMalloc((void **)&S, sizeof(double) * n * n));
-        int rc = pg_gp_xxt_dev(ctx, G_dev, p, n, ld, S);
-        if (rc == PG_OK && (hipMemcpyAsync(T.data(), S, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                            hipStreamSynchronize(ctx->stream) != hipSuccess))
-            rc = pg_fail(ctx, PG_ERR_HIP, "gp_proxy: D2H failed");
-        (void)hipFree(S);
+        DevBuf<double> S;
+        int rc = S.alloc(ctx, sizeof(double) * n * n, "gp_proxy");
+        if (!rc) rc = pg_gp_xxt_dev(ctx, G_dev, p, n, ld, S.get());
         if (rc) return rc;
+        if (hipMemcpyAsync(T.data(), S.get(), sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            return pg_fail(ctx, PG_ERR_HIP, "gp_proxy: D2H failed");
     }
     PG_HIP(ctx, hipMemcpyAsync(glast.data(), G_dev + (p - 1) * ld, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1829,45 +1777,38 @@ extern "C" int pg_gp_proxy_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int 
     bool identity = nr == n && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0;
     for (int a = 0; a < nr && identity; ++a) identity = row_idx[a] == a;
     const int64_t ld2 = identity ? ld : nr + (nr & 1);
-    double *Gs = nullptr, *scratch = nullptr;
-    int32_t *rows_dev = nullptr;
     std::vector<int32_t> rows32(nr);
     for (int a = 0; a < nr; ++a) rows32[a] = (int32_t)row_idx[a];
-    auto cleanup = [&] { if (!identity) (void)hipFree(Gs); (void)hipFree(scratch); (void)hipFree(rows_dev); };
-    if ((!identity && hipMalloc((void **)&Gs, sizeof(double) * (size_t)p * ld2) != hipSuccess) ||
-        hipMalloc((void **)&scratch, sizeof(double) * (size_t)p * k) != hipSuccess ||
-        hipMalloc((void **)&rows_dev, sizeof(int32_t) * nr) != hipSuccess) {
-        cleanup();
-        return pg_fail(ctx, PG_ERR_HIP, "gp_proxy: out of device memory");
-    }
-    if (hipMemcpyAsync(rows_dev, rows32.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        cleanup();
+    DevBuf<double> Gs_own, scratch; // Gs_own: the compacted copy; the launches read `Gs`, which is the caller's G when nothing is compacted
+    DevBuf<int32_t> rows_dev;
+    int rc = identity ? PG_OK : Gs_own.alloc(ctx, sizeof(double) * (size_t)p * ld2, "gp_proxy");
+    if (!rc) rc = scratch.alloc(ctx, sizeof(double) * (size_t)p * k, "gp_proxy");
+    if (!rc) rc = rows_dev.alloc(ctx, sizeof(int32_t) * nr, "gp_proxy");
+    if (rc) return rc;
+    if (hipMemcpyAsync(rows_dev.get(), rows32.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         return pg_fail(ctx, PG_ERR_HIP, "gp_proxy: H2D failed");
-    }
-    if (identity) Gs = const_cast<double *>(G_dev);
-    else
+    const double *Gs = identity ? G_dev : Gs_own.get();
+    if (!identity)
         hipLaunchKernelGGL(k_gather_pools, dim3((unsigned)(((size_t)p * ld2 + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, p, ld,
-                           rows_dev, nr, ld2, Gs);
-    int rc = pg_covariates_set(ctx, nr, ev.data(), 1, Ys.data(), k);
-    if (rc == PG_OK) rc = pg_ols_sweep_dev(ctx, Gs, p, nr, ld2, proxy_dev + k, scratch, scratch);
-    if (rc == PG_OK) {
-        // y ~ a0 + b0 PC1 for the constant loci
-        ProxyFix F{};
-        double s1 = 0.0, s2 = 0.0;
-        for (int a = 0; a < nr; ++a) { s1 += ev[a]; s2 += ev[a] * ev[a]; }
-        const double det = (double)nr * s2 - s1 * s1;
-        for (int j = 0; j < k; ++j) {
-            double sy = 0.0, sey = 0.0;
-            for (int a = 0; a < nr; ++a) { sy += Ys[(size_t)a * k + j]; sey += ev[a] * Ys[(size_t)a * k + j]; }
-            F.a0[j] = (s2 * sy - s1 * sey) / det;
-        }
-        hipLaunchKernelGGL(k_proxy_fix_constant, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, Gs, p, nr, ld2, F, k,
-                           proxy_dev + k);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(proxy_dev, ymean.data(), sizeof(double) * k, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            rc = pg_fail(ctx, PG_ERR_HIP, "gp_proxy: closing step failed");
+                           rows_dev.get(), nr, ld2, Gs_own.get());
+    rc = pg_covariates_set(ctx, nr, ev.data(), 1, Ys.data(), k);
+    if (!rc) rc = pg_ols_sweep_dev(ctx, Gs, p, nr, ld2, proxy_dev + k, scratch.get(), scratch.get());
+    if (rc) return rc;
+    // y ~ a0 + b0 PC1 for the constant loci
+    ProxyFix F{};
+    double s1 = 0.0, s2 = 0.0;
+    for (int a = 0; a < nr; ++a) { s1 += ev[a]; s2 += ev[a] * ev[a]; }
+    const double det = (double)nr * s2 - s1 * s1;
+    for (int j = 0; j < k; ++j) {
+        double sy = 0.0, sey = 0.0;
+        for (int a = 0; a < nr; ++a) { sy += Ys[(size_t)a * k + j]; sey += ev[a] * Ys[(size_t)a * k + j]; }
+        F.a0[j] = (s2 * sy - s1 * sey) / det;
     }
-    cleanup();
-    return rc;
+    hipLaunchKernelGGL(k_proxy_fix_constant, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, Gs, p, nr, ld2, F, k,
+                       proxy_dev + k);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(proxy_dev, ymean.data(), sizeof(double) * k, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return pg_fail(ctx, PG_ERR_HIP, "gp_proxy: closing step failed");
+    return PG_OK;
 }

@@ -469,6 +469,30 @@ def test_gp_ridge_leftover_group_only_trains(engine, oracle):
     assert np.allclose(beta.cpu().numpy(), rb, rtol=1e-10, atol=1e-11 * np.abs(rb).max())
 
 
+def test_gp_ridge_error_return_gives_memory_back(engine):
+    """A fold id out of range is found after gp_ridge has allocated its work buffer (16 doubles per locus and more), so
+    the error return has to release it.  32 failing calls may not cost the device half of 32 work buffers; a leak
+    would cost all of them, and the half is the margin for whatever else allocates on the card meanwhile."""
+    from poolgen_amd import NativeError
+    n, p, n_folds, calls = 8, 600_000, 2, 32
+    work_bytes = 8 * 16 * p   # the p x GP_LMAX coefficient block alone; the partial sums come on top
+    assert work_bytes >= 64 << 20
+    G, Y = make(p, n, 83)
+    Y = Y[:, :1]
+    rows = np.arange(n)
+    folds = (np.arange(n) % n_folds)[None, :].copy()
+    folds[0, -1] = n_folds + 1
+    torch.cuda.synchronize()
+    free_before, _ = torch.cuda.mem_get_info()
+    for _ in range(calls):
+        with pytest.raises(NativeError, match="fold id out of range"):
+            engine.gp_ridge(G, Y, rows, folds, n_folds, alpha=0.0, n=n)
+    torch.cuda.synchronize()
+    free_after, _ = torch.cuda.mem_get_info()
+    print(f"free before {free_before} after {free_after}: fell by {free_before - free_after} of {calls * work_bytes} at stake")
+    assert free_before - free_after < calls * work_bytes // 2
+
+
 @pytest.mark.parametrize("n,p,k,rows", [(40, 3000, 2, None), (50, 2001, 1, "odd"), (64, 1500, 2, "drop")])
 def test_gp_proxy_matches_oracle(engine, oracle, exact, n, p, k, rows):
     """ols_iterative_with_kinship_pca_covariate (gp/ols.rs:104-199): per-locus coefficient of y ~ [1 | PC1 | g] on the
