@@ -140,7 +140,9 @@ int pg_thin_qr(const double *Z, int n, int c, double *Q);
 std::vector<double> pg_tdist_coef(int df);
 // symmetric pseudo-inverse with the reference's tolerance (helpers.rs:463-482)
 int pg_pinv_sym(const double *A, int n, double *out);
-int pg_gp_subset_solve(const double *xxt, int n, const double *Y, int k, const int64_t *rows, int r, double *V);
+// X X^T of the full data (n x n, intercept included) on the host: the caller's copy, or the kinship pass and a copy (pg_gp.hip)
+int pg_gp_xxt_host(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *given_or_null, const char *who,
+                   std::vector<double> &xxt);
 int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Z_host, int ncol,
                     double *out_dev, int colmajor = 0, double *ss_out_dev = nullptr); // out p x ncol, or ncol x p when colmajor; ss: g'g per row
 int pg_pinv_solve_sym(const double *A, int n, const double *B, int k, double *X); // pinv(A) B, Cholesky when A is safely SPD

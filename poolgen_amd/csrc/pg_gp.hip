@@ -1,4 +1,5 @@
-// pg_gp.hip -- ridge-like penalised genomic prediction (gp/penalise.rs:133-159, :248-669).
+// pg_gp.hip -- genomic prediction: gp::ols (gp/ols.rs:8-101) and the penalised models over it, the ridge-like lambda
+// path with k-fold cross-validation (gp/penalise.rs:133-159, :248-669).
 //
 // Reference flow (alpha = 0, iterative = false): for r repetitions x nfolds folds: b = gp::ols on the
 // training pools; for every lambda of the path: b_lambda = expand_and_contract(b, b, alpha, lambda)
@@ -7,24 +8,29 @@
 // all-rows fit.  The reference draws folds from an unseeded thread_rng (:452-453); here the fold of
 // every training row in every repetition is an explicit argument, so results are reproducible.
 //
-// GPU decomposition per (repetition, fold):
-//   1. pg_gp_ols_dev              b (1+p) x k        one streaming pass over G (k_gp_beta)
-//   2. k_gp_norm_max              max of the penalty norm over the p slopes
-//   3. k_gp_path_sums             for all L lambdas at once: the four redistribution masses of
-//                                 expand_and_contract (one pass over b)
-//   4. k_gp_blambda               B[l][i] = expand_and_contract(b)[l] for lambda_i   (p x L)
-//   5. k_gp_predict (+ reduce)    yhat[pool][lambda] = b0 + sum_l G[l][pool] B[l][lambda]: the second
-//                                 streaming pass over G, all lambdas at once
-//   6. host: error_index on the validation pools (n_val x L numbers)
+// penalised_path: X X^T on the host, the work buffers, one of two cross-validations, then select_and_apply.
+// cv_fused (a wide design): every pool is validated by ONE fold of a repetition, so per repetition
+//   1. FoldSolver (host thread)   pinv(X X^T[train, train]) y of every fold, scattered over the pools (solve_scatter)
+//   2. pg_gp_beta_cols            every fold's slopes as columns G Z: one streaming pass over G per repetition, or
+//                                 (batched) 16 columns per pass whatever repetition they belong to
+//   3. ridge_path_params_cols     per column the max of the penalty norm, then for all L lambdas at once the four
+//                                 redistribution masses of expand_and_contract (one pass over the columns)
+//   4. PredictPipeline            k_gp_predict_folds (+ reduce): yhat[pool][lambda] from the coefficients of the fold that
+//                                 holds the pool out, contracted on the fly: the second streaming pass over G, kept
+//                                 out while the host scores the pass before it (error_index, n_val x L numbers)
+// cv_per_fold (a tall design, too many columns, POOLGEN_RIDGE_PER_FOLD=1) per (repetition, fold): pg_gp_ols_dev, then per trait
+// ridge_path_params (the same masses), k_gp_blambda (B[l][i] = expand_and_contract(b)[l] for lambda_i) and k_gp_predict (+ reduce).
 // All L lambdas share the two passes over G; the reference does 1 + L passes per fold.
 #include "pg_common.h"
 #include <algorithm>
 #include <cmath>
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
-#include <future>
+#include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -453,13 +459,120 @@ double host_pearson_r(const std::vector<double> &x, const std::vector<double> &y
     return std::round(r * 1e7) / 1e7; // sensible_round(r, 7)
 }
 
+// ---- host side: the steps every route shares --------------------------------------------------------------------
+
+// What a call of the path is given (the entry points fill it in the order of their own arguments), and the grid.
+struct GpCall {
+    const double *G; int64_t p; int n; int64_t ld;   // device: p loci x n pools, row pitch ld
+    const double *Y; int k;                          // host: n x k
+    const int64_t *rows; int n_rows;                 // the outer training pools
+    const int32_t *fold_of; int n_reps, n_folds;     // fold of rows[i] in repetition r: fold_of[r * n_rows + i]
+    double alpha;                                    // < 0: the 2-D grid alpha x lambda (:479-498)
+    const double *proxy;                             // device (1 + p) x k of pg_gp_proxy_dev, or null (see Proxy)
+    std::vector<double> path;                        // the lambda values (:470-476); the grid's alpha values are the same
+    int L() const { return (int)path.size(); }
+    int A() const { return alpha >= 0.0 ? 1 : L(); }
+    int C() const { return n_folds * k; }            // fold x trait coefficient columns of one repetition
+    double alpha_at(int a) const { return alpha >= 0.0 ? alpha : path[a]; }
+    // error indices (rep, fold, alpha, lambda, trait) as the reference's `performances` (:509)
+    size_t perf_at(int rep, int fold, int a, int li, int j) const { return ((((size_t)rep * n_folds + fold) * A() + a) * L() + li) * k + j; }
+};
+
+// POOLGEN_GP_TIMING=1: host-side phase times of a call on stderr.  A phase is what runs in the scope of a Phase on its field.
+struct PhaseTimes {
+    using Clock = std::chrono::steady_clock;
+    const bool report = std::getenv("POOLGEN_GP_TIMING") != nullptr;
+    const Clock::time_point entry = Clock::now();
+    double before = 0, solve = 0, beta = 0, params = 0, predict = 0, alloc = 0, release = 0; // seconds
+    static double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
+    void report_phases() const {
+        if (report)
+            std::fprintf(stderr, "gp path: before the repetitions %.1f ms; fold solves %.1f ms, coefficient passes %.1f ms, masses %.1f ms, prediction + scores %.1f ms; the columns' memory: allocation %.1f ms, release %.1f ms; since entry %.1f ms\n",
+                         1e3 * before, 1e3 * solve, 1e3 * beta, 1e3 * params, 1e3 * predict, 1e3 * alloc, 1e3 * release, 1e3 * since(entry));
+    }
+    void report_call() const { if (report) std::fprintf(stderr, "gp path: whole call %.1f ms\n", 1e3 * since(entry)); }
+};
+struct Phase {
+    double &acc;
+    PhaseTimes::Clock::time_point t0 = PhaseTimes::Clock::now();
+    ~Phase() { acc += PhaseTimes::since(t0); }
+};
+
+// f(std::integral_constant<int, LP>{}) for LP = the even path length (upwards: downwards, the same kernels come out in the opposite order)
+template <int LP = 2, typename F>
+void with_path_len(int L, F f) {
+    if (((L + 1) & ~1) == LP) f(std::integral_constant<int, LP>{});
+    else if constexpr (LP < GP_LMAX) with_path_len<LP + 2>(L, f);
+}
+
+// the slabs of loci of a prediction pass: `nblk` blocks of `lpb` loci each
+struct Slabs { int nblk; int64_t lpb; };
+Slabs predict_slabs(const pg_ctx *ctx, int64_t p) {
+    const int want = std::max(1, std::min<int>(ctx->cus * 4, (int)((p + 255) / 256)));
+    const int64_t lpb = (p + want - 1) / want;
+    return Slabs{(int)((p + lpb - 1) / lpb), lpb};
+}
+
 struct RidgeWork {
+    DevBuf<double> raw;
+    Slabs S{0, 0};
     double *part = nullptr;   // block partials (max / path sums / predictions)
     double *B = nullptr;      // p x GP_LMAX
     double *yhat = nullptr;   // n x GP_LMAX
+    int alloc(pg_ctx *ctx, const GpCall &in) {
+        S = predict_slabs(ctx, in.p);
+        const size_t C = in.C();
+        const size_t part_doubles = std::max<size_t>((C + 1) * 1024 * 4 * GP_LMAX + C * 4 * GP_LMAX,
+                                                     (size_t)S.nblk * in.n * GP_LMAX * 4); // (x 4: the prediction pass' locus groups at n <= 256)
+        if (int rc = raw.alloc(ctx, sizeof(double) * (part_doubles + (size_t)in.p * GP_LMAX + (size_t)in.n * GP_LMAX), "gp_ridge")) return rc;
+        part = raw.get();
+        B = part + part_doubles;
+        yhat = B + (size_t)in.p * GP_LMAX;
+        return PG_OK;
+    }
 };
 
-// steps 2-4 for trait j of `beta_dev`; returns the path parameters with the masses filled in
+// gp::ols, wide branch (gp/ols.rs:47-72), as far as the host takes it: the fit on the pools `rows` is b = X^T z with
+// z = pinv(A) Y[rows] scattered over the pools and zero elsewhere, A the principal sub-block `rows` of the full-data X X^T
+// (n x n, host).  Fills the columns col0 .. col0 + k - 1 of Z (n rows of `stride`, zero on entry) and adds the intercepts (the
+// column sums: X's first column is all ones) to b0[0 .. k), in row order.  Non-zero when the pinv fails; nothing is written then.
+int solve_scatter(const double *xxt, int n, const double *Y, int k, const int64_t *rows, int r, double *Z, int stride, int col0,
+                  double *b0) {
+    std::vector<double> A((size_t)r * r), Ysub((size_t)r * k), V((size_t)r * k);
+    for (int a = 0; a < r; ++a) {
+        for (int b = 0; b < r; ++b) A[(size_t)a * r + b] = xxt[(size_t)rows[a] * n + rows[b]];
+        for (int j = 0; j < k; ++j) Ysub[(size_t)a * k + j] = Y[(size_t)rows[a] * k + j];
+    }
+    if (pg_pinv_solve_sym(A.data(), r, Ysub.data(), k, V.data()) != 0) return 1;
+    for (int a = 0; a < r; ++a)
+        for (int j = 0; j < k; ++j) {
+            Z[(size_t)rows[a] * stride + col0 + j] = V[(size_t)a * k + j];
+            b0[j] += V[(size_t)a * k + j];
+        }
+    return 0;
+}
+
+PathParams path_params(double alpha, const std::vector<double> &path) { // nmax and the masses still to come
+    PathParams P;
+    std::memset(&P, 0, sizeof P);
+    P.alpha = alpha;
+    P.L = (int)path.size();
+    for (int i = 0; i < P.L; ++i) P.lambda[i] = path[i];
+    return P;
+}
+
+// from the four sums of one lambda (subtracted / added of the penalised set, norms of the de-penalised set by sign) to its two quotients
+void close_masses(double sp, double ap, double sd, double ad, double &sub_scale, double &add_scale) {
+    // "absence of available slots" (:329-335)
+    if ((sp > 0.0) & (sd == 0.0)) { ap -= sp; sp = 0.0; }
+    else if ((ap > 0.0) & (ad == 0.0)) { sp -= ap; ap = 0.0; }
+    // b += subtracted_penalised * (normed / subtracted_depenalised)  (:345-351); 0/0 never reaches a
+    // coefficient because an empty de-penalised side has no coefficients to expand
+    sub_scale = (sd != 0.0) ? sp / sd : 0.0;
+    add_scale = (ad != 0.0) ? ap / ad : 0.0;
+}
+
+// norm maximum, path sums and masses for trait j of `beta_dev` ((1 + p) x k); the blocks' partials are combined on the host, in block order
 int ridge_path_params(pg_ctx *ctx, const double *beta_dev, int64_t p, int k, int j, double alpha,
                       const std::vector<double> &path, RidgeWork &W, PathParams &P, int row0 = 1, Proxy X = Proxy{nullptr, 0, 0}) {
     const int nb = 1024;
@@ -469,19 +582,11 @@ int ridge_path_params(pg_ctx *ctx, const double *beta_dev, int64_t p, int k, int
     PG_HIP(ctx, hipGetLastError());
     PG_HIP(ctx, hipMemcpyAsync(h.data(), W.part, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    double mx = 0.0;
-    for (int b = 0; b < nb; ++b) mx = std::max(mx, h[b]);
-    std::memset(&P, 0, sizeof P);
-    P.alpha = alpha;
-    P.nmax = mx;
-    P.L = (int)path.size();
-    for (int i = 0; i < P.L; ++i) P.lambda[i] = path[i];
-    switch ((P.L + 1) & ~1) {
-#define PG_PATH_SUMS(LPV) case LPV: hipLaunchKernelGGL(k_gp_path_sums<LPV>, dim3(nb), dim3(256), 0, ctx->stream, beta_dev, p, k, j, row0, P, X, W.part); break;
-        PG_PATH_SUMS(2) PG_PATH_SUMS(4) PG_PATH_SUMS(6) PG_PATH_SUMS(8) PG_PATH_SUMS(10) PG_PATH_SUMS(12) PG_PATH_SUMS(14)
-        default: hipLaunchKernelGGL(k_gp_path_sums<GP_LMAX>, dim3(nb), dim3(256), 0, ctx->stream, beta_dev, p, k, j, row0, P, X, W.part); break;
-#undef PG_PATH_SUMS
-    }
+    P = path_params(alpha, path);
+    for (int b = 0; b < nb; ++b) P.nmax = std::max(P.nmax, h[b]);
+    with_path_len(P.L, [&](auto lp) {
+        hipLaunchKernelGGL(k_gp_path_sums<decltype(lp)::value>, dim3(nb), dim3(256), 0, ctx->stream, beta_dev, p, k, j, row0, P, X, W.part);
+    });
     PG_HIP(ctx, hipGetLastError());
     PG_HIP(ctx, hipMemcpyAsync(h.data(), W.part, sizeof(double) * nb * 4 * GP_LMAX, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -491,13 +596,7 @@ int ridge_path_params(pg_ctx *ctx, const double *beta_dev, int64_t p, int k, int
             const double *q = &h[(size_t)b * 4 * GP_LMAX];
             sp += q[i]; ap += q[GP_LMAX + i]; sd += q[2 * GP_LMAX + i]; ad += q[3 * GP_LMAX + i];
         }
-        // "absence of available slots" (:329-335)
-        if ((sp > 0.0) & (sd == 0.0)) { ap -= sp; sp = 0.0; }
-        else if ((ap > 0.0) & (ad == 0.0)) { sp -= ap; ap = 0.0; }
-        // b += subtracted_penalised * (normed / subtracted_depenalised)  (:345-351); 0/0 never reaches a
-        // coefficient because an empty de-penalised side has no coefficients to expand
-        P.sub_scale[i] = (sd != 0.0) ? sp / sd : 0.0;
-        P.add_scale[i] = (ad != 0.0) ? ap / ad : 0.0;
+        close_masses(sp, ap, sd, ad, P.sub_scale[i], P.add_scale[i]);
     }
     return PG_OK;
 }
@@ -523,45 +622,34 @@ __global__ __launch_bounds__(256) void k_gp_reduce_parts(const double *__restric
 
 // ridge_path_params for all columns of `cols_dev` (COLUMN-major, ncols x p: every column is one contiguous stream) at once: the columns' launches queue up behind
 // each other and the host synchronises twice instead of 2 * ncols times.  skip[c] != 0: column not in use.
+// The blocks' partials are combined on the device (k_gp_reduce_parts): not the order of ridge_path_params, so the two are not interchangeable bit for bit.
 int ridge_path_params_cols(pg_ctx *ctx, const double *cols_dev, int64_t p, int ncols, int k, double alpha,
                            const std::vector<double> &path, RidgeWork &W, const double *proxy_dev, const std::vector<int> &skip,
-                           std::vector<PathParams> &out) {
+                           std::vector<FoldMasses> &out) {
     // blocks per column: enough to fill the chip on a long column, few on a short one (every block's 64 partial sums are
     // cleared, written and reduced again: at p = 2e5 that overhead was most of the mass step)
     const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(32, p / 2048));
     const int width = 4 * GP_LMAX;
-    double *red = W.part + (size_t)ncols * nb * width; // room reserved by the caller (sized for nb = 1024)
+    double *red = W.part + (size_t)ncols * nb * width; // room reserved by RidgeWork::alloc (sized for nb = 1024)
     std::vector<double> h((size_t)ncols * width);
-    out.assign(ncols, PathParams{});
+    out.assign(ncols, FoldMasses{}); // (entries beyond the path stay zero)
     PG_HIP(ctx, hipMemsetAsync(W.part, 0, sizeof(double) * (size_t)ncols * nb * width, ctx->stream)); // skipped columns reduce to 0
     // the maxima stay on the device for the path sums (and travel to the host with them, further down)
     double *nmax_dev = red + (size_t)ncols * width;
     int *skip_dev = reinterpret_cast<int *>(nmax_dev + ncols);
     PG_HIP(ctx, hipMemcpyAsync(skip_dev, skip.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gp_norm_max_cols, dim3(nb, ncols), dim3(256), 0, ctx->stream, cols_dev, p, Proxy{proxy_dev, k, 0}, k, alpha, skip_dev,
+    const Proxy X{proxy_dev, k, 0};
+    hipLaunchKernelGGL(k_gp_norm_max_cols, dim3(nb, ncols), dim3(256), 0, ctx->stream, cols_dev, p, X, k, alpha, skip_dev,
                        W.part, (int64_t)nb * width); // every column in one launch (was one launch per column: 200 per config-4 run)
     hipLaunchKernelGGL(k_gp_reduce_parts, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, W.part, ncols, nb, (int64_t)nb * width, 1,
                        1, 1, red);
     PG_HIP(ctx, hipGetLastError());
     PG_HIP(ctx, hipMemcpyAsync(nmax_dev, red, sizeof(double) * ncols, hipMemcpyDeviceToDevice, ctx->stream));
-    PathParams Pc;
-    std::memset(&Pc, 0, sizeof Pc);
-    Pc.alpha = alpha;
-    Pc.L = (int)path.size();
-    for (int i = 0; i < Pc.L; ++i) Pc.lambda[i] = path[i];
-    switch ((Pc.L + 1) & ~1) {
-#define PG_PATH_SUMS(LPV)                                                                                                   \
-    case LPV:                                                                                                               \
-        hipLaunchKernelGGL(k_gp_path_sums_cols<LPV>, dim3(nb, ncols), dim3(256), 0, ctx->stream, cols_dev, p, Pc, Proxy{proxy_dev, k, 0}, k, \
-                           nmax_dev, skip_dev, W.part);                                                                     \
-        break;
-        PG_PATH_SUMS(2) PG_PATH_SUMS(4) PG_PATH_SUMS(6) PG_PATH_SUMS(8) PG_PATH_SUMS(10) PG_PATH_SUMS(12) PG_PATH_SUMS(14)
-        default:
-            hipLaunchKernelGGL(k_gp_path_sums_cols<GP_LMAX>, dim3(nb, ncols), dim3(256), 0, ctx->stream, cols_dev, p, Pc, Proxy{proxy_dev, k, 0}, k,
-                               nmax_dev, skip_dev, W.part);
-            break;
-#undef PG_PATH_SUMS
-    }
+    const PathParams Pc = path_params(alpha, path);
+    with_path_len(Pc.L, [&](auto lp) {
+        hipLaunchKernelGGL(k_gp_path_sums_cols<decltype(lp)::value>, dim3(nb, ncols), dim3(256), 0, ctx->stream, cols_dev, p, Pc, X, k,
+                           nmax_dev, skip_dev, W.part);
+    });
     hipLaunchKernelGGL(k_gp_reduce_parts, dim3((ncols * width + 3) / 4), dim3(256), 0, ctx->stream, W.part, ncols, nb,
                        (int64_t)nb * width, width, width, 0, red);
     PG_HIP(ctx, hipGetLastError());
@@ -570,423 +658,474 @@ int ridge_path_params_cols(pg_ctx *ctx, const double *cols_dev, int64_t p, int n
     PG_HIP(ctx, hipMemcpyAsync(hmax.data(), nmax_dev, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `skip` (the caller's) has been consumed as well
     for (int c = 0; c < ncols; ++c) {
-        PathParams &P = out[c];
-        P = Pc;
-        P.nmax = hmax[c];
-        if (skip[c]) continue;
+        FoldMasses &M = out[c];
+        M.nmax = skip[c] ? 1.0 : hmax[c];
         const double *q = &h[(size_t)c * width];
-        for (int i = 0; i < P.L; ++i) {
-            double sp = q[i], ap = q[GP_LMAX + i], sd = q[2 * GP_LMAX + i], ad = q[3 * GP_LMAX + i];
-            if ((sp > 0.0) & (sd == 0.0)) { ap -= sp; sp = 0.0; }      // "absence of available slots" (:329-335)
-            else if ((ap > 0.0) & (ad == 0.0)) { sp -= ap; ap = 0.0; }
-            P.sub_scale[i] = (sd != 0.0) ? sp / sd : 0.0;
-            P.add_scale[i] = (ad != 0.0) ? ap / ad : 0.0;
+        for (int i = 0; i < Pc.L && !skip[c]; ++i) close_masses(q[i], q[GP_LMAX + i], q[2 * GP_LMAX + i], q[3 * GP_LMAX + i], M.sub_scale[i], M.add_scale[i]);
+    }
+    return PG_OK;
+}
+
+// error_index (:359-426) of trait j on the validation pools `iva`, for every lambda, from the slopes' part of the
+// predictions yh (n x GP_LMAX) and the intercept b0j
+void score(const GpCall &in, std::vector<double> &perf, const std::vector<double> &yh, int rep, int fold, int a, int j, double b0j,
+           const std::vector<int64_t> &iva) {
+    const int nv = (int)iva.size(), k = in.k;
+    std::vector<double> yt(nv), yp(nv);
+    double mn = 0, mx = 0;
+    for (int i = 0; i < nv; ++i) {
+        yt[i] = in.Y[(size_t)iva[i] * k + j];
+        if (i == 0 || yt[i] < mn) mn = yt[i];
+        if (i == 0 || yt[i] > mx) mx = yt[i];
+    }
+    for (int li = 0; li < in.L(); ++li) {
+        for (int i = 0; i < nv; ++i) yp[i] = b0j + yh[(size_t)iva[i] * GP_LMAX + li];
+        const double cor = host_pearson_r(yt, yp);
+        double mae = 0, mse = 0;
+        for (int i = 0; i < nv; ++i) { const double d = yt[i] - yp[i]; mae += std::fabs(d); mse += d * d; }
+        mae /= (mx - mn);
+        mse /= ((mx - mn) * (mx - mn));
+        const double rmse = std::sqrt(mse) / (mx - mn);
+        perf[in.perf_at(rep, fold, a, li, j)] = ((1.0 - std::fabs(cor)) + mae + mse + rmse) / 4.0;
+    }
+}
+
+// ---- the fused cross-validation -------------------------------------------------------------------------------
+
+// the host's part of the fits of one repetition (or, with no folds and k columns, of the all-rows fit)
+struct RepSolve {
+    std::vector<std::vector<int64_t>> tr, va; // per fold: training and validation pools
+    std::vector<double> Z, b0c;               // n x columns: pinv(X X^T) y scattered over the pools; the columns' intercepts
+    bool bad = false;                         // a pinv failed
+    bool live(int f) const { return !va[f].empty() && !tr[f].empty(); } // an empty fold leaves NaN, as an empty slice would
+    void split(const GpCall &in, int rep) {   // tr, va of repetition `rep`, pools in row order
+        tr.assign(in.n_folds, {}); va.assign(in.n_folds, {});
+        for (int i = 0; i < in.n_rows; ++i) {
+            const int f = in.fold_of[(size_t)rep * in.n_rows + i];
+            for (int g = 0; g < in.n_folds; ++g) (g == f ? va[g] : tr[g]).push_back(in.rows[i]);
         }
+    }
+};
+
+// The folds' host solves need nothing from the GPU but X X^T: a background thread works through the repetitions (one
+// worker thread per fold inside), then the all-rows fit, ahead of the device passes.  The destructor joins it.
+class FoldSolver {
+    const GpCall &in_;
+    const double *xxt_;
+    std::vector<RepSolve> fits_; // [n_reps] is the all-rows fit (gp/ols.rs:47-72 on `rows`)
+    std::mutex m_;
+    std::condition_variable cv_;
+    int done_ = 0;               // fits_[0 .. done_) are final
+    std::thread th_;
+
+    void solve_rep(RepSolve &R, int rep) const {
+        const int n_folds = in_.n_folds, k = in_.k, C = in_.C();
+        R.split(in_, rep);
+        R.Z.assign((size_t)in_.n * C, 0.0); R.b0c.assign(C, 0.0);
+        std::vector<int> badf(n_folds, 0);
+        std::vector<std::thread> th;
+        for (int f = 0; f < n_folds; ++f)
+            if (R.live(f))
+                th.emplace_back([&, f] {
+                    badf[f] = solve_scatter(xxt_, in_.n, in_.Y, k, R.tr[f].data(), (int)R.tr[f].size(), R.Z.data(), C, f * k, &R.b0c[f * k]);
+                });
+        for (auto &x : th) x.join();
+        for (int f = 0; f < n_folds; ++f) R.bad = R.bad || badf[f];
+    }
+
+public:
+    FoldSolver(const GpCall &in, const double *xxt, bool with_all_rows) : in_(in), xxt_(xxt), fits_(in.n_reps + 1) {
+        th_ = std::thread([this, with_all_rows] {
+            for (int r = 0; r <= in_.n_reps; ++r) {
+                RepSolve &R = fits_[r];
+                if (r < in_.n_reps) solve_rep(R, r);
+                else if (with_all_rows) {
+                    R.Z.assign((size_t)in_.n * in_.k, 0.0); R.b0c.assign(in_.k, 0.0);
+                    R.bad = solve_scatter(xxt_, in_.n, in_.Y, in_.k, in_.rows, in_.n_rows, R.Z.data(), in_.k, 0, R.b0c.data()) != 0;
+                }
+                { std::lock_guard<std::mutex> g(m_); ++done_; }
+                cv_.notify_all();
+            }
+        });
+    }
+    ~FoldSolver() { th_.join(); }
+    const RepSolve *wait(int r) { // repetition r, or at n_reps the all-rows fit; null when one of its pinvs failed
+        std::unique_lock<std::mutex> g(m_);
+        cv_.wait(g, [&] { return done_ > r; });
+        return fits_[r].bad ? nullptr : &fits_[r];
+    }
+};
+
+// One prediction pass is kept OUT while the host goes on (the next repetition's coefficient passes, the next masses, the
+// scores of the pass before): its predictions land in yh_in_[turn], the small host arrays its copies read stay alive in
+// turn.  The destructor waits for whatever is still out: no return leaves a copy in flight into or out of this staging.
+class PredictPipeline {
+    pg_ctx *ctx_;
+    const GpCall &in_;
+    RidgeWork &W_;
+    FoldMasses *fm_dev_;        // C
+    int32_t *colof_dev_;        // n
+    std::vector<double> &perf_;
+    std::vector<double> yh_in_[2];
+    std::vector<int32_t> colof_h_[2];
+    std::vector<FoldMasses> fm_h_[2];
+    int fm_turn_ = 0;
+    struct Pending { const RepSolve *R; int rep, a, j, turn; } pend_{nullptr, 0, 0, 0, 0}; // R == null: nothing out
+    bool busy_ = false;         // something has been queued since the last synchronisation this object has seen
+    PathParams P0_;             // alpha and the path of the launches that follow (set_masses)
+
+    void score_pass(const Pending &q) {
+        for (int f = 0; f < in_.n_folds; ++f)
+            if (q.R->live(f)) score(in_, perf_, yh_in_[q.turn], q.rep, f, q.a, q.j, q.R->b0c[f * in_.k + q.j], q.R->va[f]);
+    }
+
+public:
+    PredictPipeline(pg_ctx *ctx, const GpCall &in, RidgeWork &W, FoldMasses *fm_dev, int32_t *colof_dev, std::vector<double> &perf)
+        : ctx_(ctx), in_(in), W_(W), fm_dev_(fm_dev), colof_dev_(colof_dev), perf_(perf) {}
+    ~PredictPipeline() { if (busy_) (void)hipStreamSynchronize(ctx_->stream); }
+
+    // the redistribution masses of every (fold, trait) column of repetition R (bfr: its C columns) for the launches that follow.
+    // Their own launches queue up behind the prediction pass that is still out, so the latency of this chain of small kernels
+    // and of its synchronisation is the device's busy time
+    int set_masses(const RepSolve &R, const double *bfr, double alpha) {
+        const int C = in_.C(), k = in_.k;
+        std::vector<FoldMasses> &fm = fm_h_[fm_turn_ ^= 1];
+        std::vector<int> skip(C, 0);
+        for (int c = 0; c < C; ++c) skip[c] = !R.live(c / k);
+        if (int rc = ridge_path_params_cols(ctx_, bfr, in_.p, C, k, alpha, in_.path, W_, in_.proxy, skip, fm)) return rc;
+        P0_ = path_params(alpha, in_.path); // alpha, lambda[], L are the same for every column; the masses travel in fm
+        busy_ = true;
+        if (hipMemcpyAsync(fm_dev_, fm.data(), sizeof(FoldMasses) * C, hipMemcpyHostToDevice, ctx_->stream) != hipSuccess)
+            return pg_fail(ctx_, PG_ERR_HIP, "gp_ridge: H2D failed");
+        return PG_OK;
+    }
+
+    // the pass of trait j (repetition `rep` and alpha index a, as set_masses was last given); scores the pass before it meanwhile
+    int launch(const RepSolve &R, const double *bfr, int rep, int a, int j) {
+        const int n = in_.n, n_folds = in_.n_folds, k = in_.k, C = in_.C();
+        // (the masses' synchronisation has seen the pass that was out: its predictions are on the host)
+        const Pending prev = pend_;
+        const int turn = prev.R ? (prev.turn ^ 1) : 0;
+        std::vector<int32_t> &colof = colof_h_[turn];
+        colof.assign(n, -1);
+        yh_in_[turn].resize((size_t)n * GP_LMAX);
+        for (int f = 0; f < n_folds; ++f)
+            if (R.live(f))
+                for (int64_t pool : R.va[f]) colof[pool] = f * k + j;
+        if (prev.R && hipStreamSynchronize(ctx_->stream) != hipSuccess) // (a no-op after the masses' own; the k > 1 traits of one alpha need it)
+            return pg_fail(ctx_, PG_ERR_HIP, "gp_ridge: prediction pass failed");
+        busy_ = true;
+        if (hipMemcpyAsync(colof_dev_, colof.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx_->stream) != hipSuccess)
+            return pg_fail(ctx_, PG_ERR_HIP, "gp_ridge: H2D failed");
+        const int LPr = (P0_.L + 1) & ~1;
+        const size_t masses_b = sizeof(double) * n_folds * (2 * GP_LMAX + 1);
+        const int chunk = std::max(4, std::min(64, (int)((49152 - masses_b) / (sizeof(double) * n_folds * (LPr + 2)))));
+        const int bthreads = n > 128 ? 512 : 256; // the coefficient stage is shared by all waves of a block
+        const int groups = n <= 256 ? bthreads / (((n + 63) / 64) * 64) : 1; // locus groups inside a block (n <= 256: 2 .. 4)
+        const dim3 grid(W_.S.nblk, groups > 1 ? 1 : (n + bthreads - 1) / bthreads);
+        const size_t lds = sizeof(double) * chunk * n_folds * (LPr + 2) + masses_b;
+        const Proxy X{in_.proxy, k, j};
+        pg_prof_begin(ctx_, PG_K_GP_PREDICT);
+        with_path_len(P0_.L, [&](auto lp) {
+            constexpr int LP = decltype(lp)::value;
+            auto go = [&](auto kern, int g) {
+                hipLaunchKernelGGL(kern, grid, dim3(bthreads), lds, ctx_->stream, in_.G, bfr, C, colof_dev_, fm_dev_, P0_, X, in_.p, n, in_.ld,
+                                   W_.S.lpb, chunk, W_.part, g);
+            };
+            if (P0_.L & 1) groups > 1 ? go(k_gp_predict_folds<LP, true, true>, groups) : go(k_gp_predict_folds<LP, false, true>, 1);
+            else groups > 1 ? go(k_gp_predict_folds<LP, true, false>, groups) : go(k_gp_predict_folds<LP, false, false>, 1);
+        });
+        pg_prof_end(ctx_);
+        hipLaunchKernelGGL(k_gp_predict_reduce, dim3((n * GP_LMAX + 63) / 64), dim3(512), 0, ctx_->stream, W_.part, W_.S.nblk * groups, n, W_.yhat);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(yh_in_[turn].data(), W_.yhat, sizeof(double) * n * GP_LMAX, hipMemcpyDeviceToHost, ctx_->stream) != hipSuccess)
+            return pg_fail(ctx_, PG_ERR_HIP, "gp_ridge: prediction pass failed");
+        pend_ = Pending{&R, rep, a, j, turn};
+        // ... and while this pass runs, the host scores the one before it
+        if (prev.R) score_pass(prev);
+        return PG_OK;
+    }
+
+    int drain() { // waits for the last pass out and scores it
+        if (!pend_.R) return PG_OK;
+        if (hipStreamSynchronize(ctx_->stream) != hipSuccess) return pg_fail(ctx_, PG_ERR_HIP, "gp_ridge: prediction pass failed");
+        busy_ = false;
+        score_pass(pend_);
+        pend_.R = nullptr;
+        return PG_OK;
+    }
+};
+
+constexpr int GP_CP = 16; // columns per batched coefficient pass: what the sweep kernel's products mode carries at 500 pools
+
+// All folds of a repetition share two passes over G: one that forms the slopes of every fold's training fit (n_folds * k
+// columns), one (per alpha and trait) that predicts every pool with the coefficients of the fold that holds it out.  Every
+// fit comes from pinv(X X^T) (solve_scatter): the wide branch of gp/ols.rs:47.  Two ways to the slopes, the same bits:
+//   batched   the slopes of ALL repetitions' folds (and of the all-rows fit) are columns G Z of the same matrix: formed GP_CP
+//             at a time, whatever repetition they belong to, they take ceil((n_reps C + k) / GP_CP) passes over G instead of
+//             n_reps + 1 (config 4: 101 columns, 7 passes instead of 11).  Needs the n_reps C + k columns resident (config 4:
+//             4 GB of the 288).  Leaves the all-rows fit in beta_dev (*have_fit).
+//   per rep   one pass per repetition: n_reps == 1, columns that do not fit, or POOLGEN_RIDGE_PER_REP=1.
+int cv_fused(pg_ctx *ctx, const GpCall &in, const std::vector<double> &xxt, RidgeWork &W, PhaseTimes &T, std::vector<double> &perf,
+             double *beta_dev, bool *have_fit) {
+    const int64_t p = in.p;
+    const int n = in.n, k = in.k, C = in.C(), n_reps = in.n_reps;
+    const size_t ncols_all = (size_t)n_reps * C + k;
+    bool batched = n_reps > 1 && !std::getenv("POOLGEN_RIDGE_PER_REP");
+    if (batched) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess || sizeof(double) * (size_t)p * ncols_all > fr / 2) batched = false;
+    }
+    DevBuf<double> bf;          // the slopes, column-major: C x p, batched (n_reps C + k) x p
+    DevBuf<FoldMasses> fm_dev;
+    DevBuf<int32_t> colof_dev;
+    {
+        Phase t{T.alloc};
+        int rc = bf.alloc(ctx, sizeof(double) * (size_t)p * (batched ? ncols_all : (size_t)C), "gp_ridge");
+        if (!rc) rc = fm_dev.alloc(ctx, sizeof(FoldMasses) * C, "gp_ridge");
+        if (!rc) rc = colof_dev.alloc(ctx, sizeof(int32_t) * n, "gp_ridge");
+        if (rc) return rc;
+    }
+    FoldSolver solver(in, xxt.data(), batched);
+    PredictPipeline pipe(ctx, in, W, fm_dev.get(), colof_dev.get(), perf);
+    // batched: the columns [0, formed) of the global numbering (repetition-major, then the all-rows fit) are in bf; one pass
+    // over G per GP_CP more of them
+    size_t formed = 0;
+    auto form_upto = [&](size_t want) -> int {
+        while (formed < want) {
+            // the first pass takes repetition 0 alone when that costs no extra pass: it then waits for ONE repetition's host
+            // solves (5 ms at config 4) instead of two before the device has anything to do
+            const bool short_first = formed == 0 && (size_t)C < (size_t)GP_CP &&
+                                     1 + (ncols_all - C + GP_CP - 1) / GP_CP == (ncols_all + GP_CP - 1) / GP_CP;
+            const size_t c1 = short_first ? (size_t)C : std::min(formed + (size_t)GP_CP, ncols_all);
+            const int nc = (int)(c1 - formed);
+            std::vector<double> Zb((size_t)n * nc, 0.0);
+            for (size_t c = formed; c < c1; ++c) {
+                Phase t{T.solve};
+                const int r = (int)(c / C); // (n_reps: the all-rows fit)
+                const RepSolve *R = solver.wait(r);
+                if (!R) return pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: pinv failed");
+                const int stride = (int)R->b0c.size(), cc = (int)(c - (size_t)r * C);
+                for (int i = 0; i < n; ++i) Zb[(size_t)i * nc + (c - formed)] = R->Z[(size_t)i * stride + cc];
+            }
+            Phase t{T.beta};
+            if (int rc = pg_gp_beta_cols(ctx, in.G, p, n, in.ld, Zb.data(), nc, bf.get() + formed * (size_t)p, 1)) return rc;
+            formed = c1;
+        }
+        return PG_OK;
+    };
+    for (int rep = 0; rep < n_reps; ++rep) {
+        const RepSolve *R;
+        { Phase t{T.solve}; R = solver.wait(rep); }
+        if (!R) return pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: pinv failed");
+        const double *bfr = batched ? bf.get() + (size_t)rep * C * (size_t)p : bf.get(); // this repetition's C columns
+        if (batched) {
+            if (int rc = form_upto((size_t)(rep + 1) * C)) return rc;
+        } else {
+            Phase t{T.beta};
+            if (int rc = pg_gp_beta_cols(ctx, in.G, p, n, in.ld, R->Z.data(), C, bf.get(), 1)) return rc; // :526 for every fold at once, column-major
+        }
+        for (int a = 0; a < in.A(); ++a) {
+            { Phase t{T.params}; if (int rc = pipe.set_masses(*R, bfr, in.alpha_at(a))) return rc; }
+            Phase t{T.predict};
+            for (int j = 0; j < k; ++j)
+                if (int rc = pipe.launch(*R, bfr, rep, a, j)) return rc;
+        }
+    }
+    if (int rc = pipe.drain()) return rc;
+    if (batched) { // whatever is left of the columns (the all-rows fit at least, unless it rode in a repetition's pass)
+        if (int rc = form_upto(ncols_all)) return rc;
+        if (hipMemcpyAsync(beta_dev, solver.wait(n_reps)->b0c.data(), sizeof(double) * k, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed");
+        hipLaunchKernelGGL(k_gp_cols_to_rows, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, bf.get() + (size_t)n_reps * C * (size_t)p, p, k, beta_dev + k);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) // (the intercepts are read by the copy)
+            return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: the all-rows fit failed");
+        *have_fit = true;
+    }
+    Phase t{T.release}; // (here, not at scope end: the report times them)
+    bf.reset(); fm_dev.reset(); colof_dev.reset();
+    return PG_OK;
+}
+
+// ---- the per-fold cross-validation: per (repetition, fold) the fit of pg_gp_ols_dev, then per (alpha, trait) the masses, the
+// contracted coefficients of all lambdas and one prediction pass.  What a tall design takes (n >= p + 1: gp::ols then uses
+// pinv(X'X), which pg_gp_ols_dev follows and the fused passes do not), and more fold x trait columns than one pass carries.
+int cv_per_fold(pg_ctx *ctx, const GpCall &in, const std::vector<double> &xxt, RidgeWork &W, std::vector<double> &perf, double *beta_dev) {
+    const int64_t p = in.p;
+    const int n = in.n, k = in.k;
+    RepSolve R; // (its pools only)
+    std::vector<double> b0(k), yh((size_t)n * GP_LMAX);
+    for (int rep = 0; rep < in.n_reps; ++rep) {
+        R.split(in, rep);
+        for (int fold = 0; fold < in.n_folds; ++fold) {
+            if (!R.live(fold)) continue;
+            const std::vector<int64_t> &itr = R.tr[fold], &iva = R.va[fold];
+            if (int rc = pg_gp_ols_dev(ctx, in.G, p, n, in.ld, in.Y, k, itr.data(), (int)itr.size(), xxt.data(), beta_dev)) return rc; // :526
+            if (hipMemcpyAsync(b0.data(), beta_dev, sizeof(double) * k, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+                return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: D2H failed");
+            for (int a = 0; a < in.A(); ++a)
+                for (int j = 0; j < k; ++j) {
+                    PathParams P;
+                    const Proxy X{in.proxy, k, j};
+                    if (int rc = ridge_path_params(ctx, beta_dev, p, k, j, in.alpha_at(a), in.path, W, P, 1, X)) return rc;
+                    hipLaunchKernelGGL(k_gp_blambda, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, beta_dev, p, k, j, P, X, W.B);
+                    hipLaunchKernelGGL(k_gp_predict, dim3(W.S.nblk, (n + 255) / 256), dim3(256), 0, ctx->stream, in.G, W.B, p, n, in.ld, W.S.lpb, W.part);
+                    hipLaunchKernelGGL(k_gp_predict_reduce, dim3((n * GP_LMAX + 63) / 64), dim3(512), 0, ctx->stream, W.part, W.S.nblk, n, W.yhat);
+                    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(yh.data(), W.yhat, sizeof(double) * n * GP_LMAX, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                        hipStreamSynchronize(ctx->stream) != hipSuccess)
+                        return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
+                    score(in, perf, yh, rep, fold, a, j, b0[j], iva);
+                }
+        }
+    }
+    return PG_OK;
+}
+
+// Per trait the mode over repetitions of the per-repetition arg-min over the (alpha, lambda) grid (:573-627): alpha and
+// lambda are counted separately, each against the path values.  Then expand_and_contract of the all-rows fit in beta_dev
+// at the chosen pair (:653-662).
+int select_and_apply(pg_ctx *ctx, const GpCall &in, const std::vector<double> &perf, RidgeWork &W, double *beta_dev, double *alphas_out,
+                     double *lambdas_out) {
+    const int L = in.L(), A = in.A(), k = in.k;
+    for (int j = 0; j < k; ++j) {
+        std::vector<int> acount(L, 0), lcount(L, 0);
+        for (int rep = 0; rep < in.n_reps; ++rep) {
+            std::vector<double> mean((size_t)A * L);
+            for (int a = 0; a < A; ++a)
+                for (int li = 0; li < L; ++li) {
+                    double sum = 0.0;
+                    for (int fold = 0; fold < in.n_folds; ++fold) sum += perf[in.perf_at(rep, fold, a, li, j)];
+                    mean[(size_t)a * L + li] = sum / (double)in.n_folds;
+                }
+            double mnv = mean[0];
+            for (double x : mean) if (x < mnv) mnv = x;
+            for (size_t q = 0; q < mean.size(); ++q)
+                if (mean[q] == mnv) {
+                    const double aval = in.alpha_at((int)(q / L)), lval = in.path[q % L];
+                    for (int c = 0; c < L; ++c) { acount[c] += (aval == in.path[c]); lcount[c] += (lval == in.path[c]); }
+                    break;
+                }
+        }
+        const int abest = (int)(std::max_element(acount.begin(), acount.end()) - acount.begin()); // (the first of equal counts)
+        const int lbest = (int)(std::max_element(lcount.begin(), lcount.end()) - lcount.begin());
+        // a single alpha off the path grid counts nowhere in the reference (:605-608), which then reports and applies
+        // path[0]; such an alpha never reaches it from its own callers (0, 1, grid), here it is kept as given
+        const double afinal = in.alpha >= 0.0 ? in.alpha : in.path[abest];
+        if (alphas_out) alphas_out[j] = afinal;
+        lambdas_out[j] = in.path[lbest];
+        PathParams P;
+        const Proxy X{in.proxy, k, j};
+        if (int rc = ridge_path_params(ctx, beta_dev, in.p, k, j, afinal, in.path, W, P, 1, X)) return rc;
+        hipLaunchKernelGGL(k_gp_apply, dim3((unsigned)((in.p + 255) / 256)), dim3(256), 0, ctx->stream, beta_dev, in.p, k, j, P, X, lbest);
+        if (hipGetLastError() != hipSuccess) return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: apply failed");
     }
     return PG_OK;
 }
 
 // The lambda path with k-fold cross-validation (:461-669) behind penalise_lasso_like / _ridge_like (alpha = 1 / 0, one
 // path), penalise_glmnet (alpha < 0: the 2-D grid alpha x lambda over the same path values, :479-498) and the
-// *_with_iterative_proxy_norms models (proxy != nullptr, :540-553, :655-657).
-int penalised_path(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y, int k,
-                   const int64_t *row_idx, int n_rows, const int32_t *fold_of, int n_reps, int n_folds, double alpha,
-                   const double *proxy_dev, double lambda_step, double *beta_dev, double *alphas_out, double *lambdas_out,
+// *_with_iterative_proxy_norms models (in.proxy != nullptr, :540-553, :655-657).
+int penalised_path(pg_ctx *ctx, GpCall in, double lambda_step, double *beta_dev, double *alphas_out, double *lambdas_out,
                    double *perf_out, const double *xxt_host_or_null) {
     const int maxu = (int)std::llround(1.0 / lambda_step);
-    const int L = maxu + 1;
-    PG_CHECK(ctx, L <= GP_LMAX, "gp_ridge: at most %d lambdas on the path", GP_LMAX);
-    std::vector<double> path(L);
-    for (int i = 0; i < L; ++i) path[i] = (double)i / (double)maxu; // :470-476
-    const int A = alpha >= 0.0 ? 1 : L;                              // :479-498
-    auto alpha_at = [&](int a) { return alpha >= 0.0 ? alpha : path[a]; };
+    PG_CHECK(ctx, maxu + 1 <= GP_LMAX, "gp_ridge: at most %d lambdas on the path", GP_LMAX);
+    in.path.resize(maxu + 1);
+    for (int i = 0; i <= maxu; ++i) in.path[i] = (double)i / (double)maxu; // :470-476
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    const auto t_entry = std::chrono::steady_clock::now(); // (POOLGEN_GP_TIMING: where the wall goes outside the repetitions)
-
+    PhaseTimes T;
     // the full-data X X^T once; every training subset uses a principal sub-block
-    std::vector<double> xxt((size_t)n * n);
-    if (xxt_host_or_null) std::memcpy(xxt.data(), xxt_host_or_null, sizeof(double) * (size_t)n * n);
-    else {
-        int rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "gp_ridge");
-        if (!rc) rc = pg_gp_xxt_dev(ctx, G_dev, p, n, ld, ctx->S_dev);
-        if (rc) return rc;
-        PG_HIP(ctx, hipMemcpyAsync(xxt.data(), ctx->S_dev, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream));
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    // scratch
-    const int nblk = std::max(1, std::min<int>(ctx->cus * 4, (int)((p + 255) / 256)));
-    const int64_t lpb = (p + nblk - 1) / nblk;
-    const int nblk2 = (int)((p + lpb - 1) / lpb);
+    std::vector<double> xxt;
+    if (int rc = pg_gp_xxt_host(ctx, in.G, in.p, in.n, in.ld, xxt_host_or_null, "gp_ridge", xxt)) return rc;
     RidgeWork W;
-    // The host ends of the asynchronous copies below come BEFORE the device buffers: releasing those waits for the device, so
-    // on an early return no copy is still in flight when these go.
-    // error indices (rep, fold, alpha, lambda, trait) as the reference's `performances` (:509)
-    std::vector<double> perf((size_t)n_reps * n_folds * A * L * k, NAN), b0(k), yh((size_t)n * GP_LMAX);
-    std::vector<double> yh_in[2] = {std::vector<double>((size_t)n * GP_LMAX), std::vector<double>((size_t)n * GP_LMAX)};
-    std::vector<int32_t> colof_h[2];
-    std::vector<FoldMasses> fm_h[2];
-    const size_t part_doubles = std::max<size_t>((size_t)(n_folds * k + 1) * 1024 * 4 * GP_LMAX + (size_t)n_folds * k * 4 * GP_LMAX,
-                                                 (size_t)nblk2 * n * GP_LMAX * 4); // (x 4: the prediction pass' locus groups at n <= 256)
-    DevBuf<double> raw;
-    if (int rc = raw.alloc(ctx, sizeof(double) * (part_doubles + (size_t)p * GP_LMAX + (size_t)n * GP_LMAX), "gp_ridge")) return rc;
-    W.part = raw.get();
-    W.B = W.part + part_doubles;
-    W.yhat = W.B + (size_t)p * GP_LMAX;
-
-    std::vector<int64_t> itr, iva;
-    for (int i = 0; i < n_reps * n_rows; ++i)
-        if (fold_of[i] < 0 || fold_of[i] > n_folds /* == n_folds: the left-over group of k_split (:444-448), never validated */) {
-            ctx->err = "gp_ridge: fold id out of range"; return PG_ERR_INVALID;
-        }
-    // error_index (:359-426) of trait j on the validation pools `iva`, for every lambda, from yhat (n x GP_LMAX)
-    auto score = [&](int rep, int fold, int a, int j, double b0j, const std::vector<int64_t> &iva_) {
-        const int nv = (int)iva_.size();
-        std::vector<double> yt(nv), yp(nv);
-        double mn = 0, mx = 0;
-        for (int i = 0; i < nv; ++i) {
-            yt[i] = Y[(size_t)iva_[i] * k + j];
-            if (i == 0 || yt[i] < mn) mn = yt[i];
-            if (i == 0 || yt[i] > mx) mx = yt[i];
-        }
-        for (int li = 0; li < L; ++li) {
-            for (int i = 0; i < nv; ++i) yp[i] = b0j + yh[(size_t)iva_[i] * GP_LMAX + li];
-            const double cor = host_pearson_r(yt, yp);
-            double mae = 0, mse = 0;
-            for (int i = 0; i < nv; ++i) { const double d = yt[i] - yp[i]; mae += std::fabs(d); mse += d * d; }
-            mae /= (mx - mn);
-            mse /= ((mx - mn) * (mx - mn));
-            const double rmse = std::sqrt(mse) / (mx - mn);
-            perf[((((size_t)rep * n_folds + fold) * A + a) * L + li) * k + j] = ((1.0 - std::fabs(cor)) + mae + mse + rmse) / 4.0;
-        }
-    };
-    // Every pool is validated by exactly ONE fold of a repetition, so all folds share two passes over G: one that
-    // forms the slopes of every fold's training fit (n_folds * k coefficient columns), one (per alpha) that predicts
-    // every pool with the coefficients of the fold that holds it out.  (Fallback below: one pair of passes per fold.)
-    // The fused passes take every fit from pinv(X X^T) (pg_gp_subset_solve): the wide branch of gp/ols.rs:47.  A tall design (n >= p + 1:
-    // at most n - 1 loci) takes the other formula there, so it goes one fold at a time through pg_gp_ols_dev, which follows that rule.
-    const int C = n_folds * k;
-    const bool fused = C <= PG_MAX_SWEEP_COLS && (int64_t)n < p + 1 && !std::getenv("POOLGEN_RIDGE_PER_FOLD");
-    DevBuf<double> bf_own;      // C x p (column-major) slopes of the folds' fits
-    DevBuf<FoldMasses> fm_own;
-    DevBuf<int32_t> colof_own;
-    // The slopes of ALL repetitions' folds (and of the all-rows fit) are columns G Z of the same matrix: formed CP at a time,
-    // whatever repetition they belong to, they take ceil((n_reps C + k) / CP) passes over G instead of n_reps + 1 (config 4:
-    // 101 columns, 7 passes instead of 11).  Needs the n_reps C + k columns resident (config 4: 4 GB of the 288); otherwise,
-    // or with POOLGEN_RIDGE_PER_REP=1, one pass per repetition as before.
-    constexpr int CP = 16;      // columns per coefficient pass: what the sweep kernel's products mode carries at 500 pools
-    const size_t ncols_all = (size_t)n_reps * C + k;
-    bool batched = fused && n_reps > 1 && !std::getenv("POOLGEN_RIDGE_PER_REP");
-    if (batched) {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess || sizeof(double) * (size_t)p * ncols_all > fr / 2) batched = false;
-    }
-    const auto t_alloc0 = std::chrono::steady_clock::now();
-    if (fused) {
-        int rc = bf_own.alloc(ctx, sizeof(double) * (size_t)p * (batched ? ncols_all : (size_t)C), "gp_ridge");
-        if (!rc) rc = fm_own.alloc(ctx, sizeof(FoldMasses) * C, "gp_ridge");
-        if (!rc) rc = colof_own.alloc(ctx, sizeof(int32_t) * n, "gp_ridge");
-        if (rc) return rc;
-    }
-    double *const bf = bf_own.get();
-    FoldMasses *const fm_dev = fm_own.get();
-    int32_t *const colof_dev = colof_own.get();
-    const double t_alloc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc0).count();
-    const double t_before = std::chrono::duration<double>(t_alloc0 - t_entry).count(); // X X^T, its copy to the host, the work buffers
-    // POOLGEN_GP_TIMING=1: host-side phase times of the repetitions on stderr
-    const bool timing = std::getenv("POOLGEN_GP_TIMING") != nullptr;
-    double t_solve = 0, t_beta = 0, t_params = 0, t_predict = 0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    // The folds' host solves (pinv(X X^T) y on every training block) need nothing from the GPU but X X^T: a background
-    // thread works through the repetitions ahead of the device passes (one worker thread per fold inside).
-    struct RepSolve {
-        std::vector<std::vector<int64_t>> tr, va;
-        std::vector<double> Z, b0c;
-        bool bad = false;
-    };
-    std::vector<RepSolve> solves(fused ? n_reps : 0);
-    std::vector<std::promise<void>> ready(fused ? n_reps + 1 : 0); // (the last one: the all-rows fit)
-    std::vector<std::shared_future<void>> readyf;
-    for (auto &pr : ready) readyf.push_back(pr.get_future().share());
-    std::vector<double> Zall, b0all(k, 0.0); // the all-rows fit: pinv(X X^T) y scattered over the pools, its intercepts
-    bool all_bad = false;
-    std::thread solver;
-    if (fused)
-        solver = std::thread([&] {
-            for (int rep = 0; rep < n_reps; ++rep) {
-                RepSolve &R = solves[rep];
-                R.tr.assign(n_folds, {}); R.va.assign(n_folds, {});
-                for (int i = 0; i < n_rows; ++i) {
-                    const int f = fold_of[(size_t)rep * n_rows + i];
-                    for (int g = 0; g < n_folds; ++g) (g == f ? R.va[g] : R.tr[g]).push_back(row_idx[i]);
-                }
-                R.Z.assign((size_t)n * C, 0.0); R.b0c.assign(C, 0.0);
-                std::vector<int> badf(n_folds, 0);
-                std::vector<std::thread> th;
-                for (int f = 0; f < n_folds; ++f) {
-                    if (R.va[f].empty() || R.tr[f].empty()) continue; // an empty fold leaves NaN, as an empty slice would
-                    th.emplace_back([&, f] {
-                        const int r = (int)R.tr[f].size();
-                        std::vector<double> V((size_t)r * k);
-                        if (pg_gp_subset_solve(xxt.data(), n, Y, k, R.tr[f].data(), r, V.data()) != 0) { badf[f] = 1; return; }
-                        for (int a2 = 0; a2 < r; ++a2)
-                            for (int j = 0; j < k; ++j) {
-                                R.Z[(size_t)R.tr[f][a2] * C + f * k + j] = V[(size_t)a2 * k + j];
-                                R.b0c[f * k + j] += V[(size_t)a2 * k + j];
-                            }
-                    });
-                }
-                for (auto &x : th) x.join();
-                for (int f = 0; f < n_folds; ++f) R.bad = R.bad || badf[f];
-                ready[rep].set_value();
-            }
-            if (batched) { // the all-rows fit rides in the last batched pass (gp/ols.rs:47-72 on `row_idx`)
-                std::vector<double> V((size_t)n_rows * k);
-                Zall.assign((size_t)n * k, 0.0);
-                if (pg_gp_subset_solve(xxt.data(), n, Y, k, row_idx, n_rows, V.data()) != 0) all_bad = true;
-                else
-                    for (int a2 = 0; a2 < n_rows; ++a2)
-                        for (int j = 0; j < k; ++j) {
-                            Zall[(size_t)row_idx[a2] * k + j] = V[(size_t)a2 * k + j];
-                            b0all[j] += V[(size_t)a2 * k + j]; // intercept column of X is all ones
-                        }
-            }
-            ready[n_reps].set_value();
-        });
-    struct Joiner { // every exit path waits for the solver before its captures go away
-        std::thread &t;
-        ~Joiner() { if (t.joinable()) t.join(); }
-    } joiner{solver};
-    // One prediction pass is kept OUT while the host goes on (the next repetition's coefficient passes, the next masses, the
-    // scores of the pass before): its predictions land in yh_in[buf], the small host arrays its copies read stay alive in turn.
-    struct Pending { bool on; int rep, a, j, buf; };
-    Pending pend{false, 0, 0, 0, 0};
-    int fm_turn = 0;
-    auto score_pending = [&](const Pending &q) {
-        const RepSolve &R = solves[q.rep];
-        yh.swap(yh_in[q.buf]); // (score reads yh)
-        for (int f = 0; f < n_folds; ++f)
-            if (!R.va[f].empty() && !R.tr[f].empty()) score(q.rep, f, q.a, q.j, R.b0c[f * k + q.j], R.va[f]);
-        yh.swap(yh_in[q.buf]);
-    };
-    size_t formed = 0; // batched: columns [0, formed) of the global numbering (repetition-major, then the all-rows fit) are in bf
-    auto form_cols = [&](size_t c0, size_t c1) -> int { // one pass over G for the columns [c0, c1)
-        const int nc = (int)(c1 - c0);
-        std::vector<double> Zb((size_t)n * nc, 0.0);
-        double t0 = now();
-        for (size_t c = c0; c < c1; ++c) {
-            const bool fin = c >= (size_t)n_reps * C;
-            const int rep = fin ? n_reps : (int)(c / C);
-            readyf[rep].wait();
-            if (fin ? all_bad : solves[rep].bad) return pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: pinv failed");
-            const double *src = fin ? Zall.data() : solves[rep].Z.data();
-            const int stride = fin ? k : C, cc = fin ? (int)(c - (size_t)n_reps * C) : (int)(c % C);
-            for (int i = 0; i < n; ++i) Zb[(size_t)i * nc + (c - c0)] = src[(size_t)i * stride + cc];
-        }
-        t_solve += now() - t0; t0 = now();
-        const int rc = pg_gp_beta_cols(ctx, G_dev, p, n, ld, Zb.data(), nc, bf + c0 * (size_t)p, 1);
-        t_beta += now() - t0;
-        return rc;
-    };
-    for (int rep = 0; rep < n_reps && fused; ++rep) {
-        double t0 = now();
-        readyf[rep].wait();
-        RepSolve &R = solves[rep];
-        if (R.bad) return pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: pinv failed");
-        const std::vector<std::vector<int64_t>> &tr = R.tr, &va = R.va;
-        const std::vector<double> &Z = R.Z;
-        t_solve += now() - t0; t0 = now();
-        int rc = PG_OK;
-        if (batched) {
-            while (formed < (size_t)(rep + 1) * C && rc == PG_OK) {
-                // the first pass takes repetition 0 alone when that costs no extra pass: it then waits for ONE repetition's host
-                // solves (5 ms at config 4) instead of two before the device has anything to do
-                const bool short_first = formed == 0 && (size_t)C < (size_t)CP &&
-                                         1 + (ncols_all - C + CP - 1) / CP == (ncols_all + CP - 1) / CP;
-                const size_t c1 = short_first ? (size_t)C : std::min(formed + (size_t)CP, ncols_all);
-                rc = form_cols(formed, c1);
-                formed = c1;
-            }
-        } else {
-            rc = pg_gp_beta_cols(ctx, G_dev, p, n, ld, Z.data(), C, bf, 1); // :526 for every fold at once, column-major
-            t_beta += now() - t0;
-        }
-        if (rc) return rc;
-        const double *bfr = batched ? bf + (size_t)rep * C * (size_t)p : bf; // this repetition's C columns
-        for (int a = 0; a < A; ++a) {
-            t0 = now();
-            // the redistribution masses of every (fold, trait) column.  Their launches queue up behind the prediction pass that is
-            // still out (`pend`), so the latency of this chain of small kernels and of its synchronisation is the device's busy time
-            std::vector<FoldMasses> &fm = fm_h[fm_turn ^= 1];
-            fm.assign(C, FoldMasses{});
-            PathParams P0;
-            std::memset(&P0, 0, sizeof P0);
-            std::vector<int> skip(C, 0);
-            for (int f = 0; f < n_folds; ++f)
-                for (int j = 0; j < k; ++j) skip[f * k + j] = va[f].empty() || tr[f].empty();
-            std::vector<PathParams> PP;
-            rc = ridge_path_params_cols(ctx, bfr, p, C, k, alpha_at(a), path, W, proxy_dev, skip, PP);
-            if (rc) return rc;
-            for (int c = 0; c < C; ++c) {
-                if (skip[c]) { std::memset(&fm[c], 0, sizeof(FoldMasses)); fm[c].nmax = 1.0; continue; }
-                fm[c].nmax = PP[c].nmax;
-                for (int i = 0; i < GP_LMAX; ++i) { fm[c].sub_scale[i] = PP[c].sub_scale[i]; fm[c].add_scale[i] = PP[c].add_scale[i]; }
-            }
-            P0 = PP[0]; // alpha, lambda[], L are the same for every column
-            P0.nmax = 0.0;
-            if (hipMemcpyAsync(fm_dev, fm.data(), sizeof(FoldMasses) * C, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed");
-            t_params += now() - t0; t0 = now();
-            for (int j = 0; j < k; ++j) {
-                // (the masses' synchronisation has seen the pass that was out: its predictions are on the host)
-                const Pending prev = pend;
-                const int turn = prev.on ? (prev.buf ^ 1) : 0;
-                std::vector<int32_t> &colof = colof_h[turn];
-                colof.assign(n, -1);
-                for (int f = 0; f < n_folds; ++f)
-                    if (!va[f].empty() && !tr[f].empty())
-                        for (int64_t pool : va[f]) colof[pool] = f * k + j;
-                if (prev.on && hipStreamSynchronize(ctx->stream) != hipSuccess) // (a no-op after the masses' own; the k > 1 traits of one alpha need it)
-                    return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
-                if (hipMemcpyAsync(colof_dev, colof.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                    return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed");
-                const int LP = (P0.L + 1) & ~1;
-                const size_t masses_b = sizeof(double) * n_folds * (2 * GP_LMAX + 1);
-                const int chunk = std::max(4, std::min(64, (int)((49152 - masses_b) / (sizeof(double) * n_folds * (LP + 2)))));
-                const int bthreads = n > 128 ? 512 : 256; // the coefficient stage is shared by all waves of a block
-                const int groups = n <= 256 ? bthreads / (((n + 63) / 64) * 64) : 1; // locus groups inside a block (n <= 256: 2 .. 4)
-                const dim3 grid(nblk2, groups > 1 ? 1 : (n + bthreads - 1) / bthreads);
-                const size_t lds = sizeof(double) * chunk * n_folds * (LP + 2) + masses_b;
-                const Proxy X{proxy_dev, k, j};
-                pg_prof_begin(ctx, PG_K_GP_PREDICT);
-#define PG_PREDICT_FOLDS2(LPV, OD)                                                                                         \
-        if (groups > 1)                                                                                                    \
-            hipLaunchKernelGGL((k_gp_predict_folds<LPV, true, OD>), grid, dim3(bthreads), lds, ctx->stream, G_dev, bfr, C, colof_dev, fm_dev, P0, X, \
-                               p, n, ld, lpb, chunk, W.part, groups);                                                      \
-        else                                                                                                               \
-            hipLaunchKernelGGL((k_gp_predict_folds<LPV, false, OD>), grid, dim3(bthreads), lds, ctx->stream, G_dev, bfr, C, colof_dev, fm_dev, P0, X, \
-                               p, n, ld, lpb, chunk, W.part, 1);
-#define PG_PREDICT_FOLDS(LPV)                                                                                              \
-    case LPV:                                                                                                              \
-        if (P0.L & 1) { PG_PREDICT_FOLDS2(LPV, true) } else { PG_PREDICT_FOLDS2(LPV, false) }                              \
-        break;
-                switch (LP) {
-                    PG_PREDICT_FOLDS(2) PG_PREDICT_FOLDS(4) PG_PREDICT_FOLDS(6) PG_PREDICT_FOLDS(8) PG_PREDICT_FOLDS(10)
-                    PG_PREDICT_FOLDS(12) PG_PREDICT_FOLDS(14) PG_PREDICT_FOLDS(16)
-                }
-#undef PG_PREDICT_FOLDS
-#undef PG_PREDICT_FOLDS2
-                pg_prof_end(ctx);
-                hipLaunchKernelGGL(k_gp_predict_reduce, dim3((n * GP_LMAX + 63) / 64), dim3(512), 0, ctx->stream, W.part, nblk2 * groups, n, W.yhat);
-                if (hipGetLastError() != hipSuccess ||
-                    hipMemcpyAsync(yh_in[turn].data(), W.yhat, sizeof(double) * n * GP_LMAX, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-                    return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
-                pend = Pending{true, rep, a, j, turn};
-                // ... and while this pass runs, the host scores the one before it
-                if (prev.on) score_pending(prev);
-            }
-            t_predict += now() - t0;
-        }
-    }
-    if (pend.on) { // the last pass out
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
-        score_pending(pend);
-        pend.on = false;
-    }
-    if (batched) { // whatever is left of the columns (the all-rows fit at least, unless it rode in a repetition's pass)
-        int rc = PG_OK;
-        while (formed < ncols_all && rc == PG_OK) {
-            const size_t c1 = std::min(formed + (size_t)CP, ncols_all);
-            rc = form_cols(formed, c1);
-            formed = c1;
-        }
-        if (rc) return rc;
-        if (hipMemcpyAsync(beta_dev, b0all.data(), sizeof(double) * k, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: H2D failed");
-        hipLaunchKernelGGL(k_gp_cols_to_rows, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, bf + (size_t)n_reps * C * (size_t)p, p, k, beta_dev + k);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) // (b0all is read by the copy)
-            return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: the all-rows fit failed");
-    }
-    const double t_free0 = now();
-    bf_own.reset(); fm_own.reset(); colof_own.reset(); // (here, not at scope end: the report below times them)
-    if (timing)
-        std::fprintf(stderr, "gp path: before the repetitions %.1f ms; fold solves %.1f ms, coefficient passes %.1f ms, masses %.1f ms, prediction + scores %.1f ms; the columns' memory: allocation %.1f ms, release %.1f ms; since entry %.1f ms\n",
-                     1e3 * t_before, 1e3 * t_solve, 1e3 * t_beta, 1e3 * t_params, 1e3 * t_predict, 1e3 * t_alloc, 1e3 * (now() - t_free0),
-                     1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count());
-    for (int rep = 0; rep < n_reps && !fused; ++rep)
-        for (int fold = 0; fold < n_folds; ++fold) {
-            itr.clear(); iva.clear();
-            for (int i = 0; i < n_rows; ++i) {
-                const int f = fold_of[(size_t)rep * n_rows + i];
-                (f == fold ? iva : itr).push_back(row_idx[i]);
-            }
-            if (iva.empty() || itr.empty()) continue; // an empty fold leaves NaN, as an empty slice would
-            int rc = pg_gp_ols_dev(ctx, G_dev, p, n, ld, Y, k, itr.data(), (int)itr.size(), xxt.data(), beta_dev); // :526
-            if (rc) return rc;
-            if (hipMemcpyAsync(b0.data(), beta_dev, sizeof(double) * k, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-                return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: D2H failed");
-            for (int a = 0; a < A; ++a)
-                for (int j = 0; j < k; ++j) {
-                    PathParams P;
-                    const Proxy X{proxy_dev, k, j};
-                    rc = ridge_path_params(ctx, beta_dev, p, k, j, alpha_at(a), path, W, P, 1, X);
-                    if (rc) return rc;
-                    hipLaunchKernelGGL(k_gp_blambda, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, beta_dev, p, k, j, P, X, W.B);
-                    hipLaunchKernelGGL(k_gp_predict, dim3(nblk2, (n + 255) / 256), dim3(256), 0, ctx->stream, G_dev, W.B, p, n, ld, lpb, W.part);
-                    hipLaunchKernelGGL(k_gp_predict_reduce, dim3((n * GP_LMAX + 63) / 64), dim3(512), 0, ctx->stream, W.part, nblk2, n, W.yhat);
-                    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(yh.data(), W.yhat, sizeof(double) * n * GP_LMAX, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                        hipStreamSynchronize(ctx->stream) != hipSuccess)
-                        return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: prediction pass failed");
-                    score(rep, fold, a, j, b0[j], iva);
-                }
-        }
-    // all-rows fit; per trait the mode over repetitions of the per-repetition arg-min over the (alpha, lambda) grid
-    // (:573-627): alpha and lambda are counted separately, each against the path values
-    int rc = batched ? PG_OK : pg_gp_ols_dev(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, xxt.data(), beta_dev); // (batched: already in beta_dev)
-    if (rc) return rc;
-    for (int j = 0; j < k; ++j) {
-        std::vector<int> acount(L, 0), lcount(L, 0);
-        for (int rep = 0; rep < n_reps; ++rep) {
-            std::vector<double> mean((size_t)A * L);
-            for (int a = 0; a < A; ++a)
-                for (int li = 0; li < L; ++li) {
-                    double sum = 0.0;
-                    for (int fold = 0; fold < n_folds; ++fold) sum += perf[((((size_t)rep * n_folds + fold) * A + a) * L + li) * k + j];
-                    mean[(size_t)a * L + li] = sum / (double)n_folds;
-                }
-            double mnv = mean[0];
-            for (double x : mean) if (x < mnv) mnv = x;
-            for (size_t q = 0; q < mean.size(); ++q)
-                if (mean[q] == mnv) {
-                    const double aval = alpha_at((int)(q / L)), lval = path[q % L];
-                    for (int c = 0; c < L; ++c) { acount[c] += (aval == path[c]); lcount[c] += (lval == path[c]); }
-                    break;
-                }
-        }
-        int amax = 0, lmax = 0, abest = 0, lbest = 0;
-        for (int c = 0; c < L; ++c) { amax = std::max(amax, acount[c]); lmax = std::max(lmax, lcount[c]); }
-        for (int c = 0; c < L; ++c) if (acount[c] == amax) { abest = c; break; }
-        for (int c = 0; c < L; ++c) if (lcount[c] == lmax) { lbest = c; break; }
-        // a single alpha off the path grid counts nowhere in the reference (:605-608), which then reports and applies
-        // path[0]; such an alpha never reaches it from its own callers (0, 1, grid), here it is kept as given
-        const double afinal = alpha >= 0.0 ? alpha : path[abest];
-        if (alphas_out) alphas_out[j] = afinal;
-        lambdas_out[j] = path[lbest];
-        PathParams P;
-        const Proxy X{proxy_dev, k, j};
-        rc = ridge_path_params(ctx, beta_dev, p, k, j, afinal, path, W, P, 1, X);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_gp_apply, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, beta_dev, p, k, j, P, X, lbest);
-        if (hipGetLastError() != hipSuccess) return pg_fail(ctx, PG_ERR_HIP, "gp_ridge: apply failed");
-    }
+    if (int rc = W.alloc(ctx, in)) return rc;
+    for (int i = 0; i < in.n_reps * in.n_rows; ++i)
+        if (in.fold_of[i] < 0 || in.fold_of[i] > in.n_folds /* == n_folds: the left-over group of k_split (:444-448), never validated */)
+            return pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: fold id out of range");
+    std::vector<double> perf((size_t)in.n_reps * in.n_folds * in.A() * in.L() * in.k, NAN);
+    const bool fused = in.C() <= PG_MAX_SWEEP_COLS && (int64_t)in.n < in.p + 1 && !std::getenv("POOLGEN_RIDGE_PER_FOLD");
+    T.before = PhaseTimes::since(T.entry); // X X^T, its copy to the host, the work buffers
+    bool have_fit = false; // the all-rows fit is in beta_dev
+    if (int rc = fused ? cv_fused(ctx, in, xxt, W, T, perf, beta_dev, &have_fit) : cv_per_fold(ctx, in, xxt, W, perf, beta_dev)) return rc;
+    T.report_phases();
+    if (!have_fit)
+        if (int rc = pg_gp_ols_dev(ctx, in.G, in.p, in.n, in.ld, in.Y, in.k, in.rows, in.n_rows, xxt.data(), beta_dev)) return rc;
+    if (int rc = select_and_apply(ctx, in, perf, W, beta_dev, alphas_out, lambdas_out)) return rc;
     if (perf_out) std::memcpy(perf_out, perf.data(), sizeof(double) * perf.size());
     (void)hipStreamSynchronize(ctx->stream);
-    raw.reset(); // (inside the whole-call time)
-    if (std::getenv("POOLGEN_GP_TIMING"))
-        std::fprintf(stderr, "gp path: whole call %.1f ms\n", 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count());
+    W.raw.reset(); // (inside the whole-call time)
+    T.report_call();
     return PG_OK;
 }
 
 } // namespace
+
+// (pg_common.h) the caller's copy when there is one, else the kinship pass into the context's n x n buffer and a copy from there
+int pg_gp_xxt_host(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *given_or_null, const char *who,
+                   std::vector<double> &xxt) {
+    xxt.resize((size_t)n * n);
+    if (given_or_null) {
+        std::memcpy(xxt.data(), given_or_null, sizeof(double) * (size_t)n * n);
+        return PG_OK;
+    }
+    int rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, who);
+    if (!rc) rc = pg_gp_xxt_dev(ctx, G_dev, p, n, ld, ctx->S_dev);
+    if (rc) return rc;
+    PG_HIP(ctx, hipMemcpyAsync(xxt.data(), ctx->S_dev, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
+
+extern "C" int pg_gp_ols_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y,
+                             int k, const int64_t *row_idx, int n_rows, const double *XXt_host_or_null,
+                             double *beta_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    PG_CHECK(ctx, G_dev && Y && row_idx && beta_dev && p > 0 && n >= 1 && k >= 1 && n_rows >= 1 && n_rows <= n,
+             "gp_ols: bad arguments");
+    PG_CHECK(ctx, ld >= n && (ld % 2) == 0, "gp_ols: ld must be even and >= n");
+    if (k > 8) return pg_fail(ctx, PG_ERR_UNSUPPORTED, "gp_ols: at most 8 traits per call");
+    for (int a = 0; a < n_rows; ++a) PG_CHECK(ctx, row_idx[a] >= 0 && row_idx[a] < n, "gp_ols: row index out of range");
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    if ((int64_t)n >= p + 1) {
+        // The tall branch (gp/ols.rs:72-99, taken when x.nrows() >= x.ncols(): at most n - 1 loci, i.e. the reference's own 5 x 3
+        // test, never a pool-seq matrix): b = pinv(X'X over the training rows) X' y.  (1 + p)^2 <= n^2 numbers: the host's,
+        // not a GPU problem.  pinv as in the wide branch (helpers.rs:463-482).
+        const int P = (int)p + 1;
+        std::vector<double> Gh((size_t)p * ld);
+        PG_HIP(ctx, hipMemcpyAsync(Gh.data(), G_dev, sizeof(double) * (size_t)p * ld, hipMemcpyDeviceToHost, ctx->stream));
+        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        auto X = [&](int64_t i, int c) { return c == 0 ? 1.0 : Gh[(size_t)(c - 1) * ld + i]; };
+        std::vector<double> xtx((size_t)P * P), pinv((size_t)P * P), T((size_t)P * n_rows), b((size_t)P * k);
+        for (int a = 0; a < P; ++a)
+            for (int c = 0; c < P; ++c) {
+                double x = 0.0;
+                for (int i = 0; i < n_rows; ++i) x += X(row_idx[i], a) * X(row_idx[i], c);
+                xtx[(size_t)a * P + c] = x;
+            }
+        if (pg_pinv_sym(xtx.data(), P, pinv.data()) != 0) return pg_fail(ctx, PG_ERR_INVALID, "gp_ols: pinv failed");
+        for (int a = 0; a < P; ++a) // (pinv X') y, in the reference's order of products
+            for (int i = 0; i < n_rows; ++i) {
+                double x = 0.0;
+                for (int c = 0; c < P; ++c) x += pinv[(size_t)a * P + c] * X(row_idx[i], c);
+                T[(size_t)a * n_rows + i] = x;
+            }
+        for (int a = 0; a < P; ++a)
+            for (int j = 0; j < k; ++j) {
+                double x = 0.0;
+                for (int i = 0; i < n_rows; ++i) x += T[(size_t)a * n_rows + i] * Y[(size_t)row_idx[i] * k + j];
+                b[(size_t)a * k + j] = x;
+            }
+        PG_HIP(ctx, hipMemcpyAsync(beta_dev, b.data(), sizeof(double) * (size_t)P * k, hipMemcpyHostToDevice, ctx->stream));
+        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // b is stack-owned
+        return PG_OK;
+    }
+    // the wide branch (gp/ols.rs:47-72): b = X^T pinv(X X^T) y.  Every training subset's X X^T is a principal sub-block of the full-data one
+    std::vector<double> xxt;
+    if (int rc = pg_gp_xxt_host(ctx, G_dev, p, n, ld, XXt_host_or_null, "gp_ols", xxt)) return rc;
+    std::vector<double> Z((size_t)n * k, 0.0), b0(k, 0.0);
+    if (solve_scatter(xxt.data(), n, Y, k, row_idx, n_rows, Z.data(), k, 0, b0.data()) != 0) return pg_fail(ctx, PG_ERR_INVALID, "gp_ols: pinv failed");
+    PG_HIP(ctx, hipMemcpyAsync(beta_dev, b0.data(), sizeof(double) * k, hipMemcpyHostToDevice, ctx->stream));
+    return pg_gp_beta_cols(ctx, G_dev, p, n, ld, Z.data(), k, beta_dev + k); // rows 1..p: one streaming pass over G; synchronises (b0 is stack-owned)
+}
 
 extern "C" int pg_gp_ridge_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y,
                                int k, const int64_t *row_idx, int n_rows, const int32_t *fold_of, int n_reps,
@@ -997,7 +1136,7 @@ extern "C" int pg_gp_ridge_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int 
     PG_CHECK(ctx, p > 0 && n >= 3 && k >= 1 && k <= 8 && n_rows >= 3 && n_rows <= n && n_reps >= 1 && n_folds >= 2,
              "gp_ridge: bad shape");
     PG_CHECK(ctx, alpha >= 0.0 && alpha <= 1.0 && lambda_step > 0.0 && lambda_step <= 1.0, "gp_ridge: bad alpha / lambda step");
-    return penalised_path(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, fold_of, n_reps, n_folds, alpha, nullptr, lambda_step,
+    return penalised_path(ctx, GpCall{G_dev, p, n, ld, Y, k, row_idx, n_rows, fold_of, n_reps, n_folds, alpha, nullptr, {}}, lambda_step,
                           beta_dev, nullptr, lambdas_out, perf_out, nullptr);
 }
 
@@ -1017,12 +1156,9 @@ extern "C" int pg_gp_penalised_dev(pg_ctx *ctx, const double *G_dev, int64_t p, 
         if (!rc) rc = pg_gp_proxy_dev(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, XXt_host_or_null, proxy.get());
         if (rc) return rc;
     }
-    return penalised_path(ctx, G_dev, p, n, ld, Y, k, row_idx, n_rows, fold_of, n_reps, n_folds, alpha, proxy.get(), lambda_step,
+    return penalised_path(ctx, GpCall{G_dev, p, n, ld, Y, k, row_idx, n_rows, fold_of, n_reps, n_folds, alpha, proxy.get(), {}}, lambda_step,
                           beta_dev, alphas_out, lambdas_out, perf_out, XXt_host_or_null);
 }
-
-namespace {
-} // namespace
 
 // yhat = X beta for every pool (the multiply_views_xx of gp/cv.rs:160-168, all rows at once)
 extern "C" int pg_gp_predict_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *beta_dev,
@@ -1031,16 +1167,14 @@ extern "C" int pg_gp_predict_dev(pg_ctx *ctx, const double *G_dev, int64_t p, in
     PG_CHECK(ctx, G_dev && beta_dev && yhat && p > 0 && n >= 1 && k >= 1 && k <= 8, "gp_predict: bad arguments");
     PG_CHECK(ctx, ld >= n, "gp_predict: ld must be >= n");
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    const int nblk = std::max(1, std::min<int>(ctx->cus * 4, (int)((p + 255) / 256)));
-    const int64_t lpb = (p + nblk - 1) / nblk;
-    const int nblk2 = (int)((p + lpb - 1) / lpb);
-    const size_t need = sizeof(double) * ((size_t)nblk2 * n * 8 + (size_t)n * 8);
+    const Slabs S = predict_slabs(ctx, p);
+    const size_t need = sizeof(double) * ((size_t)S.nblk * n * 8 + (size_t)n * 8);
     int rc = pg_ws_reserve(ctx, need);
     if (rc) return rc;
     double *part = static_cast<double *>(ctx->ws.get());
-    double *out = part + (size_t)nblk2 * n * 8;
-    hipLaunchKernelGGL(k_gp_predict_beta, dim3(nblk2, (n + 255) / 256), dim3(256), 0, ctx->stream, G_dev, beta_dev, k, p, n, ld, lpb, part);
-    hipLaunchKernelGGL(k_gp_predict_beta_reduce, dim3((n * 8 + 255) / 256), dim3(256), 0, ctx->stream, part, nblk2, n, out);
+    double *out = part + (size_t)S.nblk * n * 8;
+    hipLaunchKernelGGL(k_gp_predict_beta, dim3(S.nblk, (n + 255) / 256), dim3(256), 0, ctx->stream, G_dev, beta_dev, k, p, n, ld, S.lpb, part);
+    hipLaunchKernelGGL(k_gp_predict_beta_reduce, dim3((n * 8 + 255) / 256), dim3(256), 0, ctx->stream, part, S.nblk, n, out);
     PG_HIP(ctx, hipGetLastError());
     std::vector<double> h((size_t)n * 8), b0(k);
     PG_HIP(ctx, hipMemcpyAsync(h.data(), out, sizeof(double) * n * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,4 +1,4 @@
-// pg_sweep.hip -- the per-locus OLS sweep of ols_iter_with_kinship and its host-side set-up.
+// pg_sweep.hip -- the per-locus OLS sweep of ols_iter_with_kinship and its host-side set-up; at the end the two users of its kernels in genomic prediction, pg_gp_beta_cols and pg_gp_proxy_dev (gp::ols itself: pg_gp.hip).
 //
 // Reference (gwas/ols.rs:340-370): for every column g of G and every trait y,
 //     X = [1 | C | g],  b = (X^T X)^-1 X^T y,  report b, var(b), p of the LAST coefficient
@@ -1509,43 +1509,18 @@ extern "C" int pg_ols_kinship(pg_ctx *ctx, const double *G, int64_t p, int n, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// gp::ols, n < p branch (gp/ols.rs:47-72): b = X^T pinv(X X^T) y over the training rows.
+// gp::ols, n < p branch (gp/ols.rs:47-72): b = X^T pinv(X X^T) y over the training rows.  Here the device's part of
+// it, the products G Z for the host's Z = pinv(X X^T) y (pg_gp.hip: pg_gp_ols_dev and the ridge path), on the sweep's kernels.
 // ---------------------------------------------------------------------------------------------
-template <int C>
-static int launch_gp_beta(pg_ctx *ctx, const double *G, const double *W, double *out, const SweepDims &D, int grid) {
-    const size_t shmem = (size_t)SW_WAVES * SW_TILE * sizeof(double);
-    PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_gp_beta<C>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+// one launch of a coefficient-pass kernel with `shmem` bytes of dynamic LDS
+template <typename... KArgs, typename... Args>
+static int launch_gp_beta_kernel(pg_ctx *ctx, void (*kern)(KArgs...), int grid, size_t shmem, Args... args) {
+    PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     pg_prof_begin(ctx, PG_K_GP_BETA);
-    hipLaunchKernelGGL(k_gp_beta<C>, dim3(grid), dim3(SW_THREADS), shmem, ctx->stream, G, W, out, D);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(SW_THREADS), shmem, ctx->stream, args...);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
     return PG_OK;
-}
-
-template <int C>
-static int launch_gp_beta_lds(pg_ctx *ctx, const double *G, const double *W, double *out, const SweepDims &D, int wdoubles) {
-    const size_t shmem = ((size_t)wdoubles + (size_t)SW_WAVES * SW_TILE) * sizeof(double);
-    PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_gp_beta_lds<C>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    const int64_t blocks = (D.ntiles + SW_WAVES - 1) / SW_WAVES;
-    const int grid = (int)std::min<int64_t>(blocks, (int64_t)ctx->cus); // one block per CU: Z occupies most of its LDS
-    pg_prof_begin(ctx, PG_K_GP_BETA);
-    hipLaunchKernelGGL(k_gp_beta_lds<C>, dim3(grid), dim3(SW_THREADS), shmem, ctx->stream, G, W, out, D, wdoubles);
-    pg_prof_end(ctx);
-    PG_HIP(ctx, hipGetLastError());
-    return PG_OK;
-}
-
-// ---- internal pieces of gp::ols shared with the ridge path (pg_gp.hip) ---------------------------------
-// V (r x k) = pinv(A) Y_rows with A the principal sub-block `rows` of the full-data X X^T (n x n, host)
-int pg_gp_subset_solve(const double *xxt, int n, const double *Y, int k, const int64_t *rows, int r, double *V) {
-    std::vector<double> A((size_t)r * r), Ysub((size_t)r * k);
-    for (int a = 0; a < r; ++a) {
-        for (int b = 0; b < r; ++b) A[(size_t)a * r + b] = xxt[(size_t)rows[a] * n + rows[b]];
-        for (int j = 0; j < k; ++j) Ysub[(size_t)a * k + j] = Y[(size_t)rows[a] * k + j];
-    }
-    return pg_pinv_solve_sym(A.data(), r, Ysub.data(), k, V);
 }
 
 // out (p x ncol, device) = G Z for a host Z (n x ncol row-major): the slopes of `ncol` fits in ONE pass over G
@@ -1579,114 +1554,34 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
     const int64_t cap = (int64_t)ctx->cus * 8;
     const int grid = (int)(blocks < cap ? blocks : cap);
     // the matrix-core kernel of the sweep in its products-only mode: every shape, one read of G at the sweep's rate
-    if (ms_fits(n, ncol, 1) && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && !std::getenv("POOLGEN_GP_BETA_OLD")) {
-        rc = launch_sweep_mfma<1>(ctx, P, cols, ncol, PG_K_GP_BETA);
-        if (rc) return rc;
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z is stack-owned
-        return PG_OK;
-    }
-    // (the older forms, kept for A/B timing: POOLGEN_GP_BETA_OLD=1)
-    // the folds' slopes of a CV repetition (column-major, up to 16 columns): the MFMA form over an LDS-staged tile
+    // (the older forms below are kept for A/B timing: POOLGEN_GP_BETA_OLD=1)
     const int zrows = (n + SW_CH - 1) / SW_CH * SW_CH;
     const size_t mfma_lds = ((size_t)zrows * 16 + (size_t)SW_WAVES * MB_TILE) * sizeof(double);
-    if (!ss_out_dev && colmajor && ncol >= 5 && ncol <= 16 && mfma_lds <= 150 * 1024 && !std::getenv("POOLGEN_GP_BETA_VALU")) {
-        rc = upload_Z(Z16, zrows, 16);
-        if (rc) return rc;
-        PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_gp_beta_mfma), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)mfma_lds));
-        const int64_t nblocks = (D.ntiles + SW_WAVES - 1) / SW_WAVES;
-        const int g2 = (int)std::min<int64_t>(nblocks, (int64_t)ctx->cus);
-        pg_prof_begin(ctx, PG_K_GP_BETA);
-        hipLaunchKernelGGL(k_gp_beta_mfma, dim3(g2), dim3(SW_THREADS), mfma_lds, ctx->stream, G_dev, ctx->W_dev, out_dev, D, zrows);
-        pg_prof_end(ctx);
-        PG_HIP(ctx, hipGetLastError());
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z16 is stack-owned
-        return PG_OK;
-    }
-    // many columns x many pools: Z no longer fits the scalar cache -> the LDS-resident variant (see k_gp_beta_lds)
     const int wdoubles = n_even * cols;
     const size_t lds_need = ((size_t)wdoubles + (size_t)SW_WAVES * SW_TILE) * sizeof(double);
-    if (!ss_out_dev && cols >= 6 && (cols % 2) == 0 && cols <= 24 && (size_t)wdoubles * sizeof(double) > 12288 && lds_need <= 150 * 1024 &&
-        !std::getenv("POOLGEN_GP_BETA_SCALAR")) {
-        rc = with_cols_in<24, 16, 12, 8, 6>(ctx, cols, [&](auto c) {
-            return launch_gp_beta_lds<decltype(c)::value>(ctx, G_dev, ctx->W_dev, out_dev, D, wdoubles);
+    if (ms_fits(n, ncol, 1) && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && !std::getenv("POOLGEN_GP_BETA_OLD"))
+        rc = launch_sweep_mfma<1>(ctx, P, cols, ncol, PG_K_GP_BETA);
+    // the folds' slopes of a CV repetition (column-major, up to 16 columns): the MFMA form over an LDS-staged tile
+    else if (!ss_out_dev && colmajor && ncol >= 5 && ncol <= 16 && mfma_lds <= 150 * 1024 && !std::getenv("POOLGEN_GP_BETA_VALU")) {
+        rc = upload_Z(Z16, zrows, 16);
+        if (rc) return rc;
+        const int g2 = (int)std::min<int64_t>(blocks, (int64_t)ctx->cus);
+        rc = launch_gp_beta_kernel(ctx, k_gp_beta_mfma, g2, mfma_lds, G_dev, ctx->W_dev.get(), out_dev, D, zrows);
+    }
+    // many columns x many pools: Z no longer fits the scalar cache -> the LDS-resident variant (see k_gp_beta_lds)
+    else if (!ss_out_dev && cols >= 6 && (cols % 2) == 0 && cols <= 24 && (size_t)wdoubles * sizeof(double) > 12288 && lds_need <= 150 * 1024 &&
+             !std::getenv("POOLGEN_GP_BETA_SCALAR"))
+        rc = with_cols_in<24, 16, 12, 8, 6>(ctx, cols, [&](auto c) { // one block per CU: Z occupies most of its LDS
+            return launch_gp_beta_kernel(ctx, k_gp_beta_lds<decltype(c)::value>, (int)std::min<int64_t>(blocks, (int64_t)ctx->cus), lds_need,
+                                         G_dev, ctx->W_dev.get(), out_dev, D, wdoubles);
         });
-        if (rc) return rc;
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z is stack-owned
-        return PG_OK;
-    }
-    rc = with_cols(ctx, cols, [&](auto c) { return launch_gp_beta<decltype(c)::value>(ctx, G_dev, ctx->W_dev, out_dev, D, grid); });
+    else
+        rc = with_cols(ctx, cols, [&](auto c) {
+            return launch_gp_beta_kernel(ctx, k_gp_beta<decltype(c)::value>, grid, (size_t)SW_WAVES * SW_TILE * sizeof(double), G_dev,
+                                         ctx->W_dev.get(), out_dev, D);
+        });
     if (rc) return rc;
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z is stack-owned
-    return PG_OK;
-}
-
-extern "C" int pg_gp_ols_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y,
-                             int k, const int64_t *row_idx, int n_rows, const double *XXt_host_or_null,
-                             double *beta_dev) {
-    if (!ctx) return PG_ERR_INVALID;
-    PG_CHECK(ctx, G_dev && Y && row_idx && beta_dev && p > 0 && n >= 1 && k >= 1 && n_rows >= 1 && n_rows <= n,
-             "gp_ols: bad arguments");
-    PG_CHECK(ctx, ld >= n && (ld % 2) == 0, "gp_ols: ld must be even and >= n");
-    if (k > 8) return pg_fail(ctx, PG_ERR_UNSUPPORTED, "gp_ols: at most 8 traits per call");
-    for (int a = 0; a < n_rows; ++a) PG_CHECK(ctx, row_idx[a] >= 0 && row_idx[a] < n, "gp_ols: row index out of range");
-    PG_HIP(ctx, hipSetDevice(ctx->device));
-    if ((int64_t)n >= p + 1) {
-        // The tall branch (gp/ols.rs:72-99, taken when x.nrows() >= x.ncols(): at most n - 1 loci, i.e. the reference's own 5 x 3
-        // test, never a pool-seq matrix): b = pinv(X'X over the training rows) X' y.  (1 + p)^2 <= n^2 numbers: the host's,
-        // not a GPU problem.  pinv as in the wide branch (helpers.rs:463-482).
-        const int P = (int)p + 1;
-        std::vector<double> Gh((size_t)p * ld);
-        PG_HIP(ctx, hipMemcpyAsync(Gh.data(), G_dev, sizeof(double) * (size_t)p * ld, hipMemcpyDeviceToHost, ctx->stream));
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        auto X = [&](int64_t i, int c) { return c == 0 ? 1.0 : Gh[(size_t)(c - 1) * ld + i]; };
-        std::vector<double> xtx((size_t)P * P), pinv((size_t)P * P), T((size_t)P * n_rows), b((size_t)P * k);
-        for (int a = 0; a < P; ++a)
-            for (int c = 0; c < P; ++c) {
-                double x = 0.0;
-                for (int i = 0; i < n_rows; ++i) x += X(row_idx[i], a) * X(row_idx[i], c);
-                xtx[(size_t)a * P + c] = x;
-            }
-        if (pg_pinv_sym(xtx.data(), P, pinv.data()) != 0) return pg_fail(ctx, PG_ERR_INVALID, "gp_ols: pinv failed");
-        for (int a = 0; a < P; ++a) // (pinv X') y, in the reference's order of products
-            for (int i = 0; i < n_rows; ++i) {
-                double x = 0.0;
-                for (int c = 0; c < P; ++c) x += pinv[(size_t)a * P + c] * X(row_idx[i], c);
-                T[(size_t)a * n_rows + i] = x;
-            }
-        for (int a = 0; a < P; ++a)
-            for (int j = 0; j < k; ++j) {
-                double x = 0.0;
-                for (int i = 0; i < n_rows; ++i) x += T[(size_t)a * n_rows + i] * Y[(size_t)row_idx[i] * k + j];
-                b[(size_t)a * k + j] = x;
-            }
-        PG_HIP(ctx, hipMemcpyAsync(beta_dev, b.data(), sizeof(double) * (size_t)P * k, hipMemcpyHostToDevice, ctx->stream));
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // b is stack-owned
-        return PG_OK;
-    }
-    std::vector<double> full((size_t)n * n);
-    if (XXt_host_or_null) {
-        std::memcpy(full.data(), XXt_host_or_null, sizeof(double) * n * n);
-    } else {
-        int rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "gp_ols");
-        if (!rc) rc = pg_launch_kinship(ctx, G_dev, p, n, ld, ctx->S_dev, true, PG_K_GP_XXT);
-        if (rc) return rc;
-        PG_HIP(ctx, hipMemcpyAsync(full.data(), ctx->S_dev, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream));
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    // every training subset's X X^T is a principal sub-block of the full-data one
-    const int r = n_rows;
-    std::vector<double> V((size_t)r * k);
-    if (pg_gp_subset_solve(full.data(), n, Y, k, row_idx, r, V.data()) != 0) return pg_fail(ctx, PG_ERR_INVALID, "gp_ols: pinv failed");
-    std::vector<double> Z((size_t)n * k, 0.0), b0(k, 0.0);
-    for (int a = 0; a < r; ++a)
-        for (int j = 0; j < k; ++j) {
-            Z[(size_t)row_idx[a] * k + j] = V[(size_t)a * k + j];
-            b0[j] += V[(size_t)a * k + j]; // intercept column of X is all ones
-        }
-    PG_HIP(ctx, hipMemcpyAsync(beta_dev, b0.data(), sizeof(double) * k, hipMemcpyHostToDevice, ctx->stream));
-    int rc = pg_gp_beta_cols(ctx, G_dev, p, n, ld, Z.data(), k, beta_dev + k); // rows 1..p
-    if (rc) return rc;
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // Z and Z16 are stack-owned
     return PG_OK;
 }
 
@@ -1733,17 +1628,8 @@ extern "C" int pg_gp_proxy_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int 
     for (int a = 0; a < n_rows; ++a) PG_CHECK(ctx, row_idx[a] >= 0 && row_idx[a] < n, "gp_proxy: row index out of range");
     PG_HIP(ctx, hipSetDevice(ctx->device));
     const int nr = n_rows;
-    std::vector<double> T((size_t)n * n), glast(n);
-    if (XXt_host_or_null) std::memcpy(T.data(), XXt_host_or_null, sizeof(double) * n * n);
-    else {
-        DevBuf<double> S;
-        int rc = S.alloc(ctx, sizeof(double) * n * n, "gp_proxy");
-        if (!rc) rc = pg_gp_xxt_dev(ctx, G_dev, p, n, ld, S.get());
-        if (rc) return rc;
-        if (hipMemcpyAsync(T.data(), S.get(), sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            return pg_fail(ctx, PG_ERR_HIP, "gp_proxy: D2H failed");
-    }
+    std::vector<double> T, glast(n);
+    if (int rc = pg_gp_xxt_host(ctx, G_dev, p, n, ld, XXt_host_or_null, "gp_proxy", T)) return rc;
     PG_HIP(ctx, hipMemcpyAsync(glast.data(), G_dev + (p - 1) * ld, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // The reference centres columns 0..P-2 of x = [1 | G^T] (the intercept IS among them, the last locus is NOT, :115),

@@ -521,7 +521,7 @@ def test_gp_proxy_matches_oracle(engine, oracle, exact, n, p, k, rows):
 
 
 # gp::ols takes pinv(X X^T) for a wide design and pinv(X'X) for a tall one (n >= p + 1 with the intercept column, gp/ols.rs:47;
-# pg_gp_ols_dev, pg_sweep.hip:1679; the fused passes only where it is wide, pg_gp.hip:667-670).  Shapes at the edge on both sides
+# pg_gp_ols_dev, pg_gp.hip:1088; the fused passes only where it is wide, penalised_path, pg_gp.hip:1045).  Shapes at the edge on both sides
 # (p = n - 1 tall, p = n wide) and well inside the tall side (p ~ n / 3); n_reps 1 and 3 (the batched passes need n_reps > 1).
 # (The reference's own 5 x 3 shape leaves a fold with a single validation pool at these fold counts: its error index is 0 / 0.)
 @pytest.mark.parametrize("n,p,k,alpha,proxy,n_reps", [
