@@ -338,6 +338,40 @@ int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t 
                int64_t n_windows, double *fst_mean, double *fst_win);
 
 /* ---------------------------------------------------------------------------------------
+ * watterson_estimator (popgen/watterson_theta.rs:8-188) and tajima_d (popgen/tajima_d.rs:10-96) on
+ * the same matrix and windows.  A (locus, pool) is polymorphic iff no frequency of the locus is
+ * >= 1.0 in the pool (:8-30; NaN never wins the fold, so an all-NaN pool counts).  Per window and
+ * pool, theta_W = (S / cov) / a1 with a1 = sum_{x = 1}^{(pool_size as usize) - 1} 1/x (:175-182);
+ * D = (pi - theta_W) / sqrt(e1 s + e2 s (s - 1)), s = theta_W / a1, with the reference's guards
+ * (tajima_d.rs:51-96); pi is pg_pi_dev's, from the same pass over G.
+ * Two ways to count S:
+ *   reference: what the reference's loop ends up with, S = poly(seed) + (cov - 1) * poly(slot) --
+ *              it evaluates the flag at the window's index, not at the locus (:107-137);
+ *   counted  : S = the polymorphic loci of head .. tail, cov = tail - head + 1.
+ * pool_sizes are used as given (the reference's CLI hands in fractions that sum to one, so that
+ * a1 = 0 and every value is inf or NaN, main.rs:463, phen.rs:83-84); sizes above 1e9 are refused.
+ * A window with tail < head (the stale tail of a ditched slot; the reference panics) is refused
+ * with PG_ERR_INVALID, as is n_windows < 1.
+ * ------------------------------------------------------------------------------------- */
+/* theta_watterson's own window loop (watterson_theta.rs:56-164): head/tail as pg_host_sliding_windows, plus per kept
+ * window the loci counted (cov), the locus its count starts from (seed) and its index in the unfiltered window list
+ * (slot): S = poly(seed) + (cov - 1) * poly(slot) is the reference's count (:107-137).  Arrays need room for L. */
+int64_t pg_host_watterson_windows(const int32_t *chr_id, const uint64_t *pos, int64_t L, uint64_t window_size_bp,
+                                  uint64_t window_slide_size_bp, uint64_t min_loci_per_window, int64_t *head,
+                                  int64_t *tail, int64_t *cov, int64_t *seed, int64_t *slot);
+/* win_cov, win_seed, win_slot all NULL = counted mode.  pool_sizes: host, n, used as given.
+ * theta_win n_windows x n, theta_mean n, seg_win (optional) n_windows x n counts S. */
+int pg_watterson_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
+                     const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
+                     const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win,
+                     double *theta_mean, int64_t *seg_win);
+/* d_win n_windows x n, d_mean n; theta_win / pi_win optional outputs of the same pass. */
+int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                    const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                    const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
+                    const double *pool_sizes, double *d_win, double *d_mean, double *theta_win, double *pi_win);
+
+/* ---------------------------------------------------------------------------------------
  * Host-side pieces of the path (O(n^3), n = pools): exported so that they can be validated
  * without a GPU and reused by a host integration.
  * ------------------------------------------------------------------------------------- */

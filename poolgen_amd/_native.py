@@ -79,6 +79,9 @@ SIGNATURES = {
     "pg_host_sliding_windows": (_i64, [_vp, _vp, _i64, _u64, _u64, _u64, _vp, _vp]),
     "pg_pi_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "pg_fst_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "pg_host_watterson_windows": (_i64, [_vp, _vp, _i64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "pg_watterson_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pg_tajima_d_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pg_gp_predict_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i, _vp]),
     "pg_host_sym_eig": (_i, [_vp, _i, _vp, _vp]),
     "pg_host_sym_eig_top": (_i, [_vp, _i, _i, _vp, _vp]),

@@ -175,6 +175,7 @@ Phen parse_phen(const std::string &fname, const std::string &delim, int name_col
         }
     }
     ph.n = (int)ph.pool_names.size();
+    ph.pool_sizes_as_written = ph.pool_sizes;
     double total = 0.0;
     for (double s : ph.pool_sizes) total = total + s;
     for (double &s : ph.pool_sizes) s /= total; // phen.rs:83-84

@@ -29,6 +29,7 @@ bool parse_i64_strict(const std::string &s, int64_t &out);
 struct Phen {
     std::vector<std::string> pool_names;
     std::vector<double> pool_sizes;    // normalised to sum 1 (phen.rs:83-84)
+    std::vector<double> pool_sizes_as_written; // the column itself (--popgen-as-documented)
     std::vector<double> phen;          // n x k row-major, NaN = missing
     int n = 0, k = 0;
 };

@@ -49,6 +49,9 @@ struct Args {
     int k_folds = 10, n_reps = 3; // genomic_prediction_cross_validation (main.rs:104-109)
     uint64_t seed = 42;           // ... and the seed of its folds (an extension: the reference's folds are unrepeatable)
     uint64_t window_size_bp = 100, window_slide_size_bp = 50, min_loci_per_window = 10; // fst / heterozygosity (main.rs:110-118)
+    // watterson_estimator / tajima_d (an extension): the pool sizes as the phenotype file has them and every locus of a window
+    // counted, instead of the reference's fractions and its count
+    bool popgen_as_documented = false;
     // multi-GPU (an extension: the reference's parallel axis is --n-threads, one worker per file chunk, sync.rs:913-939):
     // the input is cut into one contiguous byte range per GPU, each with its own parser threads.  0 = flag absent.
     int n_gpus = 0;
@@ -78,7 +81,7 @@ static int flag_int(const std::string &v, const std::string &flag, int64_t lo = 
 static const char *USAGE =
     "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
     "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship,\n"
-    "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity\n"
+    "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d\n"
     "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
     "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
     "                                     writes A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on pileup-derived\n"
@@ -91,7 +94,11 @@ static const char *USAGE =
     "      --keep-p-minus-1                drop the major allele of every locus when loading the matrix\n"
     "  -x, --xxt-eigen-variance-explained <0.75>   ols_iter_with_kinship: the n_eigenvecs rule's threshold\n"
     "      --k-folds <10>  --n-reps <3>  --seed <42>     genomic_prediction_cross_validation\n"
-    "      --window-size-bp <100>  --window-slide-size-bp <50>  --min-loci-per-window <10>   fst, heterozygosity\n"
+    "      --window-size-bp <100>  --window-slide-size-bp <50>  --min-loci-per-window <10>   fst, heterozygosity, watterson_estimator, tajima_d\n"
+    "      --popgen-as-documented          watterson_estimator, tajima_d: use the pool sizes as the phenotype file has them and count\n"
+    "                                      the polymorphic loci of every window.  Default: the reference's behaviour -- pool sizes as\n"
+    "                                      fractions of their sum (its harmonic sums are then empty: every value is inf or NaN) and\n"
+    "                                      its count, which looks the flag up at the window's index instead of the locus\n"
     "      --n-threads <1>                 parser / writer threads\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
     "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship: one contiguous\n"
@@ -151,6 +158,7 @@ static Args parse_args(int argc, char **argv) {
         else if (k == "--window-size-bp") a.window_size_bp = flag_u64(val(), k);
         else if (k == "--window-slide-size-bp") a.window_slide_size_bp = flag_u64(val(), k);
         else if (k == "--min-loci-per-window") a.min_loci_per_window = flag_u64(val(), k);
+        else if (k == "--popgen-as-documented") a.popgen_as_documented = true;
         else if (k.rfind("-", 0) == 0) throw std::runtime_error("unknown flag " + k);
         else pos.push_back(k);
     }
@@ -790,12 +798,14 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
     return done_ok();
 }
 
-// fst (popgen/fst.rs:10-261) and heterozygosity = pi (popgen/pi.rs:115-190) on the loaded matrix: loci and windows on
-// the host (count_loci, define_sliding_windows), the per-locus arithmetic and the means on the GPU, the files as written
-// by the reference.
-static int run_popgen(const Args &a, bool is_fst, Ctx &gpu, const double *G_dev, const double *cov_dev, int64_t p, int n,
+// fst (popgen/fst.rs:10-261), heterozygosity = pi (popgen/pi.rs:115-190), watterson_estimator (popgen/watterson_theta.rs:191-289)
+// and tajima_d (popgen/tajima_d.rs:10-171) on the loaded matrix: loci and windows on the host (count_loci,
+// define_sliding_windows), the per-locus arithmetic and the means on the GPU, the files as written by the reference.
+// pool_sizes: watterson_estimator / tajima_d only -- the reference's fractions, or the file's column (--popgen-as-documented).
+static int run_popgen(const Args &a, Analysis analysis, Ctx &gpu, const double *G_dev, const double *cov_dev, int64_t p, int n,
                       int64_t ld, const std::vector<std::string> &lab_chr, const std::vector<uint64_t> &lab_pos,
-                      const std::vector<std::string> &pool_names, Lap &lap) {
+                      const std::vector<std::string> &pool_names, const std::vector<double> &pool_sizes, Lap &lap) {
+    const bool is_fst = analysis == Analysis::fst;
     // count_loci (sync.rs:73-97) without the intercept entry: column starts, and each locus' coordinates
     std::vector<int64_t> locus_col;
     std::vector<int32_t> chr_id;
@@ -818,12 +828,37 @@ static int run_popgen(const Args &a, bool is_fst, Ctx &gpu, const double *G_dev,
     const std::string win = std::to_string(a.window_size_bp);
     const std::string time = unix_time_string();
     if (!is_fst) {
+        // one row per pool: name, mean across windows, the windows (pi.rs:160-188, watterson_theta.rs:244-287, tajima_d.rs:127-169)
         std::string out = a.output;
-        if (out.empty()) out = basename_no_ext(a.fname) + "-pi-" + win + "_bp_windows-" + time + ".csv"; // pi.rs:135-159
         std::vector<double> pw((size_t)nw * n), pm(n);
-        gpu.ok(pg_pi_dev(gpu.c, G_dev, cov_dev, p, n, ld, locus_col.data(), L, wh.data(), wt.data(), nw, pw.data(), pm.data()),
-               "heterozygosity");
-        lap("pi on the GPU");
+        const char *tag = "-pi-", *what = "heterozygosity"; // pi.rs:135-159
+        if (analysis == Analysis::heterozygosity)
+            gpu.ok(pg_pi_dev(gpu.c, G_dev, cov_dev, p, n, ld, locus_col.data(), L, wh.data(), wt.data(), nw, pw.data(), pm.data()), what);
+        else {
+            const bool tajima = analysis == Analysis::tajima_d;
+            tag = tajima ? "-Tajimas_D-" : "-watterson-"; // tajima_d.rs:120-125, watterson_theta.rs:237-242
+            what = tajima ? "tajima_d" : "watterson_estimator";
+            std::vector<int64_t> wc, wseed, wslot;
+            if (!a.popgen_as_documented) { // the reference's own loop: the same windows, and what its count is made of
+                std::cerr << "note: " << what << " reproduces the reference: the pool sizes are fractions of their sum, so every value is inf or NaN, "
+                             "and the segregating sites are counted its way; --popgen-as-documented uses the pool sizes as written and counts every locus\n";
+                std::vector<int64_t> h2(L), t2(L);
+                wc.resize(L); wseed.resize(L); wslot.resize(L);
+                const int64_t nw2 = pg_host_watterson_windows(chr_id.data(), loc_pos.data(), L, a.window_size_bp, a.window_slide_size_bp,
+                                                              a.min_loci_per_window, h2.data(), t2.data(), wc.data(), wseed.data(), wslot.data());
+                h2.resize(nw2); t2.resize(nw2);
+                if (h2 != wh || t2 != wt) throw std::runtime_error("internal error: the two window loops disagree"); // tajima_d.rs:46-47
+            }
+            const int64_t *c = wc.empty() ? nullptr : wc.data(), *sd = wc.empty() ? nullptr : wseed.data(), *sl = wc.empty() ? nullptr : wslot.data();
+            if (tajima)
+                gpu.ok(pg_tajima_d_dev(gpu.c, G_dev, cov_dev, p, n, ld, locus_col.data(), L, wh.data(), wt.data(), c, sd, sl, nw, pool_sizes.data(),
+                                       pw.data(), pm.data(), nullptr, nullptr), what);
+            else
+                gpu.ok(pg_watterson_dev(gpu.c, G_dev, p, n, ld, locus_col.data(), L, wh.data(), wt.data(), c, sd, sl, nw, pool_sizes.data(), pw.data(),
+                                        pm.data(), nullptr), what);
+        }
+        if (out.empty()) out = basename_no_ext(a.fname) + tag + win + "_bp_windows-" + time + ".csv";
+        lap("windows on the GPU");
         FILE *fo = create_new(out);
         std::string line = "Pool,Mean_across_windows";
         for (int64_t w = 0; w < nw; ++w)
@@ -993,15 +1028,18 @@ static int run(int argc, char **argv) {
         {"fisher_exact_test", Analysis::fisher_exact_test}, {"ols_iter_with_kinship", Analysis::ols_iter_with_kinship},
         {"mle_iter_with_kinship", Analysis::mle_iter_with_kinship},
         {"genomic_prediction_cross_validation", Analysis::genomic_prediction_cross_validation}, {"fst", Analysis::fst},
-        {"heterozygosity", Analysis::heterozygosity}, {"pileup2sync", Analysis::pileup2sync}};
+        {"heterozygosity", Analysis::heterozygosity}, {"watterson_estimator", Analysis::watterson_estimator},
+        {"tajima_d", Analysis::tajima_d}, {"pileup2sync", Analysis::pileup2sync}};
     const auto found = known.find(a.analysis);
     if (found == known.end())
         throw std::runtime_error("Invalid analysis utility for this build: `" + a.analysis +
                                  "` (available: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship, "
-                                 "mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity)");
+                                 "mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d)");
+    const Analysis analysis = found->second;
+    if (a.popgen_as_documented && analysis != Analysis::watterson_estimator && analysis != Analysis::tajima_d)
+        throw std::runtime_error("--popgen-as-documented applies to watterson_estimator and tajima_d");
     if (a.generate_plots || a.sig_only)
         throw std::runtime_error("--generate-plots / --output-sig-snps-only call the reference's python scripts and are out of scope here");
-    const Analysis analysis = found->second;
     Phen ph = parse_phen(a.phen_fname, a.phen_delim, a.phen_name_col, a.phen_pool_size_col, a.phen_value_col);
     const PileupFilter pf = pileup_filter(a, ph.pool_sizes);
     // the counts are parsed straight into pinned memory: the copy to the device needs no staging pass
@@ -1072,16 +1110,16 @@ static int run(int argc, char **argv) {
     if (sb.size() == 0) throw std::runtime_error("no loci in " + a.fname);
     if (sb.n != ph.n) throw std::runtime_error("the number of pools in the sync file and in the phenotype file differ");
     const int k = ph.k;
-    const bool popgen = analysis == Analysis::fst || analysis == Analysis::heterozygosity;
+    const bool popgen = pgh::popgen(analysis);
 
     // ---------------- the analyses on the loaded matrix (main.rs:280-298, :397-455) ---------------------------
-    const bool kpm1 = analysis == Analysis::heterozygosity ? false : a.keep_p_minus_1; // heterozygosity: "we need all alleles in each locus" (main.rs:445)
+    const bool kpm1 = popgen && analysis != Analysis::fst ? false : a.keep_p_minus_1; // "we need all alleles in each locus" (main.rs:445, :460, :475)
     GenotypesAndPhenotypes genotypes_and_phenotypes =
         into_genotypes_and_phenotypes(gpu, sb, ph, flt, kpm1, /*remove_missing=*/!popgen, /*with_coverages=*/popgen, lap);
     GenotypesAndPhenotypes &g = genotypes_and_phenotypes;
-    if (popgen) // fst / heterozygosity use every pool (main.rs:427-455)
-        return run_popgen(a, analysis == Analysis::fst, gpu, g.intercept_and_allele_frequencies.get(), g.coverages.get(), g.p, g.n, g.ld, g.chromosome, g.position,
-                          g.pool_names, lap);
+    if (popgen) // fst / heterozygosity / watterson_estimator / tajima_d use every pool (main.rs:427-485)
+        return run_popgen(a, analysis, gpu, g.intercept_and_allele_frequencies.get(), g.coverages.get(), g.p, g.n, g.ld, g.chromosome, g.position,
+                          g.pool_names, a.popgen_as_documented ? ph.pool_sizes_as_written : ph.pool_sizes, lap);
     if (analysis == Analysis::genomic_prediction_cross_validation) { // genomic_prediction_cross_validation (main.rs:397-426)
         CvLabels labels{g.chromosome, g.allele, g.position};
         CvArgs ca;

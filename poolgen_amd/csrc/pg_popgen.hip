@@ -6,6 +6,11 @@
 //
 //   k_pop_locus      thread = (locus, pool): sum of squared frequencies over the locus' alleles, the n/(n-1) factor,
 //                    q1 (fst.rs:69-75) and pi (pi.rs:51-54): two L x n arrays, 1/a of the size of G
+//                    (optionally, in the same pass, the polymorphic flag of watterson_theta.rs:8-30: one byte)
+//   k_poly_locus     thread = (locus, pool): the flag alone, for watterson_estimator, which needs no pi
+//   k_diversity_windows  thread = (window, pool): one walk over the window's loci -> the pi sum (k_range_mean_1d's order
+//                    and bits) and the count of flagged loci, then theta_W (watterson_theta.rs:175-182) and Tajima's D
+//                    (tajima_d.rs:62-81) from per-pool constants the host computed
 //   k_pop_check      thread = locus: the reference's guard that the frequencies of a locus sum to n (fst.rs:66), in
 //                    ndarray's summation orders
 //   k_range_mean_1d  thread = (window, pool): mean of pi over the window's loci, summed left to right as
@@ -25,23 +30,42 @@ namespace {
 
 constexpr double POP_EPS = 2.220446049250313e-16; // f64::EPSILON
 
+// FLAG (polymorphic_loci_per_pool, watterson_theta.rs:20-27): 1 iff the fold (0.0, |max, x| if x > max { x } else { max })
+// over the locus' frequencies ends below 1.0 -- a NaN never wins the comparison, so an all-NaN pool counts as polymorphic.
+__device__ __forceinline__ double poly_fold(double m, double g) { return g > m ? g : m; }
+
+template <bool WITH_Q1, bool WITH_FLAG>
 __global__ __launch_bounds__(256) void k_pop_locus(const double *__restrict__ G, const double *__restrict__ cov,
                                                    const int64_t *__restrict__ locus_col, int64_t L, int n, int64_t ld,
-                                                   double *__restrict__ Q1, double *__restrict__ PI) {
+                                                   double *__restrict__ Q1, double *__restrict__ PI,
+                                                   uint8_t *__restrict__ FLAG) {
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t l = gid / n;
     if (l >= L) return;
     const int pool = (int)(gid - l * n);
     const int64_t c0 = locus_col[l], c1 = locus_col[l + 1];
-    double s = 0.0;
+    double s = 0.0, m = 0.0;
     for (int64_t c = c0; c < c1; ++c) {
         const double g = G[c * ld + pool];
         s = s + g * g;
+        if (WITH_FLAG) m = poly_fold(m, g);
     }
     const double nj = cov[c0 * ld + pool];
     const double r = nj / (nj - 1.00 + POP_EPS);
-    Q1[gid] = (s * r) + (1.00 - r);
+    if (WITH_Q1) Q1[gid] = (s * r) + (1.00 - r);
     PI[gid] = fabs((s * r) - r);
+    if (WITH_FLAG) FLAG[gid] = m < 1.0 ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_poly_locus(const double *__restrict__ G, const int64_t *__restrict__ locus_col,
+                                                    int64_t L, int n, int64_t ld, uint8_t *__restrict__ FLAG) {
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t l = gid / n;
+    if (l >= L) return;
+    const int pool = (int)(gid - l * n);
+    double m = 0.0;
+    for (int64_t c = locus_col[l]; c < locus_col[l + 1]; ++c) m = poly_fold(m, G[c * ld + pool]);
+    FLAG[gid] = m < 1.0 ? 1 : 0;
 }
 
 // |sum_i (sum_a g) - n| <= eps with ndarray's orders: the lane of < 8 alleles left to right, the n row sums by
@@ -85,6 +109,49 @@ __global__ __launch_bounds__(256) void k_range_mean_1d(const double *__restrict_
     double s = 0.0;
     for (int64_t l = head[w]; l <= tail[w]; ++l) s = s + V[l * n + pool];
     out[gid] = s / (double)(tail[w] + 1 - head[w]);
+}
+
+// Per (window, pool): S, theta_W and -- TAJIMA -- pi and D.  wcov == nullptr is the counted mode (S = the flagged loci of
+// head..tail, cov = their number); otherwise the reference's count (watterson_theta.rs:107-137): the window's first flag plus
+// cov - 1 times the flag of the locus whose index is the window's slot.  kc = a1[n], e1[n], e2[n] (tajima_d.rs:53-61).
+// Every step is one IEEE operation in the reference's order; NaN fails each comparison and reaches the division.
+template <bool TAJIMA>
+__global__ __launch_bounds__(256) void k_diversity_windows(const double *__restrict__ PI, const uint8_t *__restrict__ FLAG,
+                                                           const int64_t *__restrict__ head, const int64_t *__restrict__ tail,
+                                                           const int64_t *__restrict__ wcov, const int64_t *__restrict__ wseed,
+                                                           const int64_t *__restrict__ wslot, int64_t nw, int n,
+                                                           const double *__restrict__ kc, int64_t *__restrict__ seg,
+                                                           double *__restrict__ theta_out, double *__restrict__ pi_out,
+                                                           double *__restrict__ d_out) {
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t w = gid / n;
+    if (w >= nw) return;
+    const int pool = (int)(gid - w * n);
+    const int64_t l0 = head[w], l1 = tail[w];
+    const bool counted = wcov == nullptr;
+    int64_t S = 0, c = l1 + 1 - l0;
+    double s = 0.0;
+    if (TAJIMA || counted)
+        for (int64_t l = l0; l <= l1; ++l) {
+            if (TAJIMA) s = s + PI[l * n + pool];
+            if (counted) S += FLAG[l * n + pool];
+        }
+    if (!counted) {
+        c = wcov[w];
+        S = (int64_t)FLAG[wseed[w] * n + pool] + (c - 1) * (int64_t)FLAG[wslot[w] * n + pool];
+    }
+    const double a1 = kc[pool];
+    const double theta = ((double)S / (double)c) / a1; // :177-180
+    if (seg) seg[gid] = S;
+    theta_out[gid] = theta;
+    if (TAJIMA) {
+        const double pi = s / (double)(l1 + 1 - l0); // k_range_mean_1d
+        const double e1 = kc[n + pool], e2 = kc[2 * n + pool];
+        const double sw = theta <= POP_EPS ? 0.0 : theta / a1;
+        const double vd = (e1 * sw) + ((e2 * sw) * (sw - 1.0));
+        pi_out[gid] = pi;
+        d_out[gid] = fabs(pi - theta) <= POP_EPS ? 0.0 : (vd <= POP_EPS ? 0.0 : (pi - theta) / sqrt(vd));
+    }
 }
 
 // a / b as hipcc's own fp64 division computes it for normal-range operands, minus the scaling and fix-up steps those
@@ -191,6 +258,104 @@ int check_shape(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t
     return PG_OK;
 }
 
+// pool_sizes[j] as usize (watterson_theta.rs:179, tajima_d.rs:52): Rust's saturating truncation, NaN -> 0
+uint64_t pool_size_as_usize(double x) {
+    if (!(x >= 1.0)) return 0;
+    return x >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)x;
+}
+
+// a1[n], e1[n], e2[n] of tajima_d.rs:53-61 (a1 alone is watterson_theta.rs:178-179), every operation and its order as
+// written there.  powf is libm's pow: the exponent is read through a volatile so that the call is not folded into x * x.
+void diversity_constants(const double *pool_sizes, int n, std::vector<double> &kc) {
+    volatile double two_v = 2.0;
+    const double two = two_v;
+    kc.assign((size_t)3 * n, 0.0);
+    for (int j = 0; j < n; ++j) {
+        const uint64_t m = pool_size_as_usize(pool_sizes[j]);
+        double a1 = 0.0, a2 = 0.0;
+        for (uint64_t x = 1; x < m; ++x) a1 = a1 + (1.00 / (double)x);
+        for (uint64_t x = 1; x < m; ++x) a2 = a2 + (1.00 / std::pow((double)x, two));
+        const double nn = (double)m;
+        const double b1 = (nn + 1.0) / (3.0 * (nn - 1.0));
+        const double b2 = (2.0 * (std::pow(nn, two) + nn + 3.0)) / (9.0 * nn * (nn - 1.0));
+        const double c1 = b1 - (1.0 / a1);
+        const double c2 = b2 - ((nn + 2.0) / (a1 * nn)) + (a2 / std::pow(a1, two));
+        kc[j] = a1;
+        kc[(size_t)n + j] = c1 / a1;
+        kc[(size_t)2 * n + j] = c2 / (std::pow(a1, two) + a2);
+    }
+}
+
+constexpr double POOL_SIZE_MAX = 1e9; // the harmonic sums are loops over 1 .. pool size
+
+// watterson_estimator (tajima == false: no coverages, no pi) and tajima_d on one locus pass and one window pass
+int diversity_run(pg_ctx *ctx, bool tajima, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                  const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov,
+                  const int64_t *win_seed, const int64_t *win_slot, int64_t nw, const double *pool_sizes, double *d_win,
+                  double *d_mean, double *theta_win, double *theta_mean, double *pi_win, int64_t *seg_win) {
+    const char *who = tajima ? "tajima_d" : "watterson";
+    int rc = check_shape(ctx, G_dev, tajima ? cov_dev : G_dev, p, n, ld, locus_col, L, win_head, win_tail, nw, who);
+    if (rc) return rc;
+    PG_CHECK(ctx, nw >= 1, "%s: There were no windows defined.", who);
+    PG_CHECK(ctx, pool_sizes && (tajima ? d_win && d_mean : theta_win && theta_mean), "%s: null argument", who);
+    const bool reference = win_cov || win_seed || win_slot;
+    PG_CHECK(ctx, !reference || (win_cov && win_seed && win_slot), "%s: win_cov, win_seed and win_slot go together", who);
+    for (int64_t w = 0; reference && w < nw; ++w)
+        PG_CHECK(ctx, win_cov[w] >= 1 && win_seed[w] >= 0 && win_seed[w] < L && win_slot[w] >= 0 && win_slot[w] < L,
+                 "%s: count of window %lld out of range", who, (long long)w);
+    for (int j = 0; j < n; ++j)
+        PG_CHECK(ctx, !(pool_sizes[j] > POOL_SIZE_MAX), "%s: pool size %d is beyond %.0f", who, j, POOL_SIZE_MAX);
+    std::vector<double> kc;
+    diversity_constants(pool_sizes, n, kc);
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ln = (size_t)L * n, wn = (size_t)nw * n;
+    const int nout = tajima ? 3 : 1; // theta | pi | D
+    DevBuf<int64_t> lc, win, seg;
+    DevBuf<double> pi, kcd, out;
+    DevBuf<uint8_t> flag;
+    const int nwin = reference ? 5 : 2; // head | tail | cov | seed | slot
+    if ((rc = lc.alloc(ctx, sizeof(int64_t) * (L + 1), who))) return rc;
+    if ((rc = flag.alloc(ctx, ln, who))) return rc;
+    if (tajima && (rc = pi.alloc(ctx, sizeof(double) * ln, who))) return rc;
+    if ((rc = win.alloc(ctx, sizeof(int64_t) * nwin * nw, who))) return rc;
+    if ((rc = kcd.alloc(ctx, sizeof(double) * 3 * n, who))) return rc;
+    if ((rc = out.alloc(ctx, sizeof(double) * nout * wn, who))) return rc;
+    if (seg_win && (rc = seg.alloc(ctx, sizeof(int64_t) * wn, who))) return rc;
+    const int64_t *host_win[5] = {win_head, win_tail, win_cov, win_seed, win_slot};
+    PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
+    for (int i = 0; i < nwin; ++i)
+        PG_HIP(ctx, hipMemcpyAsync(win.get() + (size_t)i * nw, host_win[i], sizeof(int64_t) * nw, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(kcd.get(), kc.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
+    const int64_t *wh = win.get(), *wt = wh + nw;
+    const int64_t *wc = reference ? wt + nw : nullptr, *wsd = reference ? wc + nw : nullptr, *wsl = reference ? wsd + nw : nullptr;
+    const dim3 lgrid((unsigned)((ln + 255) / 256)), wgrid((unsigned)((wn + 255) / 256));
+    double *theta_dev = out.get(), *pi_dev = tajima ? theta_dev + wn : nullptr, *d_dev = tajima ? pi_dev + wn : nullptr;
+    if (tajima) {
+        hipLaunchKernelGGL((k_pop_locus<false, true>), lgrid, dim3(256), 0, ctx->stream, G_dev, cov_dev, lc.get(), L, n, ld,
+                           (double *)nullptr, pi.get(), flag.get());
+        hipLaunchKernelGGL(k_diversity_windows<true>, wgrid, dim3(256), 0, ctx->stream, pi.get(), flag.get(), wh, wt, wc, wsd, wsl,
+                           nw, n, kcd.get(), seg.get(), theta_dev, pi_dev, d_dev);
+    } else {
+        hipLaunchKernelGGL(k_poly_locus, lgrid, dim3(256), 0, ctx->stream, G_dev, lc.get(), L, n, ld, flag.get());
+        hipLaunchKernelGGL(k_diversity_windows<false>, wgrid, dim3(256), 0, ctx->stream, (const double *)nullptr, flag.get(), wh, wt,
+                           wc, wsd, wsl, nw, n, kcd.get(), seg.get(), theta_dev, pi_dev, d_dev);
+    }
+    PG_HIP(ctx, hipGetLastError());
+    if (theta_win) PG_HIP(ctx, hipMemcpyAsync(theta_win, theta_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
+    if (tajima && pi_win) PG_HIP(ctx, hipMemcpyAsync(pi_win, pi_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
+    if (tajima) PG_HIP(ctx, hipMemcpyAsync(d_win, d_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
+    if (seg_win) PG_HIP(ctx, hipMemcpyAsync(seg_win, seg.get(), sizeof(int64_t) * wn, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double *vals = tajima ? d_win : theta_win;
+    double *mean = tajima ? d_mean : theta_mean;
+    for (int j = 0; j < n; ++j) { // mean_axis(Axis(0)) over the windows (watterson_theta.rs:213-215, tajima_d.rs:98): left to right
+        double s = 0.0;
+        for (int64_t w = 0; w < nw; ++w) s = s + vals[(size_t)w * n + j];
+        mean[j] = s / (double)nw;
+    }
+    return PG_OK;
+}
+
 } // namespace
 
 // define_sliding_windows (base/helpers.rs:294-403)
@@ -221,6 +386,37 @@ extern "C" int64_t pg_host_sliding_windows(const int32_t *chr, const uint64_t *p
     return no;
 }
 
+// theta_watterson's own copy of that loop (watterson_theta.rs:56-164), with what it keeps per window besides head and tail
+extern "C" int64_t pg_host_watterson_windows(const int32_t *chr, const uint64_t *pos, int64_t l, uint64_t window_size_bp,
+                                             uint64_t window_slide_size_bp, uint64_t min_loci_per_window, int64_t *out_head,
+                                             int64_t *out_tail, int64_t *out_cov, int64_t *out_seed, int64_t *out_slot) {
+    if (l <= 0 || !chr || !pos || !out_head || !out_tail || !out_cov || !out_seed || !out_slot) return 0;
+    std::vector<int64_t> head{0}, tail{0}, seed{0};
+    std::vector<uint64_t> cnt{1};
+    bool next_found = false;
+    int64_t next_head = 0;
+    for (int64_t i = 1; i < l; ++i) {
+        const int64_t h = head.back();
+        if (chr[i] != chr[h] || pos[i] > pos[h] + window_size_bp) {
+            if (next_found) i = next_head;                                                     // :89-93
+            if (cnt.back() >= min_loci_per_window) { head.push_back(i); tail.push_back(i); cnt.push_back(1); seed.push_back(i); } // :100-109
+            else { head.back() = i; cnt.back() = 1; seed.back() = (int64_t)head.size() - 1; } // polymorphic_loci_per_pool(.., i_), :113-119
+            next_found = false;
+        } else {
+            tail.back() = i;
+            cnt.back() += 1; // and polymorphic[i_] += polymorphic_loci_per_pool(.., i_): the slot's index again (:127-137)
+            if (!next_found && pos[i] >= pos[h] + window_slide_size_bp) { next_found = true; next_head = i; }
+        }
+    }
+    int64_t no = 0;
+    for (size_t w = 0; w < head.size(); ++w) // :152-164
+        if (w == 0 || tail[w] != out_tail[no - 1]) {
+            out_head[no] = head[w]; out_tail[no] = tail[w]; out_cov[no] = (int64_t)cnt[w]; out_seed[no] = seed[w]; out_slot[no] = (int64_t)w;
+            ++no;
+        }
+    return no;
+}
+
 extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                          const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                          int64_t n_windows, double *pi_win, double *pi_mean) {
@@ -240,8 +436,8 @@ extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev
     PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(ctx, hipMemcpyAsync(wh.get(), win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(ctx, hipMemcpyAsync(wt.get(), win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_pop_locus, dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, cov_dev,
-                       lc.get(), L, n, ld, q1.get(), pi.get());
+    hipLaunchKernelGGL((k_pop_locus<true, false>), dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev,
+                       cov_dev, lc.get(), L, n, ld, q1.get(), pi.get(), (uint8_t *)nullptr);
     hipLaunchKernelGGL(k_range_mean_1d, dim3((unsigned)(((size_t)n_windows * n + 255) / 256)), dim3(256), 0, ctx->stream,
                        pi.get(), wh.get(), wt.get(), n_windows, n, out.get());
     PG_HIP(ctx, hipGetLastError());
@@ -286,8 +482,8 @@ extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_de
     PG_HIP(ctx, hipMemcpyAsync(cht.get(), ct.data(), sizeof(int64_t) * nchunks, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_pop_check, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, lc.get(), L, n,
                        ld, bad.get());
-    hipLaunchKernelGGL(k_pop_locus, dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, cov_dev,
-                       lc.get(), L, n, ld, q1.get(), pi.get());
+    hipLaunchKernelGGL((k_pop_locus<true, false>), dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev,
+                       cov_dev, lc.get(), L, n, ld, q1.get(), pi.get(), (uint8_t *)nullptr);
     int hbad = 0;
     PG_HIP(ctx, hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -320,4 +516,22 @@ extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_de
     }
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PG_OK;
+}
+
+extern "C" int pg_watterson_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
+                                const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
+                                const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win,
+                                double *theta_mean, int64_t *seg_win) {
+    if (!ctx) return PG_ERR_INVALID;
+    return diversity_run(ctx, false, G_dev, nullptr, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
+                         pool_sizes, nullptr, nullptr, theta_win, theta_mean, nullptr, seg_win);
+}
+
+extern "C" int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                               const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                               const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
+                               const double *pool_sizes, double *d_win, double *d_mean, double *theta_win, double *pi_win) {
+    if (!ctx) return PG_ERR_INVALID;
+    return diversity_run(ctx, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
+                         pool_sizes, d_win, d_mean, theta_win, nullptr, pi_win, nullptr);
 }

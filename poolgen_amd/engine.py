@@ -392,6 +392,55 @@ class Engine:
                                          mean.ctypes.data, win.ctypes.data), "pg_fst_dev")
         return mean, win
 
+    def watterson_windows(self, chrom_ids, pos, window_size_bp: int, window_slide_size_bp: int, min_loci_per_window: int):
+        """theta_watterson's own window loop (popgen/watterson_theta.rs:56-164) -> (head, tail, cov, seed, slot): head/tail
+        as sliding_windows; cov, seed, slot describe the reference's segregating-site count (include/poolgen_hip.h)."""
+        ch = np.ascontiguousarray(chrom_ids, dtype=np.int32)
+        po = np.ascontiguousarray(pos, dtype=np.uint64)
+        out = [np.empty(max(len(ch), 1), dtype=np.int64) for _ in range(5)]
+        nw = self._lib.pg_host_watterson_windows(ch.ctypes.data, po.ctypes.data, len(ch), int(window_size_bp),
+                                                 int(window_slide_size_bp), int(min_loci_per_window),
+                                                 *[o.ctypes.data for o in out])
+        return tuple(o[:nw].copy() for o in out)
+
+    @staticmethod
+    def _count_args(count, nw):
+        """count = None: counted mode (three NULLs); else (cov, seed, slot) per window: the reference's count."""
+        if count is None:
+            return [None, None, None], []
+        keep = [np.ascontiguousarray(c, dtype=np.int64) for c in count]
+        if len(keep) != 3 or any(len(c) != nw for c in keep):
+            raise ValueError("count must be (cov, seed, slot), one entry per window each")
+        return [c.ctypes.data for c in keep], keep
+
+    def theta_watterson(self, G, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
+        """popgen::theta_watterson (popgen/watterson_theta.rs:36-188): (theta_W per window [n_windows x n], mean across
+        windows [n], segregating sites per window [n_windows x n]).  count = (cov, seed, slot) of watterson_windows
+        reproduces the reference's count; None counts the polymorphic loci of each window.  pool_sizes are used as given."""
+        p, ld, n, lc, wh, wt = self._popgen_args(G, G, locus_col, win_head, win_tail, n)
+        ps = _host_f64(pool_sizes)
+        assert len(ps) == n
+        cptr, keep = self._count_args(count, len(wh))
+        win = np.empty((len(wh), n)); mean = np.empty(n); seg = np.empty((len(wh), n), dtype=np.int64)
+        self._check(self._lib.pg_watterson_dev(self._ctx, self._dev(G, torch.float64), p, n, ld, lc.ctypes.data, len(lc) - 1,
+                                               wh.ctypes.data, wt.ctypes.data, *cptr, len(wh), ps.ctypes.data,
+                                               win.ctypes.data, mean.ctypes.data, seg.ctypes.data), "pg_watterson_dev")
+        return win, mean, seg
+
+    def tajima_d(self, G, cov, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
+        """popgen::tajima_d (popgen/tajima_d.rs:10-96) in one pass over G: (D per window [n_windows x n], mean across
+        windows [n], theta_W per window, pi per window).  count as for theta_watterson."""
+        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
+        ps = _host_f64(pool_sizes)
+        assert len(ps) == n
+        cptr, keep = self._count_args(count, len(wh))
+        d = np.empty((len(wh), n)); mean = np.empty(n); theta = np.empty((len(wh), n)); pi = np.empty((len(wh), n))
+        self._check(self._lib.pg_tajima_d_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
+                                              lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, *cptr, len(wh),
+                                              ps.ctypes.data, d.ctypes.data, mean.ctypes.data, theta.ctypes.data,
+                                              pi.ctypes.data), "pg_tajima_d_dev")
+        return d, mean, theta, pi
+
     # ---- genomic prediction -------------------------------------------------------------------
     def gp_xxt(self, G: torch.Tensor, n: int | None = None) -> torch.Tensor:
         p, ld, n = self._g_dims(G, n)

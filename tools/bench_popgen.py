@@ -1,5 +1,12 @@
-"""Throughput of fst / theta_pi on a resident synthetic matrix: python tools/bench_popgen.py [pools] [loci]"""
+"""Throughput of fst / theta_pi / tajima_d / theta_watterson on a resident synthetic matrix:
+    python tools/bench_popgen.py [pools] [loci] [--rounds R] [--baseline-lib other/libpoolgen_hip.so]
+Every leg is warmed up once, then the legs alternate for R rounds in this one process and the median wall time of each is
+printed (one JSON line per leg).  --baseline-lib adds a `theta_pi_baseline` leg: pg_pi_dev of another build of the library
+(e.g. the previous commit's) on the same matrix and windows, loaded beside this one."""
+import argparse
+import ctypes as C
 import json
+import statistics
 import sys
 import time
 
@@ -9,8 +16,13 @@ import torch
 sys.path.insert(0, ".")
 from poolgen_amd import Engine, Filter, synth  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-L = int(sys.argv[2]) if len(sys.argv) > 2 else 500_000
+ap = argparse.ArgumentParser()
+ap.add_argument("pools", nargs="?", type=int, default=200)
+ap.add_argument("loci", nargs="?", type=int, default=500_000)
+ap.add_argument("--rounds", type=int, default=15)
+ap.add_argument("--baseline-lib", default=None)
+args = ap.parse_args()
+n, L = args.pools, args.loci
 eng = Engine(0)
 counts = synth.sync_counts(L, n, "cuda", seed=3)
 ps = np.full(n, 20.0)
@@ -22,13 +34,39 @@ nl = len(starts) - 1
 pos = np.arange(nl, dtype=np.uint64) * 37 + 100
 chrom = (np.arange(nl) // (nl // 4 + 1)).astype(np.int32)
 wh, wt = eng.sliding_windows(chrom, pos, 37 * 400, 37 * 200, 10)      # ~400 loci per window, half-overlapping
-for name, fn in (("theta_pi", lambda: eng.theta_pi(G, cov, starts, wh, wt, n=n)), ("fst", lambda: eng.fst(G, cov, starts, wh, wt, n=n))):
+legs = [("theta_pi", lambda: eng.theta_pi(G, cov, starts, wh, wt, n=n)),
+        ("tajima_d", lambda: eng.tajima_d(G, cov, starts, wh, wt, ps, n=n)),          # counted mode
+        ("theta_watterson", lambda: eng.theta_watterson(G, starts, wh, wt, ps, n=n)),
+        ("fst", lambda: eng.fst(G, cov, starts, wh, wt, n=n))]
+if args.baseline_lib:
+    base = C.CDLL(args.baseline_lib)
+    base.pg_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
+    base.pg_pi_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    bctx = C.c_void_p()
+    assert base.pg_create(C.byref(bctx), 0, C.c_void_p(torch.cuda.current_stream(0).cuda_stream)) == 0
+    lc = np.ascontiguousarray(starts, dtype=np.int64)
+    bwin, bmean = np.empty((len(wh), n)), np.empty(n)
+
+    def baseline():
+        assert base.pg_pi_dev(bctx, G.data_ptr(), cov.data_ptr(), G.shape[0], n, G.shape[1], lc.ctypes.data, nl, wh.ctypes.data,
+                              wt.ctypes.data, len(wh), bwin.ctypes.data, bmean.ctypes.data) == 0
+        return bwin, bmean
+    legs.insert(1, ("theta_pi_baseline", baseline))
+    assert np.array_equal(baseline()[0], eng.theta_pi(G, cov, starts, wh, wt, n=n)[0])
+times = {name: [] for name, _ in legs}
+for name, fn in legs:
     fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    pairs = n * (n + 1) // 2
-    print(json.dumps({"op": name, "pools": n, "loci": nl, "columns": int(G.shape[0]), "windows": int(len(wh)), "wall_s": dt,
-                      "loci_per_s": nl / dt, "pair_locus_evals_per_s": (3 * nl * pairs / dt) if name == "fst" else None}))
+torch.cuda.synchronize()
+for _ in range(args.rounds):
+    for name, fn in legs:
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times[name].append(time.perf_counter() - t0)
+pairs = n * (n + 1) // 2
+for name, _ in legs:
+    dt = statistics.median(times[name])
+    print(json.dumps({"op": name, "pools": n, "loci": nl, "columns": int(G.shape[0]), "windows": int(len(wh)), "rounds": args.rounds,
+                      "wall_s": dt, "wall_s_min": min(times[name]), "wall_s_max": max(times[name]), "loci_per_s": nl / dt,
+                      "pair_locus_evals_per_s": (3 * nl * pairs / dt) if name == "fst" else None}))
