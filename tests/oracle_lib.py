@@ -240,8 +240,9 @@ class Oracle:
         k = Y.shape[1]
         beta, var, pv = (np.empty((p, k)) for _ in range(3))
         cptr = None
-        if covariate is not None:
-            covariate = np.ascontiguousarray(covariate, dtype=np.float64).reshape(n, -1)
+        if covariate is not None:   # (n x 0: the m = 0 fits without the kinship and its eigen-solve)
+            covariate = np.ascontiguousarray(covariate, dtype=np.float64)
+            covariate = covariate.reshape(n, covariate.size // n)
             force_m = covariate.shape[1]
             cptr = covariate.ctypes.data
         m = self.lib.orc_mle_with_covariate(G.ctypes.data, p, n, ld, Y.ctypes.data, k, float(var_explained), int(force_m), cptr,

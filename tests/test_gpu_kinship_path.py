@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import dispatch_rules as R
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10
@@ -33,10 +35,33 @@ def cmp_fit(got, ref, what=""):
     assert np.max(np.abs(pv[ok] - ref["pval"][ok])) <= PTOL, what + " pval"
 
 
+# The block rules of pg_launch_kinship (pg_kinship.hip:698-725, :812, :831) at their edges, T = ceil(n / 16) tile columns: one pool
+# block up to T = 13, where the 13-tile kernel takes over with its narrow-tile bits (3 up to 200 pools, 1 above); two weighted blocks
+# at T = 14; two merged blocks, split in two, at T = 15 and 16; three weighted blocks up to T = 24; merged from T = 25 (four blocks).
+# (p, n, ld, (T, nb, merged, split, narrow-tile bits))
+KINSHIP_EDGE_POINTS = [
+    (1500, 193, None, (13, 1, False, 1, 3)),   # first pool count of the 13-tile kernel: one pool in the last tile column
+    (1201, 200, 202, (13, 1, False, 1, 3)),    # last count with the narrow last column (n <= 200, :831); padding behind the pools
+    (1500, 201, None, (13, 1, False, 1, 1)),   # first without it
+    (1100, 208, None, (13, 1, False, 1, 1)),   # T = 13 full: the last single-block count
+    (1300, 225, None, (15, 2, True, 2, 0)),    # T = 15: first merged two-block count, split 2 (T = 14, weighted: 209 and 224 above)
+    (1201, 240, 242, (15, 2, True, 2, 0)),     # T = 15 full
+    (1500, 241, None, (16, 2, True, 2, 0)),    # T = 16: one pool in the last tile column
+    (1100, 256, 258, (16, 2, True, 2, 0)),     # T = 16 full: the last two-block count (257 above: T = 17, three weighted blocks of 6, 6, 5)
+    (1300, 384, None, (24, 3, False, 1, 0)),   # T = 24: the last three-block count, weighted blocks of 8
+    (1201, 400, None, (25, 4, True, 1, 0)),    # T = 25: merged four blocks (385 above is its first count)
+]
+for _p, _n, _ld, _want in KINSHIP_EDGE_POINTS:
+    _k = R.kin_layout(_n)
+    assert (_k["T"], _k["nb"], _k["merged"], _k["split"], _k["small"]) == _want and _k["weighted"] == (not _k["merged"] and _k["nb"] > 1), _n
+assert [R.kin_layout(n)["nb"] for n in (209, 224, 257, 385)] == [2, 2, 3, 4] and not R.kin_layout(224)["merged"]
+
+
 @pytest.mark.parametrize("p,n,ld", [(3000, 200, None), (777, 100, None), (513, 5, None), (100, 37, 38),
                                     (64, 16, 16), (1, 8, 8), (1000, 250, None), (300, 209, 210),
                                     (700, 500, None), (333, 401, 402), (257, 385, 386), (200, 640, None),
-                                    (20011, 300, None), (9001, 224, None), (1030, 360, 362), (40000, 257, 258)])   # 2-3 pool blocks: weighted pairs
+                                    (20011, 300, None), (9001, 224, None), (1030, 360, 362), (40000, 257, 258)]   # 2-3 pool blocks: weighted pairs
+                         + [pt[:3] for pt in KINSHIP_EDGE_POINTS])
 def test_kinship_matches_oracle(engine, oracle, p, n, ld):
     G, _ = make(p, n, 11, ld=ld)
     S = engine.kinship_partial(G, n).cpu().numpy()
@@ -580,8 +605,10 @@ def test_gp_penalised_family_matches_oracle(engine, oracle, exact, n, p, k, alph
 
 @pytest.mark.parametrize("n,p,k,n_folds", [(80, 1500, 2, 10), (40, 900, 2, 10), (120, 2500, 1, 16), (300, 4000, 1, 10)])
 def test_gp_ridge_many_fold_columns(engine, oracle, n, p, k, n_folds):
-    """More fold x trait columns than one MFMA tile holds (20 -> the 24-column VALU forms, Z in LDS or in the scalar
-    cache), exactly 16, and the 10-column MFMA form at a pool count with a ragged last chunk."""
+    """Fold x trait columns of 20, 16 and 10 per repetition with n_reps = 2: the batched passes (pg_gp.hip:874, :894-916) form them
+    at most 16 per pass over G, whatever repetition they belong to (2 x 20 + 2 = 42 columns: 16 + 16 + 10; 33: 16 + 16 + 1; 21: 10 + 11), each pass
+    in the matrix-core products mode at these pool counts.  More than 16 columns in ONE pass (the 24- and 34-column forms) need
+    n_reps = 1: tests/test_gpu_dispatch_edges_gp.py, which also runs the first two shapes that way."""
     G, Y = make(p, n, 91)
     Y = np.hstack([Y, Y[:, :1] * 0.3 - 1.0])[:, :k]
     rng = np.random.default_rng(13)
@@ -660,7 +687,22 @@ def test_gp_ridge_path_matches_oracle(engine, oracle, n, p, k, alpha, n_reps):
     assert np.array_equal(lam4, lam) and np.array_equal(perf4, perf) and np.array_equal(beta4.cpu().numpy(), b)
 
 
-@pytest.mark.parametrize("p,n,k", [(6000, 200, 2), (5000, 200, 3), (3000, 33, 1), (2000, 100, 2), (4000, 208, 1), (1500, 193, 1)])
+# The fused intercept-only sums ride in the kinship pass only with one pool block (pg_kinship.hip:799: up to 208 pools) and at most two
+# traits; pg_set_phenotypes keeps no phenotypes at all above 256 pools (:883).  (p, n, k, fused)
+FUSED_EDGE_POINTS = [
+    (1500, 200, 1, True),     # the 13-tile kernel with the narrow last column, fused
+    (1500, 201, 2, True),     # ... without it, two traits
+    (1500, 209, 1, False),    # two pool blocks: no fused sums (:799)
+    (1500, 256, 2, False),    # the last pool count whose phenotypes are kept (:883); two merged blocks: not fused
+    (1500, 257, 1, False),    # phenotypes not kept: the regular two-pass path
+]
+for _p, _n, _k, _fused in FUSED_EDGE_POINTS:
+    assert R.kin_fuses(_n, _k) == _fused, _n
+assert R.kin_fuses(208, 2) and not R.kin_fuses(208, 3)
+
+
+@pytest.mark.parametrize("p,n,k", [(6000, 200, 2), (5000, 200, 3), (3000, 33, 1), (2000, 100, 2), (4000, 208, 1), (1500, 193, 1)]
+                         + [pt[:3] for pt in FUSED_EDGE_POINTS])
 def test_fused_and_two_pass_paths_agree_with_oracle(engine, oracle, p, n, k):
     """m = 0 through the fused kinship pass (k <= 2) or the two-pass path (k = 3), generic and 13-tile
     kernels, odd n: same answers as the oracle, and as each other."""
