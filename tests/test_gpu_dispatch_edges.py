@@ -85,6 +85,29 @@ def test_count_operators_across_pool_count_rules(engine, oracle, n, dirty, ols_k
     check_chisq(engine.chisq(counts, ps, f), rows, ps, fo, oracle)
 
 
+def check_loader(engine, oracle, counts, host, ps, f, fo, keep_p_minus_1=False):
+    """load_frequencies against filter_locus / to_frequencies (/ sort_by_allele_freq, the major allele dropped): the set of columns,
+    their loci and alleles and every frequency bit-exact.  Returns (columns, col_locus, col_allele)."""
+    n = host.shape[1]
+    G, col_locus, col_allele = (x.cpu().numpy() for x in engine.load_frequencies(counts, ps, f, keep_p_minus_1=keep_p_minus_1))
+    want_cols, want_loc, want_al = [], [], []
+    for l in range(host.shape[0]):
+        res = oracle.filter_locus(host[l], ps, fo)
+        if res is None:
+            continue
+        ids, fc = res
+        fr = oracle.to_frequencies(fc)
+        if keep_p_minus_1:
+            fr, ids = oracle.sort_by_allele_freq(fr, ids, True)
+            fr, ids = fr[:, 1:], ids[1:]
+        for j, a in enumerate(ids):
+            want_cols.append(fr[:, j]); want_loc.append(l); want_al.append(int(a))
+    assert len(want_cols) == G.shape[0]
+    assert col_locus.tolist() == want_loc and col_allele.tolist() == want_al
+    assert np.array_equal(G[:, :n], np.stack(want_cols), equal_nan=True)
+    return len(want_cols), col_locus, col_allele
+
+
 @pytest.mark.parametrize("n", [31, 50, 113, 226, 449, 450])
 def test_loader_across_pool_count_rules(engine, oracle, n):
     """load_frequencies shares launch_passes (streaming period, staging, second pass) with the count operators."""
@@ -95,19 +118,7 @@ def test_loader_across_pool_count_rules(engine, oracle, n):
     ps = np.linspace(10, 30, n)
     f, fo = flt_pair(oracle, maf=0.01)
     host = counts.cpu().numpy().astype(np.uint64)
-    G, col_locus, col_allele = (x.cpu().numpy() for x in engine.load_frequencies(counts, ps, f))
-    want_cols, want_loc, want_al = [], [], []
-    for l in range(L):
-        res = oracle.filter_locus(host[l], ps, fo)
-        if res is None:
-            continue
-        ids, fc = res
-        fr = oracle.to_frequencies(fc)
-        for j, a in enumerate(ids):
-            want_cols.append(fr[:, j]); want_loc.append(l); want_al.append(int(a))
-    assert len(want_cols) == G.shape[0] > L
-    assert col_locus.tolist() == want_loc and col_allele.tolist() == want_al
-    assert np.array_equal(G[:, :n], np.stack(want_cols), equal_nan=True)
+    assert check_loader(engine, oracle, counts, host, ps, f, fo)[0] > L
 
 
 def test_pool_table_top_edge(engine, oracle):
