@@ -66,13 +66,13 @@ int pg_synchronize(pg_ctx *ctx);
 /* Per-kernel HIP-event timing (used by bench.py for the roofline record). */
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
-                    PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_COUNT = 12 };
+                    PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_COUNT = 13 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
 int pg_profile_get(pg_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
 /* Diagnostics of the last batch operator call (pg_ols_iter_batch[_dev], pg_pearson_batch[_dev], pg_chisq_batch[_dev],
- * pg_fisher_batch[_dev], pg_load_plan_dev) on this context: *loci = L of that call, *listed = the loci its streaming pass could not close in place
+ * pg_fisher_batch[_dev], pg_gwalpha_batch[_dev], pg_load_plan_dev) on this context: *loci = L of that call, *listed = the loci its streaming pass could not close in place
  * and handed to the second pass (three or more surviving alleles, or a speculated allele pair that did not hold; summed
  * over the launch groups of a multi-trait call).  Either pointer may be NULL. */
 int pg_locus_op_stats(const pg_ctx *ctx, int64_t *loci, int64_t *listed);
@@ -257,6 +257,36 @@ int pg_chisq_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const 
 int pg_fisher_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const double *pool_sizes,
                     const pg_filter *filter, int32_t *n_out, int32_t *allele_ids, double *p_observed,
                     double *pval);
+
+/* gwas::gwalpha_ls / gwalpha_ml (gwas/gwalpha.rs:281-380; CLI main.rs:335-356): per locus filter -> to_frequencies ->
+ * sort_by_allele_freq(decreasing) -> drop the first allele (:176-196); per kept allele (= row = slot) two Beta distributions are
+ * fitted to the cumulative allele distribution over the phenotype-ranked pools (:227-279) by Nelder-Mead (argmin 0.8 as
+ * pg_mle_kinship_dev words it, start simplex prepare_solver_neldermead(4, 1), <= 1000 iterations) on the four logit-bounded
+ * shapes in [EPSILON, 10], cost = least squares (:11-41) or -log10 likelihood (:43-79), and
+ *   alpha = 2 sqrt(p_a (1 - p_a)) (mu_A - mu_B) / sig,  mu = min + (max - min) s0 / (s0 + s1)      (:314-316).
+ * bins (host, n): the pools' shares; they are also the pool sizes the filter sees (main.rs:210, phen.rs:157).  q (host, n):
+ * column 1 of the reference's phenotype matrix AS HANDED OVER (the gwalpha_fmt parser has normalised it once already,
+ * phen.rs:139-142); the operator applies q'_0 = 0, q'_i = (q_i - min) / (max - min) to it as written (:248-251).  n >= 3
+ * (the reference's phenotype matrix does not match the counts below that and check() panics): PG_ERR_INVALID otherwise.
+ * Outputs slot-major as above: n_out[L], allele_ids / mean_freq / alpha [5*L]; optional (NULL = not wanted) what makes a fit
+ * checkable: shapes[(r*L + l)*4 + c] the fit's final bounded shapes (A: c = 0, 1; B: c = 2, 3), cost[r*L + l] its lowest cost,
+ * iters[r*L + l] the iterations done (1000 = the cap ended it).
+ * A row whose p_a = sum_i f_i bins_i is 0, 1 or NaN has no defined cost in the reference (bins_a or bins_b are 0/0; statrs
+ * panics on the NaN percentile): alpha, shapes and cost are NaN and iters 0 there.  Such a row needs --min-allele-frequency 0
+ * (an allele nobody carries survives) or a pool without reads under a filter that lets it pass (min_coverage_depth 0 and
+ * max_missingness_rate > 0).
+ * A row's result depends on its counts, the filter, bins, q, sig, min, max, method and n only -- not on the batch. */
+enum { PG_GWALPHA_LS = 0, PG_GWALPHA_ML = 1 };
+int pg_gwalpha_batch_dev(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const double *bins, const double *q,
+                         double sig, double min, double max, const pg_filter *filter, int method, int32_t *n_out_dev,
+                         int32_t *allele_ids_dev, double *mean_freq_dev, double *alpha_dev, double *shapes_dev,
+                         double *cost_dev, int32_t *iters_dev);
+int pg_gwalpha_batch(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const double *bins, const double *q, double sig,
+                     double min, double max, const pg_filter *filter, int method, int32_t *n_out, int32_t *allele_ids,
+                     double *mean_freq, double *alpha, double *shapes, double *cost, int32_t *iters);
+/* out[i] = Beta(a[i], b[i]).cdf(x[i]) as the fit evaluates it: 0 for x <= 0, 1 for x >= 1, else statrs' beta_reg (modified
+ * Lentz continued fraction, <= 140 iterations, symmetry switch at (a + 1) / (a + b + 2)); NaN for a or b not > 0 or a NaN x. */
+int pg_beta_reg_dev(pg_ctx *ctx, const double *a_dev, const double *b_dev, const double *x_dev, int64_t count, double *out_dev);
 
 /* ---------------------------------------------------------------------------------------
  * Genomic prediction: gp::ols (gp/ols.rs:8-101) for the n < p case, b = X^T pinv(X X^T) y,

@@ -69,6 +69,9 @@ SIGNATURES = {
     "pg_pearson_batch": (_i, _batch),
     "pg_chisq_batch": (_i, [_vp, _vp, _i64, _i, _vp, _pf, _vp, _vp, _vp, _vp]),
     "pg_fisher_batch": (_i, [_vp, _vp, _i64, _i, _vp, _pf, _vp, _vp, _vp, _vp]),
+    "pg_gwalpha_batch_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _d, _d, _d, _pf, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_gwalpha_batch": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _d, _d, _d, _pf, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_beta_reg_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "pg_gp_xxt_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp]),
     "pg_gp_ols_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i, _vp, _i, _vp, _vp]),
     "pg_gp_ridge_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i, _vp, _i, _vp, _i, _i, _d, _d, _vp, _vp, _vp]),
@@ -91,7 +94,8 @@ SIGNATURES = {
 }
 
 KERNEL_IDS = {"kinship": 0, "kinship_reduce": 1, "sweep": 2, "ols_iter": 3, "pearson": 4,
-              "chisq": 5, "gp_xxt": 6, "gp_beta": 7, "sweep_finish": 8, "allreduce": 9, "gp_predict": 10, "fisher": 11}
+              "chisq": 5, "gp_xxt": 6, "gp_beta": 7, "sweep_finish": 8, "allreduce": 9, "gp_predict": 10, "fisher": 11,
+              "gwalpha": 12}
 
 
 def load_library():

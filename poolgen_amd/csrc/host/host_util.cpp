@@ -182,6 +182,64 @@ Phen parse_phen(const std::string &fname, const std::string &delim, int name_col
     return ph;
 }
 
+Phen parse_phen_gwalpha(const std::string &fname) {
+    std::ifstream in(fname);
+    if (!in) throw std::runtime_error("Input phenotype file not found: " + fname);
+    std::vector<std::string> lines;
+    std::string line;
+    while (std::getline(in, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        lines.push_back(line);
+    }
+    const char *missing = "T_T Phenotype file in GWAlpha format is missing some lines, e.g. Pheno_name, sig, MIN, MAX, perc and/or q.";
+    if (lines.size() < 6) throw std::runtime_error(missing);
+    auto rhs = [&](int i, bool brackets) { // all_lines[i].split("=")[1] with ';' (and the brackets) removed, trimmed
+        const std::vector<std::string> v = split(lines[i], "=");
+        if (v.size() < 2) throw std::runtime_error(missing);
+        std::string t;
+        for (char c : v[1])
+            if (c != ';' && !(brackets && (c == '[' || c == ']'))) t.push_back(c);
+        return trim(t);
+    };
+    auto number = [&](int i, const char *what) {
+        double x = 0.0;
+        if (!parse_f64_strict(rhs(i, false), x))
+            throw std::runtime_error(std::string("T_T Error parsing the ") + what + " as f64 in the GWAlpha formatted phenotype file.");
+        return x;
+    };
+    auto numbers = [&](int i, const char *what) {
+        std::vector<double> out;
+        for (const std::string &t : split(rhs(i, true), ",")) {
+            double x = 0.0;
+            if (!parse_f64_strict(trim(t), x))
+                throw std::runtime_error(std::string("T_T Error parsing the ") + what + " as f64 in the GWAlpha formatted phenotype file.");
+            out.push_back(x);
+        }
+        return out;
+    };
+    (void)rhs(0, false); // the name is read and dropped (:111-114)
+    const double sig = number(1, "standard deviation of the trait"), mn = number(2, "minimum value of the trait"),
+                 mx = number(3, "maximum value of the trait");
+    const std::vector<double> perc = numbers(4, "pool percentiles"), q = numbers(5, "pool quantiles");
+    Phen ph;
+    ph.n = (int)perc.size() + 1;
+    ph.k = 3;
+    for (int i = 0; i < ph.n; ++i) ph.pool_sizes.push_back((i < ph.n - 1 ? perc[i] : 1.0) - (i > 0 ? perc[i - 1] : 0.0)); // perc0 - perc1
+    ph.pool_sizes_as_written = ph.pool_sizes;
+    const int rows = ph.n < 3 ? 3 : ph.n;
+    if ((int)q.size() + 1 > rows) throw std::runtime_error("GWAlpha formatted phenotype file: more quantiles (q) than pools");
+    std::vector<double> q_prime(rows, 0.0);
+    for (size_t i = 0; i < q.size(); ++i) q_prime[i + 1] = (q[i] - mn) / (mx - mn); // :139-142
+    const double third[3] = {sig, mn, mx};
+    for (int i = 0; i < ph.n; ++i) {
+        ph.phen.push_back(ph.pool_sizes[i]);
+        ph.phen.push_back(q_prime[i]);
+        ph.phen.push_back(i < 3 ? third[i] : -INFINITY);
+    }
+    for (int i = 0; i < rows; ++i) ph.pool_names.push_back("pool-" + std::to_string(i));
+    return ph;
+}
+
 // ---- sync parsing -----------------------------------------------------------------------------
 SyncBatch &SyncBatch::operator=(SyncBatch &&o) noexcept {
     if (this != &o) {

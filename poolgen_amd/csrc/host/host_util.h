@@ -35,6 +35,11 @@ struct Phen {
 };
 Phen parse_phen(const std::string &fname, const std::string &delim, int name_col, int size_col,
                 const std::vector<int> &value_cols);
+// --phen-format gwalpha_fmt: the GWAlpha.py phenotype file (phen.rs:99-159) -- six lines Pheno_name=, sig=, MIN=, MAX=, perc=[..],
+// q=[..], each split at '=' with ';' (and '[', ']') stripped.  n = the number of bins = diff of [0, perc.., 1]; pool_sizes = the
+// bins as they are (:157); phen = the reference's n x 3 matrix: column 0 the bins, column 1 q' = (0, (q_i - MIN) / (MAX - MIN)..),
+// column 2 sig, MIN, MAX in rows 0..2 and -inf below; pool names "pool-i", max(n, 3) of them as the reference makes them.
+Phen parse_phen_gwalpha(const std::string &fname);
 
 // ---- sync ---------------------------------------------------------------------------------------
 // Counts of a whole sync file, locus-major: L x n x 6 u32, columns A,T,C,G,N,D in the READER's order

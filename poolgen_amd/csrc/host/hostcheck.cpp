@@ -2,6 +2,7 @@
 //   hostcheck fmt                      : stdin "x n_digits" per line -> "display(x) roundup_own(x,n)"
 //   hostcheck phen <file> <delim> <name_col> <size_col> <c1,c2,..>
 //   hostcheck parse <sync> <threads>   : "L n" then one line per locus: chrom pos counts[n*6]
+//   hostcheck gwalpha_phen <file>      : "n sig MIN MAX", the pool names, then "bin q'" per pool (the gwalpha_fmt parser)
 #include "host_util.h"
 #include "pileup.h"
 #include "rank_gate.h"
@@ -67,6 +68,16 @@ int main(int argc, char **argv) {
                 for (int j = 0; j < ph.k; ++j) std::cout << " " << rust_display(ph.phen[(size_t)i * ph.k + j]);
                 std::cout << "\n";
             }
+        } else if (mode == "gwalpha_phen") {
+            if (argc < 3) return 2;
+            const Phen ph = parse_phen_gwalpha(argv[2]);
+            std::cout << ph.n;
+            for (int j = 0; j < 3; ++j) std::cout << " " << (j < ph.n ? rust_display(ph.phen[(size_t)j * 3 + 2]) : std::string("-"));
+            std::cout << "\n";
+            for (size_t i = 0; i < ph.pool_names.size(); ++i) std::cout << (i ? " " : "") << ph.pool_names[i];
+            std::cout << "\n";
+            for (int i = 0; i < ph.n; ++i)
+                std::cout << rust_display(ph.pool_sizes[i]) << " " << rust_display(ph.phen[(size_t)i * 3 + 1]) << "\n";
         } else if (mode == "parse") {
             // hostcheck parse <sync> <threads> [16]: "16" asks for 16-bit counts; the first line then ends with the width in use
             const bool want16 = argc > 4 && std::string(argv[4]) == "16";

@@ -38,7 +38,7 @@
 using namespace pgh;
 
 struct Args {
-    std::string analysis, fname, output, phen_fname, phen_delim = ",";
+    std::string analysis, fname, output, phen_fname, phen_delim = ",", phen_format = "default", gwalpha_method = "ML";
     double max_base_error_rate = 0.01, min_coverage_breadth = 1.0, min_allele_frequency = 0.001,
            max_missingness_rate = 0.0, xxt = 0.75;
     uint64_t min_coverage_depth = 1;
@@ -80,7 +80,7 @@ static int flag_int(const std::string &v, const std::string &flag, int64_t lo = 
 
 static const char *USAGE =
     "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
-    "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship,\n"
+    "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
     "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d\n"
     "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
     "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
@@ -89,6 +89,8 @@ static const char *USAGE =
     "  -p, --phen-fname <file>            delimited file: pool name, pool size, trait value(s)\n"
     "  -o, --output <file>                must not exist; default: derived from the input name and the time\n"
     "      --phen-delim <,>  --phen-name-col <0>  --phen-pool-size-col <1>  --phen-value-col <2[,3..]>\n"
+    "      --phen-format <default|gwalpha_fmt>   gwalpha_fmt: the GWAlpha.py file (Pheno_name=, sig=, MIN=, MAX=, perc=[..], q=[..]); gwalpha needs it\n"
+    "      --gwalpha-method <ML|LS>        gwalpha: maximum likelihood (the default, and what any other value means) or least squares\n"
     "      --max-base-error-rate <0.01>  --min-coverage-depth <1>  --min-coverage-breadth <1.0>\n"
     "      --min-allele-frequency <0.001>  --max-missingness-rate <0.0>  --keep-ns  --keep-lowercase-reference\n"
     "      --keep-p-minus-1                drop the major allele of every locus when loading the matrix\n"
@@ -101,7 +103,7 @@ static const char *USAGE =
     "                                      its count, which looks the flag up at the window's index instead of the locus\n"
     "      --n-threads <1>                 parser / writer threads\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
-    "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship: one contiguous\n"
+    "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
     "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
     "                                      all-reduced over the GPUs with RCCL; the kinship path then needs an input sorted by\n"
     "                                      (chromosome, position)\n"
@@ -126,6 +128,8 @@ static Args parse_args(int argc, char **argv) {
         else if (k == "-o" || k == "--output") a.output = val();
         else if (k == "-p" || k == "--phen-fname") a.phen_fname = val();
         else if (k == "--phen-delim") a.phen_delim = val();
+        else if (k == "--phen-format") a.phen_format = val();
+        else if (k == "--gwalpha-method") a.gwalpha_method = val();
         else if (k == "--phen-name-col") a.phen_name_col = flag_int(val(), k);
         else if (k == "--phen-pool-size-col") a.phen_pool_size_col = flag_int(val(), k);
         else if (k == "--phen-value-col") {
@@ -654,7 +658,7 @@ static int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &l
     return done_ok();
 }
 
-// fisher_exact_test / chisq_test / pearson_corr / ols_iter (main.rs:245-271): the per-locus operators know nothing beyond their own line, so
+// fisher_exact_test / chisq_test / pearson_corr / ols_iter / gwalpha (main.rs:245-271, :335-356): the per-locus operators know nothing beyond their own line, so
 // the file is taken in pieces whatever its size -- the worker threads parse piece c + 1 into one of two pinned buffers
 // (16-bit counts when they fit) while the GPU takes piece c and its rows are formatted and appended, in file order
 // (sync.rs:927-946).  Nothing of the size of the input is ever allocated, pinned or copied in one go.
@@ -665,7 +669,12 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
     const std::vector<size_t> cuts = mf.cuts(std::max<size_t>((size_t)R, (mf.size() + chunk_bytes - 1) / chunk_bytes));
     const int nchunks = (int)cuts.size() - 1;
     const std::vector<int> first = deal_pieces(nchunks, R);
-    const int n = ph.n, k = ph.k;
+    // gwalpha: one statistic per row, no p-value; its phenotype matrix carries (bins, q', [sig, MIN, MAX]) instead of traits
+    const bool gwa = op == Analysis::gwalpha;
+    const int n = ph.n, k = gwa ? 1 : ph.k;
+    std::vector<double> gw_q(gwa ? n : 0);
+    for (int i = 0; gwa && i < n; ++i) gw_q[i] = ph.phen[(size_t)i * 3 + 1];
+    const int gw_method = a.gwalpha_method == "LS" ? PG_GWALPHA_LS : PG_GWALPHA_ML; // main.rs:337-356: anything but LS is ML
     std::string out = a.output;
     if (out.empty()) out = basename_no_ext(a.fname) + "-" + unix_time_string() + "-" + a.analysis + ".csv"; // sync.rs:903
     { FILE *t = create_new(out); fclose(t); ::unlink(out.c_str()); } // probe, as the reference does before any work (sync.rs:906)
@@ -737,7 +746,10 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
                 hip_ok(hipMemcpy(counts_dev.get(), counts2.data(), sizeof(uint32_t) * counts2.size(), hipMemcpyHostToDevice), "H2D counts");
             } else
                 upload(gpu, sb, counts_dev.get());
-            if (op == Analysis::fisher_exact_test)
+            if (gwa) // sig, MIN, MAX: rows 0..2 of the matrix' third column (gwalpha.rs:214-216)
+                gpu.ok(pg_gwalpha_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), gw_q.data(), ph.phen[2], ph.phen[5], ph.phen[8], &flt, gw_method,
+                                            n_out_dev.get(), ids_dev.get(), mf_dev.get(), stat_dev.get(), nullptr, nullptr, nullptr), "gwalpha");
+            else if (op == Analysis::fisher_exact_test)
                 gpu.ok(pg_fisher_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, n_out_dev.get(), ids_dev.get(), stat_dev.get(), pv_dev.get()),
                        "fisher_exact_test");
             else if (op == Analysis::chisq_test)
@@ -760,7 +772,7 @@ static int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap
             hip_ok(hipMemcpy(ids.data(), ids_dev.get(), sizeof(int32_t) * L * used, hipMemcpyDeviceToHost), "D2H results");
             if (!tables) hip_ok(hipMemcpy(mfq.data(), mf_dev.get(), sizeof(double) * L * used, hipMemcpyDeviceToHost), "D2H results");
             hip_ok(hipMemcpy(stat.data(), stat_dev.get(), sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
-            hip_ok(hipMemcpy(pv.data(), pv_dev.get(), sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
+            if (!gwa) hip_ok(hipMemcpy(pv.data(), pv_dev.get(), sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
             if (!fo) {
                 fo = create_new(part[r]);
                 if (R == 1) fputs(header, fo);
@@ -1025,7 +1037,7 @@ static int run(int argc, char **argv) {
     Lap lap;
     const std::map<std::string, Analysis> known{
         {"chisq_test", Analysis::chisq_test}, {"pearson_corr", Analysis::pearson_corr}, {"ols_iter", Analysis::ols_iter},
-        {"fisher_exact_test", Analysis::fisher_exact_test}, {"ols_iter_with_kinship", Analysis::ols_iter_with_kinship},
+        {"fisher_exact_test", Analysis::fisher_exact_test}, {"gwalpha", Analysis::gwalpha}, {"ols_iter_with_kinship", Analysis::ols_iter_with_kinship},
         {"mle_iter_with_kinship", Analysis::mle_iter_with_kinship},
         {"genomic_prediction_cross_validation", Analysis::genomic_prediction_cross_validation}, {"fst", Analysis::fst},
         {"heterozygosity", Analysis::heterozygosity}, {"watterson_estimator", Analysis::watterson_estimator},
@@ -1033,14 +1045,26 @@ static int run(int argc, char **argv) {
     const auto found = known.find(a.analysis);
     if (found == known.end())
         throw std::runtime_error("Invalid analysis utility for this build: `" + a.analysis +
-                                 "` (available: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, ols_iter_with_kinship, "
+                                 "` (available: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship, "
                                  "mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d)");
     const Analysis analysis = found->second;
     if (a.popgen_as_documented && analysis != Analysis::watterson_estimator && analysis != Analysis::tajima_d)
         throw std::runtime_error("--popgen-as-documented applies to watterson_estimator and tajima_d");
     if (a.generate_plots || a.sig_only)
         throw std::runtime_error("--generate-plots / --output-sig-snps-only call the reference's python scripts and are out of scope here");
-    Phen ph = parse_phen(a.phen_fname, a.phen_delim, a.phen_name_col, a.phen_pool_size_col, a.phen_value_col);
+    if (a.phen_format != "default" && a.phen_format != "gwalpha_fmt")
+        throw std::runtime_error("Invalid phenotype format. Please select: 'default' or 'gwalpha_fmt'"); // phen.rs:161-164
+    const bool gwalpha_fmt = a.phen_format == "gwalpha_fmt";
+    if (analysis == Analysis::gwalpha && !gwalpha_fmt)
+        throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "
+                                 "(Pheno_name=, sig=, MIN=, MAX=, perc=[..], q=[..])");
+    if (gwalpha_fmt && analysis != Analysis::gwalpha && analysis != Analysis::pileup2sync)
+        throw std::runtime_error("--phen-format gwalpha_fmt is read by gwalpha and pileup2sync; `" + a.analysis + "` needs the default phenotype file");
+    Phen ph = gwalpha_fmt ? parse_phen_gwalpha(a.phen_fname)
+                          : parse_phen(a.phen_fname, a.phen_delim, a.phen_name_col, a.phen_pool_size_col, a.phen_value_col);
+    if (analysis == Analysis::gwalpha && ph.n < 3) // the reference's check() panics: its matrix has 3 rows, the counts fewer
+        throw std::runtime_error("gwalpha needs at least 3 pools; the phenotype file describes " + std::to_string(ph.n));
+    if (gwalpha_fmt) ph.pool_names.resize(ph.n); // (the reference names max(n, 3) pools; fewer than 3 are refused by the operator)
     const PileupFilter pf = pileup_filter(a, ph.pool_sizes);
     // the counts are parsed straight into pinned memory: the copy to the device needs no staging pass
     SyncAlloc pinned;
@@ -1056,7 +1080,7 @@ static int run(int argc, char **argv) {
         return done_ok();
     }
     if (a.n_gpus > 0 && !per_locus(analysis) && analysis != Analysis::ols_iter_with_kinship)
-        throw std::runtime_error("--n-gpus applies to fisher_exact_test, chisq_test, pearson_corr, ols_iter and ols_iter_with_kinship; `" + a.analysis + "` runs on one GPU");
+        throw std::runtime_error("--n-gpus applies to fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha and ols_iter_with_kinship; `" + a.analysis + "` runs on one GPU");
     const RankSetup ranks = rank_setup(a, analysis == Analysis::ols_iter_with_kinship);
     Ctx gpu(ranks.devices[0]); // first: the pinned allocator below needs a HIP context
     lap("start-up");

@@ -25,6 +25,17 @@ void format_locus_rows(Analysis op, const std::string &chromosome, uint64_t posi
         append_rust_display(line, pval[0]); line.push_back('\n');
         return;
     }
+    if (op == Analysis::gwalpha) { // gwalpha.rs:318-326
+        for (int i = 0; i < n_out; ++i) {
+            line += chromosome; line.push_back(','); line += std::to_string(position); line.push_back(',');
+            line.push_back(ALLELES[ids[i * S]]); line.push_back(',');
+            append_roundup_own(line, mean_freq[i * S], 6);
+            line += ",Pheno_0,";
+            append_roundup_own(line, stat[i * S], 6);
+            line += ",Unknown\n";
+        }
+        return;
+    }
     for (int i = 0; i < n_out; ++i)
         for (int j = 0; j < k; ++j) {
             const size_t e = (size_t)i * S * k + j;

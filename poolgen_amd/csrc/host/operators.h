@@ -37,19 +37,19 @@ struct LocusCountsAndPhenotypes { // structs_and_traits.rs:131-136
     std::vector<std::string> pool_names;
 };
 
-// What the CLI can be asked for (main.rs:26-143); the first four are the per-locus operators.
+// What the CLI can be asked for (main.rs:26-143); the first five are the per-locus operators.
 enum class Analysis {
-    chisq_test, pearson_corr, ols_iter, fisher_exact_test,
+    chisq_test, pearson_corr, ols_iter, fisher_exact_test, gwalpha,
     ols_iter_with_kinship, mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d,
     pileup2sync
 };
-inline bool per_locus(Analysis a) { return a <= Analysis::fisher_exact_test; }
+inline bool per_locus(Analysis a) { return a <= Analysis::gwalpha; }
 inline bool popgen(Analysis a) { return a >= Analysis::fst && a <= Analysis::tajima_d; } // all pools, coverages, windows (main.rs:427-485)
 inline bool counts_only(Analysis a) { return a == Analysis::chisq_test || a == Analysis::fisher_exact_test; } // one row per locus, no phenotype used
 
 // Formats the rows of one locus exactly as the reference's operators do; shared with the CLI's writer.
 // chisq_test: tables/chisq_test.rs:37-45, pearson_corr: gwas/correlation_test.rs:113-127, ols_iter: gwas/ols.rs:255-275,
-// fisher_exact_test: tables/fisher_exact_test.rs:119-129.  n_out <= 0 appends nothing.  The pointers are those of the locus' slot 0 in the
+// fisher_exact_test: tables/fisher_exact_test.rs:119-129, gwalpha: gwas/gwalpha.rs:318-326 (stat = alpha, k = 1, no p-value: "Unknown").  n_out <= 0 appends nothing.  The pointers are those of the locus' slot 0 in the
 // library's slot-major arrays (include/poolgen_hip.h), slot_stride = the L of the call that filled them (1 for a single locus).
 void format_locus_rows(Analysis op, const std::string &chromosome, uint64_t position, int n_out, const int32_t *ids, const double *mean_freq,
                        const double *stat, const double *pval, int k, std::string &out, size_t slot_stride = 1);

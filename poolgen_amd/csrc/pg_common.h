@@ -147,6 +147,15 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
                     double *out_dev, int colmajor = 0, double *ss_out_dev = nullptr); // out p x ncol, or ncol x p when colmajor; ss: g'g per row
 int pg_pinv_solve_sym(const double *A, int n, const double *B, int k, double *X); // pinv(A) B, Cholesky when A is safely SPD
 
+// The loader's filter pass for operators that live in other translation units (pg_locus_ops.hip): one header word per locus at
+// (*flags)[l] -- bit 0 alive, bits 1..6 the surviving alleles, PG_HDR_NK_SHIFT.. +3 their number, from PG_HDR_ORD_SHIFT three bits
+// per surviving allele in column order (sort_desc = 0) or by decreasing frequency (sort_desc = 1).  `tail_bytes` of the context's
+// workspace behind the pass' own are the caller's, 16-byte aligned at *tail; *listed = loci the second pass took.
+constexpr int PG_HDR_ALIVE = 1, PG_HDR_NK_SHIFT = 8, PG_HDR_ORD_SHIFT = 11;
+int pg_filter_headers(pg_ctx *ctx, const char *who, int kid, bool args_ok, const uint32_t *counts_dev, int64_t L, int n,
+                      const double *pool_sizes, const pg_filter *flt, int sort_desc, size_t tail_bytes, const int32_t **flags,
+                      int64_t *listed, char **tail);
+
 // launchers (defined in the .hip files)
 int pg_launch_kinship(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, double *S,
                       bool add_intercept, int kid, bool allow_fuse = false);

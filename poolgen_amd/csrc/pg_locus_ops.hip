@@ -198,7 +198,7 @@ __device__ __forceinline__ int64_t unit_slot(int64_t l, int pshift) {
 __device__ __forceinline__ size_t rec_base(int64_t slot) {
     return (size_t)(slot >> 6) * (size_t)(REC_DOUBLES * 64) + (size_t)(slot & 63);
 }
-constexpr int FLAG_ALIVE = 1, FLAG_SECOND = 1 << 7; // bits 1..6: surviving alleles
+constexpr int FLAG_ALIVE = PG_HDR_ALIVE, FLAG_SECOND = 1 << 7; // bits 1..6: surviving alleles
 
 // The operator's running sums of one locus over the alleles "in play" (NJ of them; allele id of slot
 // jj is aj(jj)).  Everything is accumulated sequentially in pool order.
@@ -292,7 +292,7 @@ struct Sums {
 //   chisq    : chi2 = total * (sum_j A_j / cs_j - 1)   (tables/chisq_test.rs:15-31 regrouped)
 // A biallelic ols_iter locus with one trait is 3 doubles + the header instead of 25: the record
 // stream is what the HBM pays for twice (written here, read by the closing kernel).
-constexpr int H_NK_SHIFT = 8, H_ORD_SHIFT = 11;
+constexpr int H_NK_SHIFT = PG_HDR_NK_SHIFT, H_ORD_SHIFT = PG_HDR_ORD_SHIFT;
 template <int K> __device__ __forceinline__ constexpr int ols_field(int d) { return d * (1 + K) + d * (d + 1) / 2; }
 template <int K> __device__ __forceinline__ constexpr int prs_field(int d) { return 3 * K + d * (1 + 3 * K); }
 
@@ -3198,6 +3198,18 @@ int fisher_host(pg_ctx *ctx, const uint32_t *counts, int64_t L, int n, const dou
 }
 
 } // namespace
+
+int pg_filter_headers(pg_ctx *ctx, const char *who, int kid, bool args_ok, const uint32_t *counts_dev, int64_t L, int n,
+                      const double *pool_sizes, const pg_filter *flt, int sort_desc, size_t tail_bytes, const int32_t **flags,
+                      int64_t *listed, char **tail) {
+    FilterPass F;
+    const int rc = filter_pass(ctx, who, kid, args_ok, counts_dev, L, n, pool_sizes, flt, sort_desc, tail_bytes, &F);
+    if (rc) return rc;
+    *flags = F.W.flags;
+    *listed = F.listed;
+    *tail = static_cast<char *>(ctx->ws.get()) + F.tail;
+    return PG_OK;
+}
 
 extern "C" int pg_locus_op_stats(const pg_ctx *ctx, int64_t *loci, int64_t *listed) {
     if (!ctx) return PG_ERR_INVALID;

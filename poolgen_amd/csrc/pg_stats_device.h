@@ -106,6 +106,69 @@ __device__ __forceinline__ double pg_ln_gamma(double x) {
     return log(s) + LN_2_SQRT_E_OVER_PI + (x - 0.5) * log((x - 0.5 + R) / 2.718281828459045);
 }
 
+// ---- statrs beta_reg (function/beta.rs checked_beta_reg) -----------------------------------------
+// approx' ulps_eq!(x, 1.0) with its defaults (epsilon = f64::EPSILON, max_ulps = 4)
+__device__ __forceinline__ bool pg_ulps_eq_one(double x) {
+    if (fabs(x - 1.0) <= PG_EPS) return true;
+    const long long a = __double_as_longlong(x), b = __double_as_longlong(1.0);
+    if ((a < 0) != (b < 0)) return false;
+    const long long d = a > b ? a - b : b - a;
+    return d <= 4;
+}
+
+// Regularised incomplete beta I_x(a, b) for a, b > 0 and 0 <= x <= 1: the modified Lentz continued fraction, at most 140
+// iterations, evaluated for (b, a, 1 - x) when x >= (a + 1) / (a + b + 2).  ln_beta = ln_gamma(a + b) - ln_gamma(a) - ln_gamma(b)
+// (in that order) is passed in: a caller that evaluates one distribution at many points forms it once.
+__device__ inline double pg_beta_reg_ln(double a, double b, double x, double ln_beta) {
+    const double bt = (x == 0.0 || pg_ulps_eq_one(x)) ? 0.0 : exp(ln_beta + a * log(x) + b * log(1.0 - x));
+    const bool symm = x >= (a + 1.0) / (a + b + 2.0);
+    if (bt == 0.0) return symm ? 1.0 : 0.0; // 0 * h / a: the fraction is not needed
+    const double eps = 1.1102230246251565e-16; // prec::F64_PREC
+    const double fpmin = 2.2250738585072014e-308 / eps;
+    if (symm) {
+        const double swap = a;
+        x = 1.0 - x;
+        a = b;
+        b = swap;
+    }
+    const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0;
+    double d = 1.0 - qab * x / qap;
+    if (fabs(d) < fpmin) d = fpmin;
+    d = 1.0 / d;
+    double h = d;
+    for (int mi = 1; mi < 141; ++mi) {
+        const double m = (double)mi;
+        const double m2 = m * 2.0;
+        double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < fpmin) d = fpmin;
+        c = 1.0 + aa / c;
+        if (fabs(c) < fpmin) c = fpmin;
+        d = 1.0 / d;
+        h = h * d * c;
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < fpmin) d = fpmin;
+        c = 1.0 + aa / c;
+        if (fabs(c) < fpmin) c = fpmin;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (fabs(del - 1.0) <= eps) break;
+    }
+    return symm ? 1.0 - bt * h / a : bt * h / a;
+}
+
+// Beta(a, b).cdf(x) as statrs' Beta::cdf reaches beta_reg: 0 below the support, 1 from x = 1 on (the cumulative percentiles of
+// gwalpha end a few ulp above one).
+__device__ inline double pg_beta_reg(double a, double b, double x) {
+    if (!(a > 0.0) || !(b > 0.0) || isnan(x)) return NAN;
+    if (x <= 0.0) return 0.0;
+    if (x >= 1.0) return 1.0;
+    return pg_beta_reg_ln(a, b, x, pg_ln_gamma(a + b) - pg_ln_gamma(a) - pg_ln_gamma(b));
+}
+
 // ---- statrs gamma_lr (Cephes igam / igamc) ----------------------------------------------------
 // Regularised lower incomplete gamma P(a, x).  ln_gamma_a = pg_ln_gamma(a) is passed in because
 // a = (n*alleles - 1)/2 takes at most a handful of values per launch.

@@ -6,6 +6,7 @@ Method names follow the reference operators they stand in for:
   correlation          gwas::correlation             (gwas/correlation_test.rs:73-129)
   chisq                tables::chisq                 (tables/chisq_test.rs:5-47)
   fisher               tables::fisher                (tables/fisher_exact_test.rs:32-130)
+  gwalpha              gwas::gwalpha_ls / gwalpha_ml (gwas/gwalpha.rs:281-380)
   gp_ols               gp::ols                       (gp/ols.rs:8-101)
 All heavy arguments are torch CUDA tensors (device memory owned by torch); results are
 torch CUDA tensors.  Everything is computed by libpoolgen_hip.so.
@@ -307,6 +308,51 @@ class Engine:
             return n_out, ids, pobs, pv
         live = torch.arange(5, device=dev)[None, :] < n_out[:, None]
         return n_out, torch.where(live, ids.T, torch.tensor(-1, dtype=torch.int32, device=dev)), pobs, pv
+
+    def gwalpha(self, counts, bins, q, sig: float, min: float, max: float, flt: Filter, method: str = "ML", raw: bool = False):
+        """gwas::gwalpha_ls / gwalpha_ml per row (= locus, kept allele): n_out, ids, mean_freq, alpha, shapes (4 per row), cost,
+        iters.  bins: the pools' shares (also the filter's pool sizes); q: column 1 of the reference's phenotype matrix as handed
+        over.  Any method other than "LS" means ML (main.rs:337-356).  A row's result depends on the row alone."""
+        L, n, six = counts.shape
+        assert six == 6
+        bh, qh = _host_f64(bins), _host_f64(q)
+        if bh.shape != (n,) or qh.shape != (n,):
+            raise ValueError(f"gwalpha: bins and q need one entry per pool ({n})")
+        dev = counts.device
+        n_out = torch.empty(L, dtype=torch.int32, device=dev)
+        ids = torch.empty((5, L), dtype=torch.int32, device=dev)
+        mf = torch.empty((5, L), dtype=torch.float64, device=dev)
+        alpha = torch.empty((5, L), dtype=torch.float64, device=dev)
+        shapes = torch.empty((5, L, 4), dtype=torch.float64, device=dev)
+        cost = torch.empty((5, L), dtype=torch.float64, device=dev)
+        iters = torch.empty((5, L), dtype=torch.int32, device=dev)
+        f = flt.to_c()
+        self._check(self._lib.pg_gwalpha_batch_dev(self._ctx, self._dev(counts, torch.int32), L, n, bh.ctypes.data, qh.ctypes.data,
+                                                   float(sig), float(min), float(max), C.byref(f), 0 if method == "LS" else 1,
+                                                   n_out.data_ptr(), ids.data_ptr(), mf.data_ptr(), alpha.data_ptr(),
+                                                   shapes.data_ptr(), cost.data_ptr(), iters.data_ptr()), "pg_gwalpha_batch_dev")
+        if raw:
+            return n_out, ids, mf, alpha, shapes, cost, iters
+        live = torch.arange(5, device=dev)[None, :] < n_out[:, None]
+        nan = torch.tensor(float("nan"), dtype=torch.float64, device=dev)
+        m1 = torch.tensor(-1, dtype=torch.int32, device=dev)
+        return (n_out, torch.where(live, ids.T, m1), torch.where(live, mf.T, nan), torch.where(live, alpha.T, nan),
+                torch.where(live[:, :, None], shapes.permute(1, 0, 2), nan), torch.where(live, cost.T, nan),
+                torch.where(live, iters.T, m1))
+
+    def beta_reg(self, a, b, x) -> torch.Tensor:
+        """Beta(a, b).cdf(x) elementwise as the gwalpha fit evaluates it (statrs' beta_reg behind Beta::cdf's guards)."""
+        dev = torch.device("cuda", self.device)
+        t = [torch.as_tensor(np.ascontiguousarray(np.asarray(v, dtype=np.float64))).to(dev) if not isinstance(v, torch.Tensor) else v
+             for v in (a, b, x)]
+        if not (t[0].shape == t[1].shape == t[2].shape):
+            raise ValueError("beta_reg: a, b and x need one shape")
+        out = torch.empty_like(t[0])
+        if out.numel() == 0:
+            return out
+        self._check(self._lib.pg_beta_reg_dev(self._ctx, self._dev(t[0], torch.float64), self._dev(t[1], torch.float64),
+                                              self._dev(t[2], torch.float64), t[0].numel(), out.data_ptr()), "pg_beta_reg_dev")
+        return out
 
     def last_listed(self):
         """(loci, listed) of the last batch operator call: how many loci its streaming pass handed to the second pass."""
