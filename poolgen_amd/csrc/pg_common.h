@@ -122,6 +122,16 @@ struct pg_ctx {
         if (!(cond)) return pg_fail(ctx, PG_ERR_INVALID, __VA_ARGS__); \
     } while (0)
 
+// The environment switches of the library: each forces a route that the default dispatch takes only at other shapes.  The table
+// (name, what it forces, what it replaces) is in pg_context.hip; pg_switch returns the variable's value, or null when unset.
+enum pg_switch_id {
+    PG_SW_SWEEP_V1, PG_SW_SWEEP_V2, PG_SW_SWEEP_GRID_MULT, PG_SW_NO_LAZY_KINSHIP, PG_SW_HOST_SLAB_MB,
+    PG_SW_GP_BETA_OLD, PG_SW_GP_BETA_VALU, PG_SW_GP_BETA_SCALAR, PG_SW_GP_TIMING, PG_SW_RIDGE_PER_REP, PG_SW_RIDGE_PER_FOLD,
+    PG_SW_MLE_LDS, PG_SW_OLS_ITER_KERNEL, PG_SW_ROWS_DIRECT, PG_SW_LOCUS_GROUPED,
+    PG_SW_COUNT
+};
+const char *pg_switch(pg_switch_id id);
+
 int pg_ws_reserve(pg_ctx *ctx, size_t bytes);
 int pg_pin_reserve(pg_ctx *ctx, size_t bytes);
 int pg_tcoef_reserve(pg_ctx *ctx, int df); // the t-distribution coefficients of `df` on the device (tcoef_dev, tcoef_df, tcoef_len)

@@ -1,5 +1,42 @@
 // pg_context.hip -- context lifetime, error reporting, workspace and HIP-event profiling.
 #include "pg_common.h"
+#include <cstdlib>
+
+// ---- the environment switches --------------------------------------------------------------------------------------------
+// Every variable the library reads, in the order of pg_switch_id, and the library's only getenv.  None of them changes what is
+// computed: each sends a call down a route that the default dispatch takes at other shapes, so that the tests can run both
+// routes on one input (INTEGRATION.md repeats this table).  A switch is read on every call, on purpose: the tests flip them
+// between calls on one context that lives for the whole session, so nothing here is cached.
+static const struct { const char *name, *forces, *replaces; } pg_switches[PG_SW_COUNT] = {
+    {"POOLGEN_SWEEP_V1", "the regression sweep runs the lane-per-locus row kernel (k_ols_sweep_rows)",
+     "the matrix-core sweep from 33 pools while its B table fits 160 KB; the super-row kernel below 12 columns"},
+    {"POOLGEN_SWEEP_V2", "the regression sweep runs the lane-per-locus super-row kernel (k_ols_sweep)",
+     "the matrix-core sweep; the row kernel from 12 columns on and up to 32 pools"},
+    {"POOLGEN_SWEEP_GRID_MULT", "=N: N workgroups per CU in the sweep's grid (N = 1: every wave walks many tiles)",
+     "what the occupancy allows (matrix-core sweep), 8 per CU (lane-per-locus sweeps)"},
+    {"POOLGEN_NO_LAZY_KINSHIP", "pg_ols_kinship_dev forms K and runs the eigen rule even when the caller does not ask for K",
+     "the one-pass lazy route (MODE 2 sweep) that decides m = 0 from 1'S1 and trace S"},
+    {"POOLGEN_HOST_SLAB_MB", "=N: pg_ols_kinship (host matrix) uploads and sweeps in slabs of N MB", "256 MB slabs"},
+    {"POOLGEN_GP_BETA_OLD", "pg_gp_beta_cols skips the matrix-core products kernel",
+     "the matrix-core kernel from 33 pools while its B table fits 160 KB (even ld, aligned G)"},
+    {"POOLGEN_GP_BETA_VALU", "... and skips k_gp_beta_mfma", "k_gp_beta_mfma for 5 .. 16 column-major columns"},
+    {"POOLGEN_GP_BETA_SCALAR", "... and skips k_gp_beta_lds, which leaves the scalar-operand k_gp_beta",
+     "k_gp_beta_lds when Z is past 12 KB (6 .. 24 columns)"},
+    {"POOLGEN_GP_TIMING", "host-side phase times of a penalised_path call on stderr", "no report"},
+    {"POOLGEN_RIDGE_PER_REP", "cross-validation runs one repetition per coefficient pass",
+     "all repetitions batched into shared passes when n_reps > 1"},
+    {"POOLGEN_RIDGE_PER_FOLD", "cross-validation fits every fold on its own",
+     "the fused route when the fold x trait columns fit one sweep (<= 34) and n < p + 1"},
+    {"POOLGEN_MLE_LDS", "the MLE runs its LDS kernel for small designs too", "the register kernel up to 4 design columns (m <= 2)"},
+    {"POOLGEN_OLS_ITER_KERNEL", "=stream: ols_iter / chisq_test run the streaming kernel; any other value: the row kernel",
+     "the choice by the last batch's error flags (rows_next), row kernel for 32 .. 448 pools"},
+    {"POOLGEN_ROWS_DIRECT", "=0: chisq_test's row kernel stages its pools through the LDS buffer",
+     "direct register loads (chisq_test only; ols_iter always stages)"},
+    {"POOLGEN_LOCUS_GROUPED", "=0 / =1: the listed-locus operators run ungrouped / grouped by allele count",
+     "grouped from LO_GROUP_FROM listed loci on"},
+};
+
+const char *pg_switch(pg_switch_id id) { return std::getenv(pg_switches[id].name); }
 
 int pg_fail(pg_ctx *ctx, int code, const char *fmt, ...) {
     char buf[1024];

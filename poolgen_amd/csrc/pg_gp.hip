@@ -481,7 +481,7 @@ struct GpCall {
 // POOLGEN_GP_TIMING=1: host-side phase times of a call on stderr.  A phase is what runs in the scope of a Phase on its field.
 struct PhaseTimes {
     using Clock = std::chrono::steady_clock;
-    const bool report = std::getenv("POOLGEN_GP_TIMING") != nullptr;
+    const bool report = pg_switch(PG_SW_GP_TIMING) != nullptr;
     const Clock::time_point entry = Clock::now();
     double before = 0, solve = 0, beta = 0, params = 0, predict = 0, alloc = 0, release = 0; // seconds
     static double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
@@ -871,7 +871,7 @@ int cv_fused(pg_ctx *ctx, const GpCall &in, const std::vector<double> &xxt, Ridg
     const int64_t p = in.p;
     const int n = in.n, k = in.k, C = in.C(), n_reps = in.n_reps;
     const size_t ncols_all = (size_t)n_reps * C + k;
-    bool batched = n_reps > 1 && !std::getenv("POOLGEN_RIDGE_PER_REP");
+    bool batched = n_reps > 1 && !pg_switch(PG_SW_RIDGE_PER_REP);
     if (batched) {
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess || sizeof(double) * (size_t)p * ncols_all > fr / 2) batched = false;
@@ -1042,7 +1042,7 @@ int penalised_path(pg_ctx *ctx, GpCall in, double lambda_step, double *beta_dev,
         if (in.fold_of[i] < 0 || in.fold_of[i] > in.n_folds /* == n_folds: the left-over group of k_split (:444-448), never validated */)
             return pg_fail(ctx, PG_ERR_INVALID, "gp_ridge: fold id out of range");
     std::vector<double> perf((size_t)in.n_reps * in.n_folds * in.A() * in.L() * in.k, NAN);
-    const bool fused = in.C() <= PG_MAX_SWEEP_COLS && (int64_t)in.n < in.p + 1 && !std::getenv("POOLGEN_RIDGE_PER_FOLD");
+    const bool fused = in.C() <= PG_MAX_SWEEP_COLS && (int64_t)in.n < in.p + 1 && !pg_switch(PG_SW_RIDGE_PER_FOLD);
     T.before = PhaseTimes::since(T.entry); // X X^T, its copy to the host, the work buffers
     bool have_fit = false; // the all-rows fit is in beta_dev
     if (int rc = fused ? cv_fused(ctx, in, xxt, W, T, perf, beta_dev, &have_fit) : cv_per_fold(ctx, in, xxt, W, perf, beta_dev)) return rc;

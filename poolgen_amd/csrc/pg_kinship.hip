@@ -681,8 +681,8 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
 #if KIN_WAVES_DEF == 16
     // Up to 64 pools (<= 10 tiles) a 16-wave workgroup leaves most of its waves without a tile: the same kernel built for 8-wave
     // workgroups (pg_kinship_w8.hip) takes over -- 1.36 -> 1.01 ms per 4 M loci at 48 and 64 pools; from 100 pools on it is no
-    // faster, at 150 slower (profiles/r03_kinship_small_n.log).  POOLGEN_KIN_NO_W8=1: A/B runs.
-    if (n <= 64 && !std::getenv("POOLGEN_KIN_NO_W8")) return pg_launch_kinship_w8(ctx, G, p, n, ld, S, add_intercept, kid, allow_fuse);
+    // faster, at 150 slower (profiles/r03_kinship_small_n.log).
+    if (n <= 64) return pg_launch_kinship_w8(ctx, G, p, n, ld, S, add_intercept, kid, allow_fuse);
 #endif
 
     PG_CHECK(ctx, G && S, "kinship: null pointer");
@@ -701,8 +701,8 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     else { P.Tb = 8; P.nb = (P.T + 7) / 8; }
     // nb >= 4: 64 + 2 * ceil(36 / (nb - 1)) <= 96 slots; nb == 2: measured -- a win at T = 15, 16 (7.6 -> 6.9 ms at n = 240..256,
     // 4 M loci), a loss at T = 14 where the diagonal workgroups stage few columns
-    P.merged = ((P.nb >= 4 || (P.nb == 2 && P.T >= 15)) && !std::getenv("POOLGEN_KIN_NO_MERGE")) ? 1 : 0;
-    if (!P.merged && P.nb >= 2 && P.nb <= 3 && !std::getenv("POOLGEN_KIN_NO_WEIGHTS")) {
+    P.merged = (P.nb >= 4 || (P.nb == 2 && P.T >= 15)) ? 1 : 0;
+    if (!P.merged && P.nb >= 2 && P.nb <= 3) {
         // the block size that runs the fewest tile slots over all pairs (T = 17: blocks of 6, 6, 5 tile columns = 13 slot units
         // where 8, 8, 1 ran 16)
         // (a pair with two slots is bound by its stage hand-over, not by its MFMAs: it costs about 2.7 slots' worth -- measured
@@ -725,7 +725,6 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     P.split = (P.merged && P.nb == 2) ? 2 : 1;                                               // nb == 2: all 136 tiles, 68 + 68
     const int npairs = (P.merged ? P.nb * (P.nb - 1) / 2 : P.nb * (P.nb + 1) / 2) * P.split;
     int nslab = cus / npairs;
-    if (const char *e = std::getenv("POOLGEN_KIN_SLAB_MULT")) nslab *= std::max(1, std::atoi(e)); // experiments: workgroups per CU
     if (nslab < 1) nslab = 1;
     const int64_t max_slabs = (p + KIN_KC - 1) / KIN_KC;
     if (nslab > max_slabs) nslab = (int)max_slabs;
@@ -737,9 +736,9 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     nslab = (int)((p + P.loci_per_wg - 1) / P.loci_per_wg);
 
     P.npairs = npairs; P.nslab = nslab;
-    P.skip_dead = (!std::getenv("POOLGEN_KIN_NO_SKIP") && P.nb <= 2) ? 1 : 0; // (from 4 blocks on the lists are full: 500 pools 10.17 -> 10.36 ms with it)
+    P.skip_dead = P.nb <= 2 ? 1 : 0; // (from 4 blocks on the lists are full: 500 pools 10.17 -> 10.36 ms with it)
     P.xcd_spx = 0;
-    if (npairs > 1 && cus % 8 == 0 && !std::getenv("POOLGEN_KIN_NO_XCD")) {
+    if (npairs > 1 && cus % 8 == 0) {
         const int spx = (cus / 8) / npairs;        // whole slabs (all their pairs) that fit one XCD's CUs
         if (spx >= 1 && 8 * spx <= nslab) P.xcd_spx = spx;
     }
@@ -748,7 +747,7 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     KC.blk = 0; KC.nb = P.nb;
     for (int q = 0; q < 6; ++q) KC.n[q] = 0;
     int grid1d = 0;
-    if (P.nb >= 2 && P.nb <= 3 && !P.merged && !std::getenv("POOLGEN_KIN_NO_WEIGHTS")) {
+    if (P.nb >= 2 && P.nb <= 3 && !P.merged) {
         // tile slots a wave of pair (bi, bj) runs per k-step (the kernel's TPW) + a constant for its share of the staging
         double wgt[6], wsum = 0.0;
         int q = 0;
@@ -827,19 +826,11 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     //   bits          0      1      2      3
     //   fused sums   7.62   7.59   7.31   7.23     (bit 1 costs the fused kernel 19 spilled registers and still pays)
     //   plain        6.84   6.80   6.41   6.30
-    // POOLGEN_KIN_SMALL=<bits> overrides (A/B timing).
-    int sm = !spec13 ? 0 : ((n <= 200 ? 2 : 0) | 1);
-    if (const char *e = std::getenv("POOLGEN_KIN_SMALL")) sm = spec13 ? (std::atoi(e) & (n <= 200 ? 3 : 1)) : 0;
-    if (std::getenv("POOLGEN_KIN_NO_SMALL")) sm = 0;
+    // So the 13-tile shape runs bits 3 up to 200 pools and bits 1 for 201 .. 208 (the last column holds more than 8 pools).
     auto pick = [&](auto fz) -> hipError_t {
         constexpr bool FZ = decltype(fz)::value;
         if (!spec13) return P.skip_dead ? launch(k_kinship_syrk<FZ, false, 0, true>) : launch(k_kinship_syrk<FZ, false, 0, false>);
-        switch (sm) {
-        case 1: return launch(k_kinship_syrk<FZ, true, 1>);
-        case 2: return launch(k_kinship_syrk<FZ, true, 2>);
-        case 3: return launch(k_kinship_syrk<FZ, true, 3>);
-        default: return launch(k_kinship_syrk<FZ, true, 0>);
-        }
+        return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3>) : launch(k_kinship_syrk<FZ, true, 1>);
     };
     le = fuse ? pick(std::true_type{}) : pick(std::false_type{});
     PG_HIP(ctx, le);

@@ -2442,12 +2442,12 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
     // Which kernel: the order-free one costs the same whatever the counts look like (0.63 of the HBM peak at 100 pools); the
     // streaming pass is faster on clean counts (0.68 - 0.70) and slower on error-bearing ones (second pass: 0.53).  A context
     // remembers what its last ols_iter batch looked like (pieces of one file look alike) and starts with the robust kernel.
-    // POOLGEN_OLS_ITER_KERNEL=rows|stream fixes the choice (tests that compare bits across calls; A/B runs).
+    // PG_SW_OLS_ITER_KERNEL (=rows|stream) fixes the choice: the tests that compare bits across calls run under both.
     constexpr int ROWS_OP = (OP == OP_CHISQ) ? 1 : 0;
     bool &rows_next = ctx->rows_next[ROWS_OP];
     if (P.t0 == 0) ctx->rows_call[ROWS_OP] = rows_next; // one choice per call: its launch groups (trait pairs) must agree on who wrote slot 0
     bool want_rows = ctx->rows_call[ROWS_OP];
-    if (const char *e = std::getenv("POOLGEN_OLS_ITER_KERNEL")) want_rows = std::strcmp(e, "stream") != 0;
+    if (const char *e = pg_switch(PG_SW_OLS_ITER_KERNEL)) want_rows = std::strcmp(e, "stream") != 0;
     if ((OP == OP_OLS || OP == OP_CHISQ) && n >= 32 && want_rows) {
         lpl = n <= 112 ? 16 : (n <= 224 ? 32 : (n <= 448 ? 64 : 0));
         if (lpl == 64 && (n & 1)) lpl = 0; // a group = one locus must be a whole number of 16-byte pieces
@@ -2457,9 +2457,9 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
         if constexpr (OP == OP_OLS || OP == OP_CHISQ) {
             // chisq_test reads its pools straight into registers (DIRECT: no staging buffer, three waves per SIMD): -3 % at 100 pools,
             // -10 % at 200 on the same box; ols_iter gains nothing from it (measured: DESIGN section 3.3) and keeps the buffer.
-            // POOLGEN_ROWS_DIRECT=0 puts chisq_test back on the buffer (A/B runs).
+            // PG_SW_ROWS_DIRECT (=0) puts chisq_test back on the buffer: the tests run both.
             bool direct = OP == OP_CHISQ;
-            if (const char *e = std::getenv("POOLGEN_ROWS_DIRECT")) direct = direct && std::strcmp(e, "0") != 0;
+            if (const char *e = pg_switch(PG_SW_ROWS_DIRECT)) direct = direct && std::strcmp(e, "0") != 0;
             auto pick_rows = [&]() -> const void * {
                 if constexpr (OP == OP_CHISQ) {
 #define PG_ROWS(LPLV) (direct ? (rns ? (const void *)k_ols_rows<OP, LPLV, true, 1, true> : (const void *)k_ols_rows<OP, LPLV, false, 1, true>) \
@@ -2528,7 +2528,7 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
         const int64_t wants = (tiles + 3) / 4, caps = (int64_t)ctx->cus * 8;
         const unsigned gs = (unsigned)(wants < caps ? wants : caps);
         int grouped = total >= (int64_t)LO_GROUP_FROM ? 1 : 0;
-        if (const char *e = std::getenv("POOLGEN_LOCUS_GROUPED")) grouped = std::atoi(e) != 0; // (A/B runs, tests of both routes)
+        if (const char *e = pg_switch(PG_SW_LOCUS_GROUPED)) grouped = std::atoi(e) != 0; // (the tests of both routes)
         const int64_t *list = W.second;
         if (grouped) {
             // (few, long-running waves: every wave ends in five atomics on the same five words -- with a wave per tile they took

@@ -432,7 +432,7 @@ extern "C" int pg_mle_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
     std::memset(&HB, 0, sizeof HB);
     // POOLGEN_MLE_LDS=1 sends the small designs through the LDS kernel too: same arithmetic in the same order, so the results must be
     // bit-identical to the register kernel's (tests/test_gpu_mle.py) -- the check that pins the LDS kernel's bookkeeping
-    const bool big = m + 2 > MLE_MAXP || std::getenv("POOLGEN_MLE_LDS") != nullptr;
+    const bool big = m + 2 > MLE_MAXP || pg_switch(PG_SW_MLE_LDS) != nullptr;
     for (int i = 0; i < n; ++i) {
         Z[(size_t)i * ncol] = 1.0;
         for (int a = 0; a < m; ++a) Z[(size_t)i * ncol + 1 + a] = V[(size_t)i * m + a];

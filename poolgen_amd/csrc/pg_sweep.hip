@@ -152,7 +152,6 @@ struct SweepGeom {
     int nch;        // 32-double chunks per super-row
     int64_t sl;     // doubles per super-row = g * ld
     int64_t total;  // p * ld: loads are clamped to the last pair of the matrix
-    int prefetch;   // experiments: 0 = the loads of a chunk are issued when the chunk is needed
 };
 
 // The 16 staging registers of a chunk are named variables, not an array: they are live across the consumption loop (the
@@ -175,9 +174,7 @@ static_assert(SW_NLD == 16, "the staging macros below spell out 16 load instruct
     }
 #define SW_STAGE(r) *reinterpret_cast<double2 *>(&tile[(SW_RPI * r + lr) * SW_PITCH + 2 * piece]) = v##r;
 
-// EXP: timing experiments only (wrong results): bit 0 = W operands are constants (no scalar loads), bit 1 = g is a constant
-// (no LDS reads), bit 2 = no LDS staging writes
-template <int C, int EXP = 0>
+template <int C>
 __global__ __launch_bounds__(SW_THREADS, SW_MINWAVES) void k_ols_sweep(
     const double *__restrict__ G, const double *__restrict__ W, const double *__restrict__ syy,
     const double *__restrict__ tcoef, double *__restrict__ beta, double *__restrict__ var,
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(SW_THREADS, SW_MINWAVES) void k_ols_sweep(
     SW_REP16(SW_DECL)
     int64_t t = (int64_t)blockIdx.x * SW_WAVES + wave;
     if (t >= D.ntiles) return;
-    if (Q.prefetch & 1) SW_ISSUE(t, 0)
+    SW_ISSUE(t, 0)
     for (; t < D.ntiles; t += wstride) {
         double acc[C];
         double s2 = 0.0, shift = 0.0;
@@ -204,15 +201,9 @@ __global__ __launch_bounds__(SW_THREADS, SW_MINWAVES) void k_ols_sweep(
                           // otherwise: WRITE_SIZE 2x)
         int j = 0, pos = 0; // locus within the super-row, position within its row (pools n..ld-1 are padding)
         for (int ch = 0; ch < Q.nch; ++ch) {
-            if (!(Q.prefetch & 1)) SW_ISSUE(t, ch)
-            if (EXP & 4) {
-#define SW_TOUCH(r) s2 += v##r.x + v##r.y;
-                SW_REP16(SW_TOUCH)
-            } else {
-                SW_REP16(SW_STAGE)
-            }
+            SW_REP16(SW_STAGE)
             __builtin_amdgcn_wave_barrier();
-            if ((Q.prefetch & 3) == 1) {   // next chunk of this tile, else the first chunk of the wave's next tile (clamped loads: harmless past the end)
+            {   // next chunk of this tile, else the first chunk of the wave's next tile (clamped loads: harmless past the end)
                 const bool more = ch + 1 < Q.nch;
                 const int64_t tn = more ? t : t + wstride;
                 const int cn = more ? ch + 1 : 0;
@@ -220,7 +211,7 @@ __global__ __launch_bounds__(SW_THREADS, SW_MINWAVES) void k_ols_sweep(
             }
             const int64_t left = Q.sl - (int64_t)ch * SW_CH;
             const int iend = left < SW_CH ? (int)left : SW_CH;
-            int i = (Q.prefetch & 4) ? iend : 0; // (timing experiments, POOLGEN_SWEEP_MODE: bit 1 = no loads after the first, bit 2 = no arithmetic)
+            int i = 0;
             while (i < iend) {
                 if (pos >= n) { // padding between n and ld
                     int skip = ld - pos;
@@ -241,15 +232,15 @@ __global__ __launch_bounds__(SW_THREADS, SW_MINWAVES) void k_ols_sweep(
                 if (i == 0 && len == SW_CH) {
 #pragma unroll
                     for (int q = 0; q < SW_CH; q += 2) {
-                        const double2 g2 = (EXP & 2) ? double2{shift + 1e-3 * q, shift - 1e-3} : *reinterpret_cast<const double2 *>(&row[q]);
+                        const double2 g2 = *reinterpret_cast<const double2 *>(&row[q]);
                         const double ga = g2.x - shift;
                         const double gb = g2.y - shift;
                         s2 = fma(ga, ga, s2);
 #pragma unroll
-                        for (int c = 0; c < C; ++c) acc[c] = fma(ga, (EXP & 1) ? 0.25 + c : Wp[q * C + c], acc[c]);
+                        for (int c = 0; c < C; ++c) acc[c] = fma(ga, Wp[q * C + c], acc[c]);
                         s2 = fma(gb, gb, s2);
 #pragma unroll
-                        for (int c = 0; c < C; ++c) acc[c] = fma(gb, (EXP & 1) ? 0.5 - c : Wp[(q + 1) * C + c], acc[c]);
+                        for (int c = 0; c < C; ++c) acc[c] = fma(gb, Wp[(q + 1) * C + c], acc[c]);
                     }
                 } else if (((i | len) & 1) == 0) {
                     // a run that is not a whole chunk (the chunk holds the end of one locus and the start of the next): blocks of
@@ -336,7 +327,8 @@ __global__ __launch_bounds__(SW_THREADS, SW_MINWAVES) void k_ols_sweep(
 // mid-chunk locus boundaries cost more than the over-fetch once 14 fp64 operations per pool keep the vector unit busy), while
 // up to 8 columns (m = 0, 2, 4, 6 with one trait: 2.70 / 2.88 / 2.93 / 2.93 ms against 2.72 / 2.95 / 2.95 / 2.97) the super-row
 // kernel is ahead and moves exactly the algorithmic bytes.
-// launch_sweep picks by column count; POOLGEN_SWEEP_V1=1 / POOLGEN_SWEEP_V2=1 force one of them (A/B timing).
+// launch_sweep takes this kernel from 12 columns on and for 32 pools or fewer, the super-row kernel otherwise; the switches
+// PG_SW_SWEEP_V1 / PG_SW_SWEEP_V2 force one of them at any shape (the tests of both routes).
 template <int C>
 __global__ __launch_bounds__(SW_THREADS, SW_MINWAVES) void k_ols_sweep_rows(
     const double *__restrict__ G, const double *__restrict__ W, const double *__restrict__ syy,
@@ -411,8 +403,6 @@ struct MsGeom {
     int cols;       // row pitch of W
     int cu;         // columns in use = m + 1 + k
     int pitch;      // doubles per locus in the closing stage (odd: conflict-free lane-per-locus reads)
-    int exp;        // timing experiments (POOLGEN_SWEEP_EXP, wrong results): 1 = no closing arithmetic, 2 = no closing at all,
-                    // 8 = no stores, 16 = stores that stay in the L2
     int mask_last;  // ... or past its n pools: those elements are zeroed
     int64_t n64;    // 64-locus groups
 };
@@ -552,7 +542,7 @@ __global__ __launch_bounds__(ms_threads(NCG), 1) void k_ols_sweep_mfma(
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) acc[cg] = ms_d4{0.0, 0.0, 0.0, 0.0};
         s2 = 0.0;
-        if (c.T != 3 || (M.exp & 2)) return;
+        if (c.T != 3) return;
         // ---- end of a 64-locus group: one lane per locus (gwas/ols.rs:102-116, 139-158) --------------------------------
         __builtin_amdgcn_wave_barrier();
         const int64_t l = c.t64 * 64 + lane;
@@ -578,8 +568,8 @@ __global__ __launch_bounds__(ms_threads(NCG), 1) void k_ols_sweep_mfma(
                 lz2 += fma(nn * g0, g0, fma(2.0 * g0, s1, gg));
             }
             if (D.k == 1) { // straight-line code and ordinary stores
-                double b = sgg, vb = gg, pv = uu;
-                if (!(M.exp & 1)) ols_close(sgg, sr[D.m1], syy[0], bad, D.dfe, D.tdf, tcoef, D.ntcoef, b, vb, pv);
+                double b, vb, pv;
+                ols_close(sgg, sr[D.m1], syy[0], bad, D.dfe, D.tdf, tcoef, D.ntcoef, b, vb, pv);
                 beta[l] = b;
                 var[l] = vb;
                 pval[l] = pv;
@@ -910,7 +900,7 @@ struct SweepArgs {
 template <int C>
 int launch_sweep(pg_ctx *ctx, const SweepArgs &A, int grid) {
     const size_t shmem = (size_t)SW_WAVES * SW_TILE * sizeof(double);
-    const bool rows_kernel = std::getenv("POOLGEN_SWEEP_V1") || ((C >= 12 || A.D.n <= 32) && !std::getenv("POOLGEN_SWEEP_V2"));
+    const bool rows_kernel = pg_switch(PG_SW_SWEEP_V1) || ((C >= 12 || A.D.n <= 32) && !pg_switch(PG_SW_SWEEP_V2));
     if (rows_kernel) {
         SweepDims D1 = A.D;
         D1.ntiles = (A.D.p + 63) / 64;
@@ -928,28 +918,6 @@ int launch_sweep(pg_ctx *ctx, const SweepArgs &A, int grid) {
     }
     PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_ols_sweep<C>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    if constexpr (C == 2) {
-        if (const char *e = std::getenv("POOLGEN_SWEEP_EXP")) {
-            const int x = std::atoi(e);
-            auto go = [&](auto kern) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                pg_prof_begin(ctx, PG_K_SWEEP);
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(SW_THREADS), shmem, ctx->stream, A.G, A.W, A.syy, A.tcoef, A.beta, A.var,
-                                   A.pval, A.D, A.Q);
-                pg_prof_end(ctx);
-            };
-            switch (x) {
-            case 1: go(k_ols_sweep<2, 1>); break;
-            case 2: go(k_ols_sweep<2, 2>); break;
-            case 3: go(k_ols_sweep<2, 3>); break;
-            case 4: go(k_ols_sweep<2, 4>); break;
-            case 6: go(k_ols_sweep<2, 6>); break;
-            default: go(k_ols_sweep<2, 7>); break;
-            }
-            PG_HIP(ctx, hipGetLastError());
-            return PG_OK;
-        }
-    }
     pg_prof_begin(ctx, PG_K_SWEEP);
     hipLaunchKernelGGL(k_ols_sweep<C>, dim3(grid), dim3(SW_THREADS), shmem, ctx->stream, A.G, A.W,
                        A.syy, A.tcoef, A.beta, A.var, A.pval, A.D, A.Q);
@@ -969,7 +937,6 @@ int launch_sweep_mfma_as(pg_ctx *ctx, const SweepArgs &A, MsGeom M, int kernel_i
     constexpr int threads = ms_threads(NCG), waves = threads / 64;
     M.ng = (M.nc + U - 1) / U;
     const int ncp = M.ng * U;
-    M.exp = std::getenv("POOLGEN_SWEEP_EXP") ? std::atoi(std::getenv("POOLGEN_SWEEP_EXP")) : 0;
     M.mask_last = 8 * ncp > A.D.n;
     const size_t shmem = ((size_t)NCG * ncp * 128 + (size_t)waves * 64 * M.pitch) * sizeof(double);
     auto kern = k_ols_sweep_mfma<U, R, NCG, MODE>;
@@ -977,7 +944,7 @@ int launch_sweep_mfma_as(pg_ctx *ctx, const SweepArgs &A, MsGeom M, int kernel_i
     int per_cu = 0;
     PG_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, shmem));
     if (per_cu < 1) return pg_fail(ctx, PG_ERR_UNSUPPORTED, "sweep: %zu bytes of LDS per workgroup do not fit", shmem);
-    if (const char *e = std::getenv("POOLGEN_SWEEP_GRID_MULT")) per_cu = std::max(1, std::atoi(e)); // experiments
+    if (const char *e = pg_switch(PG_SW_SWEEP_GRID_MULT)) per_cu = std::max(1, std::atoi(e));
     if (MODE == 2) per_cu = std::min(per_cu, MS_LZ_PER_CU); // one (1'S1, trace S) pair per wave of the grid: what lz_dev holds
     const int64_t blocks = (M.n64 + waves - 1) / waves, cap = (int64_t)ctx->cus * per_cu;
     pg_prof_begin(ctx, kernel_id);
@@ -994,7 +961,6 @@ int ms_pick_u(int nc) {
         const int padded = (nc + u - 1) / u * u;
         if (padded < best) { best = padded; U = u; }
     }
-    if (const char *e = std::getenv("POOLGEN_SWEEP_U")) { const int u = std::atoi(e); if (u >= 5 && u <= 8) U = u; } // experiments
     return U;
 }
 // row pitch (doubles) of the closing stage: MODE 2 keeps the locus' shift behind the sums
@@ -1019,15 +985,6 @@ int launch_sweep_mfma(pg_ctx *ctx, const SweepArgs &A, int cols, int cu, int ker
     return ncg == 1 ? launch_sweep_mfma_as<UU, R1, 1, MODE>(ctx, A, M, kernel_id)                                 \
          : ncg == 2 ? launch_sweep_mfma_as<UU, RR, 2, MODE>(ctx, A, M, kernel_id)                                 \
                     : launch_sweep_mfma_as<UU, RR, 3, MODE>(ctx, A, M, kernel_id);
-    if (const char *e = std::getenv("POOLGEN_SWEEP_R")) { // experiments: other ring depths (one accumulator, the sweep only)
-        const int r = std::atoi(e);
-        if constexpr (MODE == 0) {
-            if (ncg == 1 && U == 5 && r == 2) return launch_sweep_mfma_as<5, 2, 1, 0>(ctx, A, M, kernel_id);
-            if (ncg == 1 && U == 5 && r == 4) return launch_sweep_mfma_as<5, 4, 1, 0>(ctx, A, M, kernel_id);
-            if (ncg == 1 && U == 7 && r == 2) return launch_sweep_mfma_as<7, 2, 1, 0>(ctx, A, M, kernel_id);
-            if (ncg == 1 && U == 8 && r == 2) return launch_sweep_mfma_as<8, 2, 1, 0>(ctx, A, M, kernel_id);
-        }
-    }
     if constexpr (MODE == 2) { // intercept + traits only: one accumulator
         switch (U) {
         case 5: return launch_sweep_mfma_as<5, 3, 1, 2>(ctx, A, M, kernel_id);
@@ -1324,8 +1281,6 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
         P.Q.sl = (int64_t)P.Q.g * ld;
         P.Q.nch = (int)((P.Q.sl + SW_CH - 1) / SW_CH);
         P.Q.total = p * ld;
-        P.Q.prefetch = std::getenv("POOLGEN_SWEEP_NOPF") ? 0 : 1;
-        if (const char *e = std::getenv("POOLGEN_SWEEP_MODE")) P.Q.prefetch = std::atoi(e); // 3: compute only, 5: memory only (wrong results)
     }
     const int64_t nsr = (p + P.Q.g - 1) / P.Q.g;
     P.D.ntiles = (nsr + 63) / 64;
@@ -1335,7 +1290,7 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
         ctx->spec_ld == ld && ctx->spec_k == ctx->st_k && ctx->ph_n == n && ctx->st_Y_matches_ph) {
         // m = 0: the kinship pass already formed the sums of the intercept-only fits from its read of G
         pg_prof_begin(ctx, PG_K_SWEEP_FINISH);
-        if (ctx->st_k == 1 && !std::getenv("POOLGEN_FINISH_X1")) {
+        if (ctx->st_k == 1) {
             const int64_t half = ((p + 1) / 2 + 255) / 256 * 256;
             hipLaunchKernelGGL(k_sweep_finish_x2, dim3((unsigned)(half / 256)), dim3(256), 0, ctx->stream, ctx->spec_dev, ctx->syy_dev,
                                ctx->tcoef_dev, beta_dev, var_dev, pval_dev, P.D, half);
@@ -1346,13 +1301,15 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
         PG_HIP(ctx, hipGetLastError());
         return PG_OK;
     }
-    // the matrix-core sweep unless an A/B run asks for one of the vector-ALU kernels
+    // The matrix-core sweep wherever it fits (ms_fits).  The two lane-per-locus kernels are no leftovers: they are the only route
+    // for fewer than 33 pools (under 5 chunks per locus) and for a B table past the 160 KB of a CU's LDS (one column group: from
+    // about 1200 pools); PG_SW_SWEEP_V1 / PG_SW_SWEEP_V2 send any shape to one of them.
     const int cu = ctx->st_m + 1 + ctx->st_k;
-    if (ms_fits(n, cu, 0) && !std::getenv("POOLGEN_SWEEP_V1") && !std::getenv("POOLGEN_SWEEP_V2"))
+    if (ms_fits(n, cu, 0) && !pg_switch(PG_SW_SWEEP_V1) && !pg_switch(PG_SW_SWEEP_V2))
         return launch_sweep_mfma<0>(ctx, P, ctx->st_cols, cu, PG_K_SWEEP);
     int64_t blocks = (P.D.ntiles + SW_WAVES - 1) / SW_WAVES;
     int mult = 8;
-    if (const char *e = std::getenv("POOLGEN_SWEEP_GRID_MULT")) mult = std::max(1, std::atoi(e)); // experiments
+    if (const char *e = pg_switch(PG_SW_SWEEP_GRID_MULT)) mult = std::max(1, std::atoi(e));
     const int64_t cap = (int64_t)cus * mult;
     const int grid = (int)(blocks < cap ? blocks : cap);
     return with_cols(ctx, ctx->st_cols, [&](auto c) { return launch_sweep<decltype(c)::value>(ctx, P, grid); });
@@ -1371,7 +1328,7 @@ extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
     // One HBM-bound pass then gives the outputs of the m = 0 analysis (the sweep kernel's own: bit-identical to the two-pass
     // route); if the bound does not clear x by 1e-9 -- never on an uncentred kinship of real frequencies -- the full route below runs.
     if (!K_out && force_m < 0 && G_dev && Y && beta_dev && var_dev && pval_dev && p > 0 && n >= 3 && k >= 1 && k <= 15 && ld >= n &&
-        (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && ms_fits(n, 1 + k, 2) && !std::getenv("POOLGEN_NO_LAZY_KINSHIP")) {
+        (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && ms_fits(n, 1 + k, 2) && !pg_switch(PG_SW_NO_LAZY_KINSHIP)) {
         rc = pg_covariates_set(ctx, n, nullptr, 0, Y, k);
         if (rc) return rc;
         const size_t lzbytes = sizeof(double) * 2 * (size_t)ctx->cus * (ms_threads(1) / 64) * MS_LZ_PER_CU; // the MODE-2 grid is clamped to it
@@ -1450,7 +1407,7 @@ extern "C" int pg_ols_kinship(pg_ctx *ctx, const double *G, int64_t p, int n, in
     PG_CHECK(ctx, ld >= n && (ld % 2) == 0, "ols_kinship: ld (%lld) must be even and >= n (%d)", (long long)ld, n);
     PG_HIP(ctx, hipSetDevice(ctx->device));
     long slab_mb = 256;
-    if (const char *e = std::getenv("POOLGEN_HOST_SLAB_MB")) slab_mb = std::max(1L, std::atol(e));
+    if (const char *e = pg_switch(PG_SW_HOST_SLAB_MB)) slab_mb = std::max(1L, std::atol(e));
     int64_t slab_loci = ((int64_t)slab_mb << 20) / (ld * 8);
     slab_loci = std::max<int64_t>(1024, slab_loci / 1024 * 1024); // a multiple of the sweep's super-row tiles
     const int nslab = (int)((p + slab_loci - 1) / slab_loci);
@@ -1553,16 +1510,17 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
     int64_t blocks = (D.ntiles + SW_WAVES - 1) / SW_WAVES;
     const int64_t cap = (int64_t)ctx->cus * 8;
     const int grid = (int)(blocks < cap ? blocks : cap);
-    // the matrix-core kernel of the sweep in its products-only mode: every shape, one read of G at the sweep's rate
-    // (the older forms below are kept for A/B timing: POOLGEN_GP_BETA_OLD=1)
+    // the matrix-core kernel of the sweep in its products-only mode wherever it fits (ms_fits): one read of G at the sweep's rate.
+    // The three older forms below are live: they take every call with fewer than 33 pools, a B table past 160 KB, an odd ld or
+    // a G that is not 16-byte aligned.  PG_SW_GP_BETA_OLD sends any shape to them, _VALU and _SCALAR one step further down.
     const int zrows = (n + SW_CH - 1) / SW_CH * SW_CH;
     const size_t mfma_lds = ((size_t)zrows * 16 + (size_t)SW_WAVES * MB_TILE) * sizeof(double);
     const int wdoubles = n_even * cols;
     const size_t lds_need = ((size_t)wdoubles + (size_t)SW_WAVES * SW_TILE) * sizeof(double);
-    if (ms_fits(n, ncol, 1) && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && !std::getenv("POOLGEN_GP_BETA_OLD"))
+    if (ms_fits(n, ncol, 1) && (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(G_dev) & 15) == 0 && !pg_switch(PG_SW_GP_BETA_OLD))
         rc = launch_sweep_mfma<1>(ctx, P, cols, ncol, PG_K_GP_BETA);
     // the folds' slopes of a CV repetition (column-major, up to 16 columns): the MFMA form over an LDS-staged tile
-    else if (!ss_out_dev && colmajor && ncol >= 5 && ncol <= 16 && mfma_lds <= 150 * 1024 && !std::getenv("POOLGEN_GP_BETA_VALU")) {
+    else if (!ss_out_dev && colmajor && ncol >= 5 && ncol <= 16 && mfma_lds <= 150 * 1024 && !pg_switch(PG_SW_GP_BETA_VALU)) {
         rc = upload_Z(Z16, zrows, 16);
         if (rc) return rc;
         const int g2 = (int)std::min<int64_t>(blocks, (int64_t)ctx->cus);
@@ -1570,7 +1528,7 @@ int pg_gp_beta_cols(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
     }
     // many columns x many pools: Z no longer fits the scalar cache -> the LDS-resident variant (see k_gp_beta_lds)
     else if (!ss_out_dev && cols >= 6 && (cols % 2) == 0 && cols <= 24 && (size_t)wdoubles * sizeof(double) > 12288 && lds_need <= 150 * 1024 &&
-             !std::getenv("POOLGEN_GP_BETA_SCALAR"))
+             !pg_switch(PG_SW_GP_BETA_SCALAR))
         rc = with_cols_in<24, 16, 12, 8, 6>(ctx, cols, [&](auto c) { // one block per CU: Z occupies most of its LDS
             return launch_gp_beta_kernel(ctx, k_gp_beta_lds<decltype(c)::value>, (int)std::min<int64_t>(blocks, (int64_t)ctx->cus), lds_need,
                                          G_dev, ctx->W_dev.get(), out_dev, D, wdoubles);

@@ -6,14 +6,14 @@ before anything is launched.  Nothing here needs a GPU (tests/test_dispatch_rule
 # ---- pg_sweep.hip ------------------------------------------------------------------------------------------------------------
 SW_CH, SW_WAVES = 32, 4                   # :34-42
 SW_TILE = 64 * (SW_CH + 2)                # :43-47
-MB_TILE = 64 * (SW_CH + 4)                # :783-784
-MS_MAX_COLS = 48                          # :965
+MB_TILE = 64 * (SW_CH + 4)                # :773-774
+MS_MAX_COLS = 48                          # :933
 PG_MAX_SWEEP_COLS = 34                    # pg_common.h:12
 COL_SIZES = (2, 3, 4, 6, 8, 12, 16, 24, PG_MAX_SWEEP_COLS)
 
 
 def ms_pick_u(nc):
-    """chunks per load group (pg_sweep.hip:991-999): the U of 8 .. 5 that pads least, the larger on a tie"""
+    """chunks per load group (pg_sweep.hip:958-965): the U of 8 .. 5 that pads least, the larger on a tie"""
     U, best = 8, 1 << 30
     for u in (8, 7, 6, 5):
         padded = (nc + u - 1) // u * u
@@ -23,15 +23,15 @@ def ms_pick_u(nc):
 
 
 def ms_threads(ncg):
-    return 256 if ncg == 3 else 512       # :421
+    return 256 if ncg == 3 else 512       # :411
 
 
 def ms_pitch(cu, mode):
-    return ((cu + 2) | 1) if mode == 2 else ((cu + 1) | 1)   # :1001
+    return ((cu + 2) | 1) if mode == 2 else ((cu + 1) | 1)   # :967
 
 
 def ms_fits(n, cu, mode):
-    """pg_sweep.hip:1003-1006: the B table plus the closing stage of a MODE launch within 160 KiB of LDS, from 5 chunks (33 pools) up"""
+    """pg_sweep.hip:969-972: the B table plus the closing stage of a MODE launch within 160 KiB of LDS, from 5 chunks (33 pools) up"""
     nc = (n + 7) // 8
     U = ms_pick_u(nc)
     ncp = (nc + U - 1) // U * U
@@ -45,7 +45,7 @@ def last_ms_count(cu, mode):
 
 
 def round_cols(c):
-    """pg_sweep.hip:1048-1053: the template width that carries c columns, -1 beyond 34"""
+    """pg_sweep.hip:1005-1010: the template width that carries c columns, -1 beyond 34"""
     for s in COL_SIZES:
         if c <= s:
             return s
@@ -53,7 +53,7 @@ def round_cols(c):
 
 
 def beta_route(n, ncol, colmajor=True, ss=False, env=()):
-    """pg_gp_beta_cols (pg_sweep.hip:1527-1586) for an even ld and an aligned G: (route, template width).  env: the set of
+    """pg_gp_beta_cols (pg_sweep.hip:1484-1544) for an even ld and an aligned G: (route, template width).  env: the set of
     POOLGEN_GP_BETA_* suffixes that are set ("OLD", "VALU", "SCALAR")."""
     cols = round_cols(ncol)
     assert cols > 0
@@ -62,14 +62,14 @@ def beta_route(n, ncol, colmajor=True, ss=False, env=()):
     mfma_lds = (zrows * 16 + SW_WAVES * MB_TILE) * 8
     wdoubles = n_even * cols
     lds_need = (wdoubles + SW_WAVES * SW_TILE) * 8
-    if ms_fits(n, ncol, 1) and "OLD" not in env:                                                       # :1562
+    if ms_fits(n, ncol, 1) and "OLD" not in env:                                                       # :1520
         return "matrix-core", cols
-    if not ss and colmajor and 5 <= ncol <= 16 and mfma_lds <= 150 * 1024 and "VALU" not in env:      # :1565
+    if not ss and colmajor and 5 <= ncol <= 16 and mfma_lds <= 150 * 1024 and "VALU" not in env:      # :1523
         return "beta_mfma", 16
     if (not ss and cols >= 6 and cols % 2 == 0 and cols <= 24 and wdoubles * 8 > 12288 and lds_need <= 150 * 1024
-            and "SCALAR" not in env):                                                                  # :1572-1573
+            and "SCALAR" not in env):                                                                  # :1530-1531
         return "beta_lds", cols
-    return "beta_scalar", cols                                                                         # :1579
+    return "beta_scalar", cols                                                                         # :1537
 
 
 # ---- pg_gp.hip ---------------------------------------------------------------------------------------------------------------
@@ -158,7 +158,7 @@ KIN_WAVES, KIN_PAIR_FLOOR, KIN_FUSE_MAXK = 16, 2.7, 2     # :28, :646, :33
 
 
 def kin_layout(n):
-    """pg_launch_kinship (pg_kinship.hip:685, :698-725, :812, :831): w8 (the 8-wave build up to 64 pools), T tile columns, nb pool
+    """pg_launch_kinship (pg_kinship.hip:685, :698-725, :811, :833): w8 (the 8-wave build up to 64 pools), T tile columns, nb pool
     blocks of Tb tile columns, merged pairs, split, the 13-tile kernel and its narrow-tile bits"""
     T = (n + 15) // 16
     if T <= 13:
@@ -188,8 +188,8 @@ def kin_layout(n):
 
 
 def kin_fuses(n, k):
-    """the fused intercept-only sums: one pool block (:799), phenotypes kept by pg_set_phenotypes (:883: k <= 4 and n <= 256) and
-    at most KIN_FUSE_MAXK traits (:799)"""
+    """the fused intercept-only sums: one pool block (:798), phenotypes kept by pg_set_phenotypes (:874: k <= 4 and n <= 256) and
+    at most KIN_FUSE_MAXK traits (:798)"""
     return kin_layout(n)["nb"] == 1 and n <= 256 and k <= min(4, KIN_FUSE_MAXK)
 
 

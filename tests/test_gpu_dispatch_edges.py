@@ -141,13 +141,13 @@ def test_pool_table_top_edge(engine, oracle):
 
 
 # ---- B. sweep ----------------------------------------------------------------------------------------------------------------
-# Matrix-core sweep while ms_fits(n, cu = m + 1 + k, 0) (pg_sweep.hip:1001-1006, :1345): U = 5..8 chunks per load group, 1 / 2 / 3
+# Matrix-core sweep while ms_fits(n, cu = m + 1 + k, 0) (pg_sweep.hip:967-972, :1308): U = 5..8 chunks per load group, 1 / 2 / 3
 # column groups for cu <= 16 / 32 / 48; above its last pool count the vector-ALU k_ols_sweep<C> with C = round_cols(cu)
 # (:1048-1053: 2, 3, 4, 6, 8, 12, 16, 24, 34).  Last matrix-core pool count: cu = 2 -> 1176, 3 -> 1120, 16 -> 728, 17 -> 336,
 # 32 -> 112, 33 and 34 -> 240.
 @pytest.mark.parametrize("k", [1, 2])
 @pytest.mark.parametrize("n", [
-    285,    # 36 chunks of 8 pools: U = 6 (ms_pick_u, pg_sweep.hip:991-999: the U of 8 .. 5 that pads least, the larger on a tie)
+    285,    # 36 chunks of 8 pools: U = 6 (ms_pick_u, pg_sweep.hip:958-965: the U of 8 .. 5 that pads least, the larger on a tie)
     301,    # 38 chunks: U = 8 (40)
     513,    # 65 chunks: U = 5
     777,    # 98 chunks: U = 7
@@ -200,7 +200,7 @@ def test_sweep_with_covariates_across_column_groups(engine, oracle, n, m, k, ld,
 
 
 def test_sweep_column_limit_is_refused(engine):
-    """cu = m + 1 + k = 35 is more than one sweep launch carries (pg_sweep.hip:1084-1087): PG_ERR_UNSUPPORTED, not a launch."""
+    """cu = m + 1 + k = 35 is more than one sweep launch carries (pg_sweep.hip:1067-1070): PG_ERR_UNSUPPORTED, not a launch."""
     from poolgen_amd import NativeError
     n = 200
     G, Y = make(100, n, 5)
@@ -212,7 +212,7 @@ def test_sweep_column_limit_is_refused(engine):
 
 
 # ---- C. lazy kinship route ---------------------------------------------------------------------------------------------------
-# pg_ols_kinship_dev without K (pg_sweep.hip:1380-1381, ms_pitch :1001): a MODE-2 matrix-core pass when ms_fits(n, 1 + k, 2), whose closing stage has
+# pg_ols_kinship_dev without K (pg_sweep.hip:1330-1331, ms_pitch :967): a MODE-2 matrix-core pass when ms_fits(n, 1 + k, 2), whose closing stage has
 # row pitch (cu + 2) | 1.  Last MODE-2 pool count: k = 1 -> 1120, k = 3 -> 1056, k = 15 -> 672; above it the full route.  (Checked
 # with the MODE-0 pitch instead, the route used to launch up to 1176 / 1120 / 728 pools and fail for want of LDS.)
 LAZY_POINTS = [

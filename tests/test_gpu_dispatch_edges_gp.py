@@ -77,20 +77,20 @@ def same_bits(a, b):
 
 
 # ---- A. the routes of the coefficient pass -----------------------------------------------------------------------------------
-# pg_gp_beta_cols (pg_sweep.hip:1527-1586), in this order: the matrix-core products mode while ms_fits(n, ncol, 1) (:1562; from 33
+# pg_gp_beta_cols (pg_sweep.hip:1484-1544), in this order: the matrix-core products mode while ms_fits(n, ncol, 1) (:1520; from 33
 # pools up to 1176 / 728 / 288 / 144 / 240 pools for 2 / 16 / 20 / 30 / 33-34 columns); k_gp_beta_mfma for column-major output, 5 ..
-# 16 columns and at most 608 pools (:1565: zrows * 16 + 4 tiles of 64 x 36 doubles within 150 KiB); k_gp_beta_lds<C> for even C in 6 ..
-# 24, Z above 12 KiB and Z + 4 tiles of 64 x 34 within 150 KiB (:1572); else the scalar k_gp_beta<C> (:1579).  C = round_cols(ncol).
+# 16 columns and at most 608 pools (:1523: zrows * 16 + 4 tiles of 64 x 36 doubles within 150 KiB); k_gp_beta_lds<C> for even C in 6 ..
+# 24, Z above 12 KiB and Z + 4 tiles of 64 x 34 within 150 KiB (:1530); else the scalar k_gp_beta<C> (:1537).  C = round_cols(ncol).
 # With n_reps = 1 the n_folds * k columns of the one repetition go in one pass (pg_gp.hip:874, :926).
 # (n, p, n_folds, k, route)
 ROUTE_POINTS = [
-    (30, 600, 3, 2, ("beta_mfma", 16)),       # C = 6 below 33 pools (ms_fits: nc >= 5, :1005): the LDS-staged MFMA form
+    (30, 600, 3, 2, ("beta_mfma", 16)),       # C = 6 below 33 pools (ms_fits: nc >= 5, :971): the LDS-staged MFMA form
     (32, 640, 4, 4, ("beta_mfma", 16)),       # C = 16, the last pool count below the matrix-core mode
     (33, 660, 3, 2, ("matrix-core", 6)),      # C = 6, the first matrix-core count
-    (30, 600, 2, 2, ("beta_scalar", 4)),      # C = 4 < 5 columns (:1565): scalar k_gp_beta<4>
+    (30, 600, 2, 2, ("beta_scalar", 4)),      # C = 4 < 5 columns (:1523): scalar k_gp_beta<4>
     (40, 800, 2, 2, ("matrix-core", 4)),      # C = 4 in the matrix-core mode
     (48, 900, 2, 4, ("matrix-core", 8)),      # C = 8
-    (32, 640, 4, 5, ("beta_scalar", 24)),     # C = 20 > 16 columns below 33 pools, Z = 32 * 24 * 8 = 6 KiB <= 12 KiB (:1572): scalar k_gp_beta<24>
+    (32, 640, 4, 5, ("beta_scalar", 24)),     # C = 20 > 16 columns below 33 pools, Z = 32 * 24 * 8 = 6 KiB <= 12 KiB (:1530): scalar k_gp_beta<24>
     (40, 900, 10, 2, ("matrix-core", 24)),    # C = 20 in one pass: the shapes of test_gp_ridge_many_fold_columns with n_reps = 1
     (80, 1500, 10, 2, ("matrix-core", 24)),
     (728, 1500, 4, 4, ("matrix-core", 16)),   # C = 16: last matrix-core count (one column group)
@@ -163,7 +163,7 @@ def test_gp_ols_trait_limit_is_refused(engine, oracle):
     assert rc == 0 and np.allclose(beta, ref, rtol=1e-10, atol=1e-11 * np.abs(ref).max())
 
 
-# The older forms behind their switches (pg_sweep.hip:1562-1573), on shapes the matrix-core mode takes by default.  POOLGEN_GP_BETA_OLD
+# The older forms behind their switches (pg_sweep.hip:1520-1531), on shapes the matrix-core mode takes by default.  POOLGEN_GP_BETA_OLD
 # alone falls to k_gp_beta_mfma (5 .. 16 columns); with _VALU to k_gp_beta_lds<C> (Z above 12 KiB: n_even * C > 1536); _SCALAR only
 # switches the LDS form off, so _OLD + _SCALAR is k_gp_beta_mfma again and the scalar kernel needs all three.
 # (n, p, n_folds, k) -> {switches: route}
@@ -222,7 +222,7 @@ def test_batched_coefficient_passes(engine, oracle, monkeypatch, n, p, n_folds, 
 
 
 # The MLE sums (pg_mle.hip:464) go through the same pass row-major with ss_out_dev: matrix-core from 33 to 1176 pools for the two
-# columns [1 | y]; below and above, the scalar k_gp_beta<2>, the one kernel besides it that writes g'g (pg_sweep.hip:659).
+# columns [1 | y]; below and above, the scalar k_gp_beta<2>, the one kernel besides it that writes g'g (pg_sweep.hip:649).
 # The assertions are those of test_mle_against_the_oracle_and_the_analytic_optimum (tests/test_gpu_mle.py) for m = 0; the oracle gets
 # an n x 0 covariate, so that it forms no kinship and solves no 1200 x 1200 eigenproblem for fits that use neither.
 @pytest.mark.parametrize("n", [24, 1200])

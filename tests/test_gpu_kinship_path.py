@@ -35,7 +35,7 @@ def cmp_fit(got, ref, what=""):
     assert np.max(np.abs(pv[ok] - ref["pval"][ok])) <= PTOL, what + " pval"
 
 
-# The block rules of pg_launch_kinship (pg_kinship.hip:698-725, :812, :831) at their edges, T = ceil(n / 16) tile columns: one pool
+# The block rules of pg_launch_kinship (pg_kinship.hip:698-725, :811, :833) at their edges, T = ceil(n / 16) tile columns: one pool
 # block up to T = 13, where the 13-tile kernel takes over with its narrow-tile bits (3 up to 200 pools, 1 above); two weighted blocks
 # at T = 14; two merged blocks, split in two, at T = 15 and 16; three weighted blocks up to T = 24; merged from T = 25 (four blocks).
 # (p, n, ld, (T, nb, merged, split, narrow-tile bits))
@@ -687,7 +687,7 @@ def test_gp_ridge_path_matches_oracle(engine, oracle, n, p, k, alpha, n_reps):
     assert np.array_equal(lam4, lam) and np.array_equal(perf4, perf) and np.array_equal(beta4.cpu().numpy(), b)
 
 
-# The fused intercept-only sums ride in the kinship pass only with one pool block (pg_kinship.hip:799: up to 208 pools) and at most two
+# The fused intercept-only sums ride in the kinship pass only with one pool block (pg_kinship.hip:798: up to 208 pools) and at most two
 # traits; pg_set_phenotypes keeps no phenotypes at all above 256 pools (:883).  (p, n, k, fused)
 FUSED_EDGE_POINTS = [
     (1500, 200, 1, True),     # the 13-tile kernel with the narrow last column, fused

@@ -49,6 +49,50 @@ def test_no_product_code_touches_the_oracle():
     assert "oracle" not in out
 
 
+CSRC = ROOT / "poolgen_amd" / "csrc"
+
+
+def library_switches():
+    """the names in the switch table of pg_context.hip, in table order"""
+    return re.findall(r'^\s*\{"(POOLGEN_[A-Z0-9_]+)",', (CSRC / "pg_context.hip").read_text(), flags=re.M)
+
+
+def test_the_library_reads_the_environment_in_one_place():
+    """Every switch goes through pg_switch: pg_context.hip holds the library's only getenv (the CLI under host/ has its own)."""
+    for path in CSRC.rglob("*"):
+        if path.is_file() and path.suffix in {".hip", ".cpp", ".h"} and "host" not in path.relative_to(CSRC).parts \
+                and path.name != "pg_context.hip":
+            assert "getenv" not in path.read_text(), path
+    assert len(re.findall(r"getenv\s*\(", (CSRC / "pg_context.hip").read_text())) == 1
+    names = library_switches()
+    assert len(names) == len(set(names)) == 15
+    enum = re.search(r"enum pg_switch_id \{(.*?)\}", (CSRC / "pg_common.h").read_text(), flags=re.S).group(1)
+    ids = re.findall(r"PG_SW_[A-Z0-9_]+", enum)
+    assert ids == [n.replace("POOLGEN_", "PG_SW_") for n in names] + ["PG_SW_COUNT"]     # same switches, same order
+
+
+def test_integration_doc_lists_the_library_switches():
+    """INTEGRATION.md's table and the library's: the same names, both ways."""
+    doc = re.findall(r"^\| `(POOLGEN_[A-Z0-9_]+)` \|", (ROOT / "INTEGRATION.md").read_text(), flags=re.M)
+    assert sorted(doc) == sorted(library_switches())
+
+
+def test_the_tests_force_only_switches_that_exist():
+    """A POOLGEN_* name in a file under tests/ is a switch of the library's table (or a prefix of some, where a comment names a
+    family), so that no test can "force" a route through a variable nothing reads.  The Python-level variables are not the
+    library's: POOLGEN_BENCH_*, POOLGEN_COMM, POOLGEN_TWO_PASS, POOLGEN_HIP_LIB."""
+    table = set(library_switches())
+    python_level = re.compile(r"POOLGEN_(BENCH_[A-Z0-9_]*|COMM|TWO_PASS|HIP_LIB)$")
+    for path in sorted((ROOT / "tests").rglob("*.py")):
+        for name in set(re.findall(r"POOLGEN_[A-Z0-9_]+", path.read_text())):
+            if python_level.match(name):
+                continue
+            if name.endswith("_"):
+                assert any(t.startswith(name) for t in table), f"{path.name}: {name}* matches no switch"
+            else:
+                assert name in table, f"{path.name}: {name} is not a switch of the library"
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful without a GPU")
 def test_fails_loudly_without_gpu(native):
     ctx = C.c_void_p()

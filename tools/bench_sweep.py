@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B timing of k_ols_sweep variants in ONE process (same clocks, same data): tools/bench_sweep.py [pools] [loci] [reps]
-Variants are selected by environment variables the library reads at launch time."""
+"""A/B timing of the sweep kernels in ONE process (same clocks, same data): tools/bench_sweep.py [pools] [loci] [reps]
+SWEEP_VARIANTS lists them: mf (the default dispatch), v1, v2, v2g<N>, mfg<N>; the library reads the switches at launch time."""
 import os, sys, json
 from pathlib import Path
 import numpy as np, torch
@@ -23,36 +23,21 @@ for m in [int(x) for x in os.environ.get('SWEEP_MS', '0,8').split(',')]:
     ref = None
     for rnd in range(2):
         for v in variants:
-            for key in ("POOLGEN_SWEEP_V1", "POOLGEN_SWEEP_V2", "POOLGEN_SWEEP_GRID_MULT", "POOLGEN_SWEEP_NOPF", "POOLGEN_SWEEP_MODE", "POOLGEN_SWEEP_EXP", "POOLGEN_SWEEP_U", "POOLGEN_SWEEP_R"):
+            for key in ("POOLGEN_SWEEP_V1", "POOLGEN_SWEEP_V2", "POOLGEN_SWEEP_GRID_MULT"):
                 os.environ.pop(key, None)
             if v == "v1":
                 os.environ["POOLGEN_SWEEP_V1"] = "1"
             elif v == "v2":
                 os.environ["POOLGEN_SWEEP_V2"] = "1"
-            elif v.startswith("v2exp"):
-                os.environ["POOLGEN_SWEEP_V2"] = "1"
-                os.environ["POOLGEN_SWEEP_EXP"] = v[5:]
-            elif v.startswith("v2mode"):
-                os.environ["POOLGEN_SWEEP_V2"] = "1"
-                os.environ["POOLGEN_SWEEP_MODE"] = v[6:]
-            elif v == "v2nopf":
-                os.environ["POOLGEN_SWEEP_V2"] = "1"
-                os.environ["POOLGEN_SWEEP_NOPF"] = "1"
             elif v.startswith("v2g"):
                 os.environ["POOLGEN_SWEEP_V2"] = "1"
                 os.environ["POOLGEN_SWEEP_GRID_MULT"] = v[3:]
-            elif v.startswith("mfu"):      # "mf" = the product's default (the matrix-core sweep); mfu<U>: chunks per load group
-                os.environ["POOLGEN_SWEEP_U"] = v[3:]
-            elif v.startswith("mfexp"):    # timing experiments (wrong results)
-                os.environ["POOLGEN_SWEEP_EXP"] = v[5:]
-            elif v.startswith("mfr"):      # mfr<ring depth>
-                os.environ["POOLGEN_SWEEP_R"] = v[3:]
-            elif v.startswith("mfg"):      # mfg<blocks per CU>
+            elif v.startswith("mfg"):      # "mf" = the product's default (the matrix-core sweep); mfg<blocks per CU>
                 os.environ["POOLGEN_SWEEP_GRID_MULT"] = v[3:]
             eng.ols_sweep(G, 1, n, out); torch.cuda.synchronize()
             if ref is None:
                 ref = out.clone()
-            elif "mode" not in v and "exp" not in v:
+            else:
                 assert torch.equal(torch.isnan(out[0]), torch.isnan(ref[0])), (v, "NaN pattern")   # (flat columns: NaN on both sides)
                 d = float(torch.nan_to_num(out[0] - ref[0]).abs().max()); dp = float(torch.nan_to_num(out[2] - ref[2]).abs().max())
                 assert d < 1e-9 and dp < 1e-9, (v, d, dp)

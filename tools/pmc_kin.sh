@@ -1,11 +1,10 @@
 #!/bin/bash
 # usage: tools/pmc_kin.sh <tag> <pools> [pools ..] -- HBM traffic of the plain kinship pass per pool count (FETCH_SIZE / WRITE_SIZE passes
-# of rocprofv3 over tools/bench_kinship_n.py), with and without the XCD placement of the block pairs (POOLGEN_KIN_NO_XCD=1)
+# of rocprofv3 over tools/bench_kinship_n.py)
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 : > gpurun_out/pmc_kin_${tag}.txt
-for mode in xcd noxcd; do
-  if [ $mode = noxcd ]; then export POOLGEN_KIN_NO_XCD=1; else unset POOLGEN_KIN_NO_XCD; fi
+mode=xcd # (block pairs placed by XCD: the one mode the launcher has)
   python3 tools/bench_kinship_n.py "$@" 2>/dev/null | sed "s/^/[$mode] /" >> gpurun_out/pmc_kin_${tag}.txt
   for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf gpurun_out/pmc_kin_tmp && mkdir -p gpurun_out/pmc_kin_tmp
@@ -21,5 +20,4 @@ for i in range(0, len(rows), 3):   # tools/bench_kinship_n.py launches the pass 
 PY
     rm -rf gpurun_out/pmc_kin_tmp
   done
-done
 cat gpurun_out/pmc_kin_${tag}.txt
