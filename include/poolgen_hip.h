@@ -402,6 +402,48 @@ int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int
                     const double *pool_sizes, double *d_win, double *d_mean, double *theta_win, double *pi_win);
 
 /* ---------------------------------------------------------------------------------------
+ * gudmc (popgen/gudmc.rs:64-462): Tajima's D peaks and troughs against pairwise Fst.  The stage on top of
+ * pg_tajima_d_dev and pg_fst_dev: Nelder-Mead normal fits (ml_normal_1d, :39-60; argmin 0.8 as pg_mle_kinship_dev
+ * words it, start simplex prepare_solver_neldermead(2, 1), <= 10 000 iterations) on (mu, x),
+ * sigma = EPSILON + (1e24 - EPSILON) / (1 + e^-x), cost = sum of -ln_pdf.  The cost is evaluated from the column's
+ * (count, mean, sum (x - mean)^2), not as the reference's sum over the column: the simplex's path is chaotic under
+ * last-bit changes of the cost, so mu and sigma agree with the reference at the solver's resolution (measured:
+ * DESIGN.md section 3.4e), not bit for bit.
+ * ------------------------------------------------------------------------------------- */
+/* Per column of a row-major table on the device (rows x cols, pitch ld >= cols), over its non-NaN entries: the fitted
+ * mu_dev[cols] and sd_dev[cols]; optional count_dev[cols] (non-NaN entries) and iters_dev[cols] (iterations done;
+ * 10000 = the cap ended the fit).  A column without entries gives (1.5, sigma(1.0)) at 0 iterations, as the reference's
+ * fold over an empty array does.  A +-inf entry has no defined cost (the reference panics): PG_ERR_INVALID.
+ * A column's result depends on its entries alone -- not on cols, ld or the other columns. */
+int pg_normal_fit_dev(pg_ctx *ctx, const double *table_dev, int64_t rows, int64_t cols, int64_t ld, double *mu_dev,
+                      double *sd_dev, int64_t *count_dev, int32_t *iters_dev);
+/* d_win_dev: w x n, D per window and population as pg_tajima_d_dev returns it (copied to the device); the entry rounds it
+ * to 8 decimals, half away from zero, as the reference reads it back from tajima_d's file (tajima_d.rs:164).  fst_win_dev:
+ * w x n*n as pg_fst_dev returns it, pair (a, b) in column a*n + b.  win_chr / win_ini / win_fin (host, w): the windows'
+ * chromosome ids (only equality is used), first and last position.
+ * Per population b, d = its non-NaN D in window order; ROW j of b takes the label of window j of the unfiltered list
+ * (gudmc.rs:168-176: a NaN window in the middle shifts every later value to an earlier window; kept as the reference has
+ * it), is significant iff |d_j - d_mean| >= sigma_threshold (not scaled by d_sd, :180), and has width 0, or
+ * pos_fin - pos_ini plus the previous row's width when that row is on the same chromosome and reaches pos_ini (:180-208).
+ * Outputs, all on the device:
+ *   rows_dev[n] int64, d_mean_dev[n], d_sd_dev[n]                        per population
+ *   fst_mean_dev, fst_sd_dev, width_mean_dev, width_sd_dev [n*n]        per pair (a, b); the width fit runs over b's rows
+ *   row_* [n*n*w], pair-major with pitch w: element (pair i, row j) at i*w + j, specified for j < rows_dev[i % n] only:
+ *     row_window (int64: the row's window = its Fst window), row_d, row_width (an integer, exact), row_width_from_r =
+ *     width - (recombination_rate_cM_per_Mb / 100) * 1e6, row_width_p and row_fst_p (one-tailed: cdf below the mean, else
+ *     1 - cdf, cdf = erfc((mean - x) / (sd sqrt 2)) / 2), row_fst_delta = fst - fst_mean.  Any row_* may be NULL.
+ * Memory: the caller's seven row_* arrays are n*n*w * 8 bytes each (200 pools x 1 496 windows: 0.48 GB each, 3.4 GB in all);
+ * the entry itself holds 2 w n + 3 n*n doubles beside them.
+ * Errors: PG_ERR_INVALID for n < 1, w < 1, a +-inf among a population's D (or in Fst), and a significant row whose label has
+ * pos_fin < pos_ini (the reference's unsigned subtraction overflows). */
+int pg_gudmc_dev(pg_ctx *ctx, const double *d_win_dev, const double *fst_win_dev, int64_t w, int n, const int32_t *win_chr,
+                 const uint64_t *win_ini, const uint64_t *win_fin, double sigma_threshold, double recombination_rate_cM_per_Mb,
+                 int64_t *rows_dev, double *d_mean_dev, double *d_sd_dev, double *fst_mean_dev, double *fst_sd_dev,
+                 double *width_mean_dev, double *width_sd_dev, int64_t *row_window_dev, double *row_d_dev,
+                 double *row_width_dev, double *row_width_from_r_dev, double *row_width_p_dev, double *row_fst_delta_dev,
+                 double *row_fst_p_dev);
+
+/* ---------------------------------------------------------------------------------------
  * Host-side pieces of the path (O(n^3), n = pools): exported so that they can be validated
  * without a GPU and reused by a host integration.
  * ------------------------------------------------------------------------------------- */

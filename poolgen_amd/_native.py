@@ -85,6 +85,8 @@ SIGNATURES = {
     "pg_host_watterson_windows": (_i64, [_vp, _vp, _i64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "pg_watterson_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pg_tajima_d_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pg_normal_fit_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pg_gudmc_dev": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _d, _d] + [_vp] * 14),
     "pg_gp_predict_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i, _vp]),
     "pg_host_sym_eig": (_i, [_vp, _i, _vp, _vp]),
     "pg_host_sym_eig_top": (_i, [_vp, _i, _i, _vp, _vp]),

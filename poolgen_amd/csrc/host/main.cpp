@@ -52,6 +52,7 @@ struct Args {
     // watterson_estimator / tajima_d (an extension): the pool sizes as the phenotype file has them and every locus of a window
     // counted, instead of the reference's fractions and its count
     bool popgen_as_documented = false;
+    double sigma_threshold = 2.0, recombination_rate_cm_per_mb = 0.73; // gudmc (main.rs:119-128)
     // multi-GPU (an extension: the reference's parallel axis is --n-threads, one worker per file chunk, sync.rs:913-939):
     // the input is cut into one contiguous byte range per GPU, each with its own parser threads.  0 = flag absent.
     int n_gpus = 0;
@@ -81,7 +82,8 @@ static int flag_int(const std::string &v, const std::string &flag, int64_t lo = 
 static const char *USAGE =
     "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
     "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
-    "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d\n"
+    "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d,\n"
+    "          gudmc\n"
     "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
     "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
     "                                     writes A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on pileup-derived\n"
@@ -96,8 +98,10 @@ static const char *USAGE =
     "      --keep-p-minus-1                drop the major allele of every locus when loading the matrix\n"
     "  -x, --xxt-eigen-variance-explained <0.75>   ols_iter_with_kinship: the n_eigenvecs rule's threshold\n"
     "      --k-folds <10>  --n-reps <3>  --seed <42>     genomic_prediction_cross_validation\n"
-    "      --window-size-bp <100>  --window-slide-size-bp <50>  --min-loci-per-window <10>   fst, heterozygosity, watterson_estimator, tajima_d\n"
-    "      --popgen-as-documented          watterson_estimator, tajima_d: use the pool sizes as the phenotype file has them and count\n"
+    "      --window-size-bp <100>  --window-slide-size-bp <50>  --min-loci-per-window <10>   fst, heterozygosity, watterson_estimator, tajima_d, gudmc\n"
+    "      --sigma-threshold <2.0>  --recombination-rate-cm-per-mb <0.73>   gudmc: |D - mean| from which a window counts as a peak or\n"
+    "                                      trough (not scaled by the fitted sd, as in the reference), and the rate behind the expected width\n"
+    "      --popgen-as-documented          watterson_estimator, tajima_d, gudmc: use the pool sizes as the phenotype file has them and count\n"
     "                                      the polymorphic loci of every window.  Default: the reference's behaviour -- pool sizes as\n"
     "                                      fractions of their sum (its harmonic sums are then empty: every value is inf or NaN) and\n"
     "                                      its count, which looks the flag up at the window's index instead of the locus\n"
@@ -163,6 +167,10 @@ static Args parse_args(int argc, char **argv) {
         else if (k == "--window-slide-size-bp") a.window_slide_size_bp = flag_u64(val(), k);
         else if (k == "--min-loci-per-window") a.min_loci_per_window = flag_u64(val(), k);
         else if (k == "--popgen-as-documented") a.popgen_as_documented = true;
+        else if (k == "--sigma-threshold") {
+            const std::string t = val();
+            if (!parse_f64_strict(t, a.sigma_threshold)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
+        } else if (k == "--recombination-rate-cm-per-mb") a.recombination_rate_cm_per_mb = parse_valid_freq(val(), k);
         else if (k.rfind("-", 0) == 0) throw std::runtime_error("unknown flag " + k);
         else pos.push_back(k);
     }
@@ -839,6 +847,107 @@ static int run_popgen(const Args &a, Analysis analysis, Ctx &gpu, const double *
     wh.resize(nw); wt.resize(nw);
     const std::string win = std::to_string(a.window_size_bp);
     const std::string time = unix_time_string();
+    if (analysis == Analysis::gudmc) {
+        // gudmc (popgen/gudmc.rs:64-462): tajima_d and fst as above, then the fits, widths and p-values on the GPU, one row per
+        // (pair, row of population b).  The reference reads both tables back from text and takes their labels apart:
+        for (const std::string &c : loc_chr)
+            if (c.find('-') != std::string::npos) // "Window-<chr>_<ini>_<fin>".split("-")[1] (:169)
+                throw std::runtime_error("gudmc: chromosome name `" + c + "` contains `-`; the reference splits its window labels at `-` and fails on it");
+        for (int i = 0; i < n; ++i) {
+            if (pool_names[i].find("_vs_") != std::string::npos) // "<a>_vs_<b>".split("_vs_") (:231)
+                throw std::runtime_error("gudmc: pool name `" + pool_names[i] + "` contains `_vs_`; the reference splits its pair labels there");
+            for (int j = 0; j < i; ++j)
+                if (pool_names[i] == pool_names[j]) // position() finds the first of them (:298)
+                    throw std::runtime_error("gudmc: pool name `" + pool_names[i] + "` occurs twice; the reference matches populations by name");
+        }
+        if (nw <= 0) throw std::runtime_error("There were no windows defined. Please check the sync file, the window size, slide size, and the minimum number of loci per window.");
+        std::vector<int64_t> wc, wseed, wslot;
+        if (!a.popgen_as_documented) {
+            std::cerr << "note: gudmc reproduces the reference: the pool sizes are fractions of their sum, so every Tajima's D is NaN, no population has a row "
+                         "and the file is the header alone; --popgen-as-documented uses the pool sizes as written and counts every locus\n";
+            std::vector<int64_t> h2(L), t2(L);
+            wc.resize(L); wseed.resize(L); wslot.resize(L);
+            const int64_t nw2 = pg_host_watterson_windows(chr_id.data(), loc_pos.data(), L, a.window_size_bp, a.window_slide_size_bp,
+                                                          a.min_loci_per_window, h2.data(), t2.data(), wc.data(), wseed.data(), wslot.data());
+            h2.resize(nw2); t2.resize(nw2);
+            if (h2 != wh || t2 != wt) throw std::runtime_error("internal error: the two window loops disagree");
+        }
+        const size_t nn = (size_t)n * n, wn = (size_t)nw * n, rows_all = nn * (size_t)nw;
+        // A window whose tail lies before its head (the stale tail of a ditched last slot; the reference's own gudmc test has one,
+        // gudmc.rs:500-510) is an empty slice there: mean_axis gives None and both tables hold NaN (pi.rs:87-90, fst.rs:194-197).
+        // The tajima_d and fst entry points refuse such a window, so they see the others and its rows stay NaN.
+        std::vector<int64_t> keep, kh, kt, kc, ksd, ksl;
+        for (int64_t w = 0; w < nw; ++w)
+            if (wh[w] <= wt[w]) {
+                keep.push_back(w); kh.push_back(wh[w]); kt.push_back(wt[w]);
+                if (!wc.empty()) { kc.push_back(wc[w]); ksd.push_back(wseed[w]); ksl.push_back(wslot[w]); }
+            }
+        const int64_t nk = (int64_t)keep.size();
+        const int64_t *c = kc.empty() ? nullptr : kc.data(), *sd = kc.empty() ? nullptr : ksd.data(), *sl = kc.empty() ? nullptr : ksl.data();
+        std::vector<double> dw(wn, std::nan("")), fw((size_t)nw * nn, std::nan(""));
+        if (nk > 0) {
+            std::vector<double> dk((size_t)nk * n), dm(n), fm(nn), fk((size_t)nk * nn);
+            gpu.ok(pg_tajima_d_dev(gpu.c, G_dev, cov_dev, p, n, ld, locus_col.data(), L, kh.data(), kt.data(), c, sd, sl, nk, pool_sizes.data(),
+                                   dk.data(), dm.data(), nullptr, nullptr), "gudmc (tajima_d)");
+            gpu.ok(pg_fst_dev(gpu.c, G_dev, cov_dev, p, n, ld, locus_col.data(), L, kh.data(), kt.data(), nk, fm.data(), fk.data()), "gudmc (fst)");
+            for (int64_t q = 0; q < nk; ++q) {
+                std::copy(dk.begin() + (size_t)q * n, dk.begin() + (size_t)(q + 1) * n, dw.begin() + (size_t)keep[q] * n);
+                std::copy(fk.begin() + (size_t)q * nn, fk.begin() + (size_t)(q + 1) * nn, fw.begin() + (size_t)keep[q] * nn);
+            }
+        }
+        std::vector<int32_t> wchr(nw);
+        std::vector<uint64_t> wini(nw), wfin(nw);
+        for (int64_t w = 0; w < nw; ++w) { wchr[w] = chr_id[wh[w]]; wini[w] = loc_pos[wh[w]]; wfin[w] = loc_pos[wt[w]]; }
+        // device: [D | Fst] in, [per population: 2 n | per pair: 4 nn | per row: 6 n^2 w] doubles and [rows: n | window: n^2 w] integers out
+        const size_t n_f64 = 2 * (size_t)n + 4 * nn + 6 * rows_all, n_i64 = (size_t)n + rows_all;
+        DeviceBuf<double> tabs(sizeof(double) * (wn + (size_t)nw * nn), "gudmc: tables"), of(sizeof(double) * n_f64, "gudmc: the rows' values");
+        DeviceBuf<int64_t> oi(sizeof(int64_t) * n_i64, "gudmc: the rows' windows");
+        hip_ok(hipMemcpy(tabs.get(), dw.data(), sizeof(double) * wn, hipMemcpyHostToDevice), "gudmc: H2D");
+        hip_ok(hipMemcpy(tabs.get() + wn, fw.data(), sizeof(double) * (size_t)nw * nn, hipMemcpyHostToDevice), "gudmc: H2D");
+        double *o = of.get();
+        gpu.ok(pg_gudmc_dev(gpu.c, tabs.get(), tabs.get() + wn, nw, n, wchr.data(), wini.data(), wfin.data(), a.sigma_threshold,
+                            a.recombination_rate_cm_per_mb, oi.get(), o, o + n, o + 2 * n, o + 2 * n + nn, o + 2 * n + 2 * nn, o + 2 * n + 3 * nn,
+                            oi.get() + n, o + 2 * n + 4 * nn, o + 2 * n + 4 * nn + rows_all, o + 2 * n + 4 * nn + 2 * rows_all,
+                            o + 2 * n + 4 * nn + 3 * rows_all, o + 2 * n + 4 * nn + 4 * rows_all, o + 2 * n + 4 * nn + 5 * rows_all), "gudmc");
+        std::vector<double> hf(n_f64);
+        std::vector<int64_t> hi(n_i64);
+        hip_ok(hipMemcpy(hf.data(), of.get(), sizeof(double) * n_f64, hipMemcpyDeviceToHost), "gudmc: D2H");
+        hip_ok(hipMemcpy(hi.data(), oi.get(), sizeof(int64_t) * n_i64, hipMemcpyDeviceToHost), "gudmc: D2H");
+        lap("gudmc on the GPU");
+        const double *d_mean = hf.data(), *d_sd = d_mean + n, *f_mean = d_sd + n, *f_sd = f_mean + nn;
+        const double *r_d = hf.data() + 2 * n + 4 * nn, *r_width = r_d + rows_all, *r_wdev = r_width + rows_all, *r_wp = r_wdev + rows_all,
+                     *r_delta = r_wp + rows_all, *r_fp = r_delta + rows_all;
+        const int64_t *r_win = hi.data() + n;
+        std::vector<int64_t> first(nn + 1, 0); // the first line of every pair (:433-434)
+        for (size_t i = 0; i < nn; ++i) first[i + 1] = first[i] + hi[i % n];
+        std::string out = a.output;
+        if (out.empty()) out = basename_no_ext(a.fname) + "-gudmc-" + time + ".csv"; // :383-401
+        FILE *fo = create_new(out);
+        fputs("pop_a,pop_b,chr,pos_ini,pos_fin,mean_tajima_d_pop_b,mean_fst,sd_tajima_d_pop_b,sd_fst,tajima_d_pop_b,tajima_width_pop_b,"
+              "tajima_width_deviation_from_r_pop_b,tajima_width_one_tail_pval_pop_b,fst_delta,fst_delta_one_tail_pval\n", fo);
+        write_rows_parallel(fo, first[nn], a.n_threads, [&](int64_t r, std::string &text) { // :435-455
+            const size_t i = (size_t)(std::upper_bound(first.begin(), first.end(), r) - first.begin()) - 1;
+            const size_t e = i * (size_t)nw + (size_t)(r - first[i]);
+            const int pa = (int)(i / n), pb = (int)(i % n);
+            const int64_t w = r_win[e];
+            text += pool_names[pa] + "," + pool_names[pb] + "," + loc_chr[wh[w]] + "," + std::to_string(loc_pos[wh[w]]) + "," +
+                    std::to_string(loc_pos[wt[w]]) + ",";
+            append_roundup_own(text, d_mean[pb], 7); text.push_back(',');
+            append_roundup_own(text, f_mean[i], 7); text.push_back(',');
+            append_roundup_own(text, d_sd[pb], 7); text.push_back(',');
+            append_roundup_own(text, f_sd[i], 7); text.push_back(',');
+            append_rust_display(text, r_d[e]); text.push_back(',');
+            append_rust_display(text, r_width[e]); text.push_back(',');
+            append_rust_display(text, r_wdev[e]); text.push_back(',');
+            append_roundup_own(text, r_wp[e], 7); text.push_back(',');
+            append_roundup_own(text, r_delta[e], 7); text.push_back(',');
+            append_roundup_own(text, r_fp[e], 7); text.push_back('\n');
+        });
+        fclose(fo);
+        lap("write CSV");
+        std::cout << out << "\n";
+        return done_ok();
+    }
     if (!is_fst) {
         // one row per pool: name, mean across windows, the windows (pi.rs:160-188, watterson_theta.rs:244-287, tajima_d.rs:127-169)
         std::string out = a.output;
@@ -1041,15 +1150,15 @@ static int run(int argc, char **argv) {
         {"mle_iter_with_kinship", Analysis::mle_iter_with_kinship},
         {"genomic_prediction_cross_validation", Analysis::genomic_prediction_cross_validation}, {"fst", Analysis::fst},
         {"heterozygosity", Analysis::heterozygosity}, {"watterson_estimator", Analysis::watterson_estimator},
-        {"tajima_d", Analysis::tajima_d}, {"pileup2sync", Analysis::pileup2sync}};
+        {"tajima_d", Analysis::tajima_d}, {"gudmc", Analysis::gudmc}, {"pileup2sync", Analysis::pileup2sync}};
     const auto found = known.find(a.analysis);
     if (found == known.end())
         throw std::runtime_error("Invalid analysis utility for this build: `" + a.analysis +
                                  "` (available: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship, "
-                                 "mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d)");
+                                 "mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d, gudmc)");
     const Analysis analysis = found->second;
-    if (a.popgen_as_documented && analysis != Analysis::watterson_estimator && analysis != Analysis::tajima_d)
-        throw std::runtime_error("--popgen-as-documented applies to watterson_estimator and tajima_d");
+    if (a.popgen_as_documented && analysis != Analysis::watterson_estimator && analysis != Analysis::tajima_d && analysis != Analysis::gudmc)
+        throw std::runtime_error("--popgen-as-documented applies to watterson_estimator, tajima_d and gudmc");
     if (a.generate_plots || a.sig_only)
         throw std::runtime_error("--generate-plots / --output-sig-snps-only call the reference's python scripts and are out of scope here");
     if (a.phen_format != "default" && a.phen_format != "gwalpha_fmt")
@@ -1141,7 +1250,7 @@ static int run(int argc, char **argv) {
     GenotypesAndPhenotypes genotypes_and_phenotypes =
         into_genotypes_and_phenotypes(gpu, sb, ph, flt, kpm1, /*remove_missing=*/!popgen, /*with_coverages=*/popgen, lap);
     GenotypesAndPhenotypes &g = genotypes_and_phenotypes;
-    if (popgen) // fst / heterozygosity / watterson_estimator / tajima_d use every pool (main.rs:427-485)
+    if (popgen) // fst / heterozygosity / watterson_estimator / tajima_d / gudmc use every pool (main.rs:427-502)
         return run_popgen(a, analysis, gpu, g.intercept_and_allele_frequencies.get(), g.coverages.get(), g.p, g.n, g.ld, g.chromosome, g.position,
                           g.pool_names, a.popgen_as_documented ? ph.pool_sizes_as_written : ph.pool_sizes, lap);
     if (analysis == Analysis::genomic_prediction_cross_validation) { // genomic_prediction_cross_validation (main.rs:397-426)

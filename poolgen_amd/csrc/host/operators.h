@@ -40,11 +40,11 @@ struct LocusCountsAndPhenotypes { // structs_and_traits.rs:131-136
 // What the CLI can be asked for (main.rs:26-143); the first five are the per-locus operators.
 enum class Analysis {
     chisq_test, pearson_corr, ols_iter, fisher_exact_test, gwalpha,
-    ols_iter_with_kinship, mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d,
+    ols_iter_with_kinship, mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d, gudmc,
     pileup2sync
 };
 inline bool per_locus(Analysis a) { return a <= Analysis::gwalpha; }
-inline bool popgen(Analysis a) { return a >= Analysis::fst && a <= Analysis::tajima_d; } // all pools, coverages, windows (main.rs:427-485)
+inline bool popgen(Analysis a) { return a >= Analysis::fst && a <= Analysis::gudmc; } // all pools, coverages, windows (main.rs:427-502)
 inline bool counts_only(Analysis a) { return a == Analysis::chisq_test || a == Analysis::fisher_exact_test; } // one row per locus, no phenotype used
 
 // Formats the rows of one locus exactly as the reference's operators do; shared with the CLI's writer.

@@ -8,6 +8,7 @@ Method names follow the reference operators they stand in for:
   fisher               tables::fisher                (tables/fisher_exact_test.rs:32-130)
   gwalpha              gwas::gwalpha_ls / gwalpha_ml (gwas/gwalpha.rs:281-380)
   gp_ols               gp::ols                       (gp/ols.rs:8-101)
+  gudmc                popgen::gudmc                 (popgen/gudmc.rs:64-462)
 All heavy arguments are torch CUDA tensors (device memory owned by torch); results are
 torch CUDA tensors.  Everything is computed by libpoolgen_hip.so.
 """
@@ -486,6 +487,62 @@ class Engine:
                                               ps.ctypes.data, d.ctypes.data, mean.ctypes.data, theta.ctypes.data,
                                               pi.ctypes.data), "pg_tajima_d_dev")
         return d, mean, theta, pi
+
+    def _table(self, a) -> torch.Tensor:
+        """a 2-D fp64 table (numpy or torch) as a contiguous tensor on this engine's GPU"""
+        dev = torch.device("cuda", self.device)
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64, order="C"))  # a copy: writable
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if t.dim() != 2:
+            raise ValueError("expected a 2-D table")
+        return t
+
+    def normal_fit(self, table):
+        """The normal fit of popgen::gudmc (ml_normal_1d, popgen/gudmc.rs:39-60) to every column of a rows x cols table over
+        its non-NaN entries: (mu [cols], sd [cols], count [cols] int64, iters [cols] int32), CUDA tensors."""
+        t = self._table(table)
+        rows, cols = t.shape
+        if cols < 1:
+            raise ValueError("normal_fit: the table has no columns")
+        mu = torch.empty(cols, dtype=torch.float64, device=t.device); sd = torch.empty_like(mu)
+        count = torch.empty(cols, dtype=torch.int64, device=t.device)
+        iters = torch.empty(cols, dtype=torch.int32, device=t.device)
+        self._check(self._lib.pg_normal_fit_dev(self._ctx, t.data_ptr() if rows else None, rows, cols, cols, mu.data_ptr(),
+                                                sd.data_ptr(), count.data_ptr(), iters.data_ptr()), "pg_normal_fit_dev")
+        return mu, sd, count, iters
+
+    def gudmc_from_tables(self, d_win, fst_win, win_chr, win_ini, win_fin, sigma_threshold: float = 2.0,
+                          recombination_rate_cM_per_Mb: float = 0.73) -> dict:
+        """popgen::gudmc (popgen/gudmc.rs:64-462) from D per window [w x n] and Fst per window [w x n*n] (tajima_d's and
+        fst's tables) and the windows' chromosome ids, first and last positions.  Returns CUDA tensors: rows [n], d_mean,
+        d_sd [n]; fst_mean, fst_sd, width_mean, width_sd [n*n]; and per (pair, row) [n*n x w], specified for
+        row < rows[pair % n]: window, d, width, width_dev, width_p, fst_delta, fst_p."""
+        d = self._table(d_win); f = self._table(fst_win)
+        w, n = d.shape
+        if f.shape != (w, n * n):
+            raise ValueError("gudmc: fst_win must be w x n*n for a w x n d_win")
+        ch = np.ascontiguousarray(win_chr, dtype=np.int32)
+        ini = np.ascontiguousarray(win_ini, dtype=np.uint64); fin = np.ascontiguousarray(win_fin, dtype=np.uint64)
+        if not (len(ch) == len(ini) == len(fin) == w):
+            raise ValueError("gudmc: win_chr, win_ini and win_fin need one entry per window")
+        dev = d.device
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        out = dict(rows=torch.empty(n, dtype=torch.int64, device=dev), d_mean=f64(n), d_sd=f64(n), fst_mean=f64(n * n),
+                   fst_sd=f64(n * n), width_mean=f64(n * n), width_sd=f64(n * n),
+                   window=torch.empty((n * n, w), dtype=torch.int64, device=dev), d=f64(n * n, w), width=f64(n * n, w),
+                   width_dev=f64(n * n, w), width_p=f64(n * n, w), fst_delta=f64(n * n, w), fst_p=f64(n * n, w))
+        self._check(self._lib.pg_gudmc_dev(self._ctx, d.data_ptr(), f.data_ptr(), w, n, ch.ctypes.data, ini.ctypes.data,
+                                           fin.ctypes.data, float(sigma_threshold), float(recombination_rate_cM_per_Mb),
+                                           *[t.data_ptr() for t in out.values()]), "pg_gudmc_dev")
+        return out
+
+    def gudmc(self, G, cov, locus_col, win_head, win_tail, win_chr, win_ini, win_fin, pool_sizes,
+              sigma_threshold: float = 2.0, recombination_rate_cM_per_Mb: float = 0.73, count=None, n: int | None = None) -> dict:
+        """tajima_d, fst and gudmc_from_tables in one call; count as for tajima_d.  The two tables come down from the device and
+        go up again (pg_tajima_d_dev and pg_fst_dev return host tables): w * (n + n*n) doubles against n*n*w rows out."""
+        d_win = self.tajima_d(G, cov, locus_col, win_head, win_tail, pool_sizes, count=count, n=n)[0]
+        fst_win = self.fst(G, cov, locus_col, win_head, win_tail, n=n)[1]
+        return self.gudmc_from_tables(d_win, fst_win, win_chr, win_ini, win_fin, sigma_threshold, recombination_rate_cM_per_Mb)
 
     # ---- genomic prediction -------------------------------------------------------------------
     def gp_xxt(self, G: torch.Tensor, n: int | None = None) -> torch.Tensor:

@@ -1,8 +1,10 @@
-"""Throughput of fst / theta_pi / tajima_d / theta_watterson on a resident synthetic matrix:
+"""Throughput of fst / theta_pi / tajima_d / theta_watterson / gudmc on a resident synthetic matrix:
     python tools/bench_popgen.py [pools] [loci] [--rounds R] [--baseline-lib other/libpoolgen_hip.so]
 Every leg is warmed up once, then the legs alternate for R rounds in this one process and the median wall time of each is
 printed (one JSON line per leg).  --baseline-lib adds a `theta_pi_baseline` leg: pg_pi_dev of another build of the library
-(e.g. the previous commit's) on the same matrix and windows, loaded beside this one."""
+(e.g. the previous commit's) on the same matrix and windows, loaded beside this one.
+The gudmc legs: `gudmc_stage` = pg_gudmc_dev alone on the two tables already on the device, `gudmc` = tajima_d + fst + the stage
+(Engine.gudmc); one more line gives the histogram of the iterations the D and Fst fits took (10000 = the cap)."""
 import argparse
 import ctypes as C
 import json
@@ -38,6 +40,11 @@ legs = [("theta_pi", lambda: eng.theta_pi(G, cov, starts, wh, wt, n=n)),
         ("tajima_d", lambda: eng.tajima_d(G, cov, starts, wh, wt, ps, n=n)),          # counted mode
         ("theta_watterson", lambda: eng.theta_watterson(G, starts, wh, wt, ps, n=n)),
         ("fst", lambda: eng.fst(G, cov, starts, wh, wt, n=n))]
+wchr, wini, wfin = chrom[wh], pos[wh], pos[wt]
+d_tab = torch.from_numpy(eng.tajima_d(G, cov, starts, wh, wt, ps, n=n)[0]).cuda()
+f_tab = torch.from_numpy(eng.fst(G, cov, starts, wh, wt, n=n)[1]).cuda()
+legs += [("gudmc_stage", lambda: eng.gudmc_from_tables(d_tab, f_tab, wchr, wini, wfin)),
+         ("gudmc", lambda: eng.gudmc(G, cov, starts, wh, wt, wchr, wini, wfin, ps, n=n))]
 if args.baseline_lib:
     base = C.CDLL(args.baseline_lib)
     base.pg_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
@@ -65,6 +72,11 @@ for _ in range(args.rounds):
         torch.cuda.synchronize()
         times[name].append(time.perf_counter() - t0)
 pairs = n * (n + 1) // 2
+iters = torch.cat([eng.normal_fit(torch.round(d_tab * 1e8) / 1e8)[3], eng.normal_fit(f_tab)[3]]).cpu().numpy()
+edges = [0, 1, 50, 100, 150, 200, 300, 500, 1000, 5000, 10000, 10001]
+print(json.dumps({"op": "gudmc_fit_iterations", "pools": n, "windows": int(len(wh)), "fits": int(iters.size),
+                  "median": float(np.median(iters)), "at_cap": int((iters == 10000).sum()), "edges": edges,
+                  "histogram": np.histogram(iters, bins=edges)[0].tolist()}))
 for name, _ in legs:
     dt = statistics.median(times[name])
     print(json.dumps({"op": name, "pools": n, "loci": nl, "columns": int(G.shape[0]), "windows": int(len(wh)), "rounds": args.rounds,
