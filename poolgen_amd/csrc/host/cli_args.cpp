@@ -1,0 +1,183 @@
+// cli_args.cpp -- the flags of `poolgen`, compatible with the reference CLI's (src/main.rs:26-143): parser, usage, checks.  No HIP.
+#include "cli_args.h"
+#include "host_util.h"
+#include <algorithm>
+#include <climits>
+#include <iostream>
+#include <sstream>
+#include <stdexcept>
+
+using namespace pgh;
+
+static double parse_valid_freq(const std::string &v, const std::string &flag) { // helpers.rs:93-100
+    double x = 0.0;
+    if (!parse_f64_strict(v, x)) throw std::runtime_error("`" + v + "` isn't a valid number (" + flag + ")");
+    if (x < 0.0 || x > 1.0) throw std::runtime_error("Value must be between 0.0 and 1.0, got `" + rust_display(x) + "` (" + flag + ")");
+    return x;
+}
+
+// integer flag values as clap's `parse::<usize / u64>()` reads them: digits only, nothing after them, no sign for the unsigned
+static uint64_t flag_u64(const std::string &v, const std::string &flag) {
+    uint64_t x = 0;
+    if (!parse_u64_strict(v, x)) throw std::runtime_error("invalid value `" + v + "` for " + flag + ": a non-negative integer is expected");
+    return x;
+}
+static int flag_int(const std::string &v, const std::string &flag, int64_t lo = 0) {
+    int64_t x = 0;
+    if (!parse_i64_strict(v, x) || x < lo || x > INT32_MAX)
+        throw std::runtime_error("invalid value `" + v + "` for " + flag + ": an integer >= " + std::to_string(lo) + " is expected");
+    return (int)x;
+}
+
+// the names of the analyses that `pick` takes, as the messages list them: "a, b, c", or "a, b and c" with last = " and "
+static std::string analysis_names(bool (*pick)(Analysis), const char *last = ", ") {
+    std::vector<std::string> names;
+    for (const AnalysisName &x : ANALYSES) if (pick(x.id)) names.push_back(x.name);
+    std::string text;
+    for (size_t i = 0; i < names.size(); ++i) text += (i == 0 ? "" : i + 1 == names.size() ? last : ", ") + names[i];
+    return text;
+}
+static bool takes_n_gpus(Analysis a) { return per_locus(a) || a == Analysis::ols_iter_with_kinship; }
+
+// (the help text also names analyses in prose, here and at the --window-*, --popgen-as-documented and --n-gpus flags)
+static const char *USAGE =
+    "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
+    "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
+    "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d,\n"
+    "          gudmc\n"
+    "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
+    "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
+    "                                     writes A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on pileup-derived\n"
+    "                                     counts the default N removal drops the DELETION column and --keep-ns keeps it)\n"
+    "  -p, --phen-fname <file>            delimited file: pool name, pool size, trait value(s)\n"
+    "  -o, --output <file>                must not exist; default: derived from the input name and the time\n"
+    "      --phen-delim <,>  --phen-name-col <0>  --phen-pool-size-col <1>  --phen-value-col <2[,3..]>\n"
+    "      --phen-format <default|gwalpha_fmt>   gwalpha_fmt: the GWAlpha.py file (Pheno_name=, sig=, MIN=, MAX=, perc=[..], q=[..]); gwalpha needs it\n"
+    "      --gwalpha-method <ML|LS>        gwalpha: maximum likelihood (the default, and what any other value means) or least squares\n"
+    "      --max-base-error-rate <0.01>  --min-coverage-depth <1>  --min-coverage-breadth <1.0>\n"
+    "      --min-allele-frequency <0.001>  --max-missingness-rate <0.0>  --keep-ns  --keep-lowercase-reference\n"
+    "      --keep-p-minus-1                drop the major allele of every locus when loading the matrix\n"
+    "  -x, --xxt-eigen-variance-explained <0.75>   ols_iter_with_kinship: the n_eigenvecs rule's threshold\n"
+    "      --k-folds <10>  --n-reps <3>  --seed <42>     genomic_prediction_cross_validation\n"
+    "      --window-size-bp <100>  --window-slide-size-bp <50>  --min-loci-per-window <10>   fst, heterozygosity, watterson_estimator, tajima_d, gudmc\n"
+    "      --sigma-threshold <2.0>  --recombination-rate-cm-per-mb <0.73>   gudmc: |D - mean| from which a window counts as a peak or\n"
+    "                                      trough (not scaled by the fitted sd, as in the reference), and the rate behind the expected width\n"
+    "      --popgen-as-documented          watterson_estimator, tajima_d, gudmc: use the pool sizes as the phenotype file has them and count\n"
+    "                                      the polymorphic loci of every window.  Default: the reference's behaviour -- pool sizes as\n"
+    "                                      fractions of their sum (its harmonic sums are then empty: every value is inf or NaN) and\n"
+    "                                      its count, which looks the flag up at the window's index instead of the locus\n"
+    "      --n-threads <1>                 parser / writer threads\n"
+    "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
+    "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
+    "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
+    "                                      all-reduced over the GPUs with RCCL; the kinship path then needs an input sorted by\n"
+    "                                      (chromosome, position)\n"
+    "environment: PGH_TIMING=1 prints the phases' wall-clock on stderr\n";
+
+Args parse_args(int argc, char **argv) {
+    Args a;
+    for (int i = 1; i < argc; ++i)
+        if (std::string(argv[i]) == "-h" || std::string(argv[i]) == "--help") { std::cout << USAGE; std::exit(0); }
+    std::vector<std::string> pos;
+    for (int i = 1; i < argc; ++i) {
+        std::string k = argv[i], v;
+        auto eq = k.find('=');
+        bool has_v = false;
+        if (k.rfind("--", 0) == 0 && eq != std::string::npos) { v = k.substr(eq + 1); k = k.substr(0, eq); has_v = true; }
+        auto val = [&]() -> std::string {
+            if (has_v) return v;
+            if (i + 1 >= argc) throw std::runtime_error("missing value for " + k);
+            return argv[++i];
+        };
+        if (k == "-f" || k == "--fname") a.fname = val();
+        else if (k == "-o" || k == "--output") a.output = val();
+        else if (k == "-p" || k == "--phen-fname") a.phen_fname = val();
+        else if (k == "--phen-delim") a.phen_delim = val();
+        else if (k == "--phen-format") a.phen_format = val();
+        else if (k == "--gwalpha-method") a.gwalpha_method = val();
+        else if (k == "--phen-name-col") a.phen_name_col = flag_int(val(), k);
+        else if (k == "--phen-pool-size-col") a.phen_pool_size_col = flag_int(val(), k);
+        else if (k == "--phen-value-col") {
+            a.phen_value_col.clear();
+            std::stringstream ss(val());
+            std::string t;
+            while (std::getline(ss, t, ',')) a.phen_value_col.push_back(flag_int(t, k));
+        } else if (k == "--n-threads") a.n_threads = flag_int(val(), k, 1);
+        else if (k == "--max-base-error-rate") a.max_base_error_rate = parse_valid_freq(val(), k);
+        else if (k == "--min-coverage-breadth") a.min_coverage_breadth = parse_valid_freq(val(), k);
+        else if (k == "--min-coverage-depth") a.min_coverage_depth = flag_u64(val(), k);
+        else if (k == "--min-allele-frequency") a.min_allele_frequency = parse_valid_freq(val(), k);
+        else if (k == "--max-missingness-rate") a.max_missingness_rate = parse_valid_freq(val(), k);
+        else if (k == "-x" || k == "--xxt-eigen-variance-explained") a.xxt = parse_valid_freq(val(), k);
+        else if (k == "--keep-ns") a.keep_ns = true;
+        else if (k == "--keep-p-minus-1") a.keep_p_minus_1 = true;
+        else if (k == "--generate-plots") a.generate_plots = true;
+        else if (k == "--output-sig-snps-only") a.sig_only = true;
+        else if (k == "--keep-lowercase-reference") a.keep_lowercase_reference = true; // pileup inputs only (pileup.rs:280-299)
+        else if (k == "--stream-chunk-mb") a.stream_chunk_mb = flag_int(val(), k);
+        else if (k == "--n-gpus") a.n_gpus = flag_int(val(), k, 1);
+        else if (k == "--gpu-ids") {
+            std::stringstream ss(val());
+            std::string t;
+            while (std::getline(ss, t, ',')) a.gpu_ids.push_back(flag_int(t, k));
+        }
+        else if (k == "--k-folds") a.k_folds = flag_int(val(), k, 1);
+        else if (k == "--n-reps") a.n_reps = flag_int(val(), k, 1);
+        else if (k == "--seed") a.seed = flag_u64(val(), k);
+        else if (k == "--window-size-bp") a.window_size_bp = flag_u64(val(), k);
+        else if (k == "--window-slide-size-bp") a.window_slide_size_bp = flag_u64(val(), k);
+        else if (k == "--min-loci-per-window") a.min_loci_per_window = flag_u64(val(), k);
+        else if (k == "--popgen-as-documented") a.popgen_as_documented = true;
+        else if (k == "--sigma-threshold") {
+            const std::string t = val();
+            if (!parse_f64_strict(t, a.sigma_threshold)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
+        } else if (k == "--recombination-rate-cm-per-mb") a.recombination_rate_cm_per_mb = parse_valid_freq(val(), k);
+        else if (k.rfind("-", 0) == 0) throw std::runtime_error("unknown flag " + k);
+        else pos.push_back(k);
+    }
+    if (pos.size() != 1) throw std::runtime_error("usage: poolgen <analysis> -f <sync> -p <phen.csv> [flags]   (--help lists them)");
+    a.analysis = pos[0];
+    if (a.fname.empty() || a.phen_fname.empty()) throw std::runtime_error("-f/--fname and -p/--phen-fname are required");
+    if (!a.gpu_ids.empty()) {
+        if (a.n_gpus == 0) a.n_gpus = (int)a.gpu_ids.size();
+        if ((int)a.gpu_ids.size() != a.n_gpus) throw std::runtime_error("--gpu-ids must list exactly --n-gpus devices");
+    }
+    return a;
+}
+
+PileupFilter pileup_filter(const Args &a, const std::vector<double> &pool_sizes) {
+    PileupFilter pf;
+    pf.remove_ns = !a.keep_ns;
+    pf.keep_lowercase_reference = a.keep_lowercase_reference;
+    pf.max_base_error_rate = a.max_base_error_rate;
+    pf.min_coverage_depth = a.min_coverage_depth;
+    pf.min_coverage_breadth = a.min_coverage_breadth;
+    pf.min_allele_frequency = a.min_allele_frequency;
+    pf.pool_sizes = pool_sizes;
+    return pf;
+}
+
+Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
+    const AnalysisName *found = std::find_if(std::begin(ANALYSES), std::end(ANALYSES), [&](const AnalysisName &x) { return a.analysis == x.name; });
+    if (found == std::end(ANALYSES))
+        throw std::runtime_error("Invalid analysis utility for this build: `" + a.analysis + "` (available: " + analysis_names([](Analysis) { return true; }) + ")");
+    const Analysis analysis = found->id;
+    if (a.popgen_as_documented && analysis != Analysis::watterson_estimator && analysis != Analysis::tajima_d && analysis != Analysis::gudmc)
+        throw std::runtime_error("--popgen-as-documented applies to watterson_estimator, tajima_d and gudmc");
+    if (a.generate_plots || a.sig_only)
+        throw std::runtime_error("--generate-plots / --output-sig-snps-only call the reference's python scripts and are out of scope here");
+    if (a.phen_format != "default" && a.phen_format != "gwalpha_fmt")
+        throw std::runtime_error("Invalid phenotype format. Please select: 'default' or 'gwalpha_fmt'"); // phen.rs:161-164
+    gwalpha_fmt = a.phen_format == "gwalpha_fmt";
+    if (analysis == Analysis::gwalpha && !gwalpha_fmt)
+        throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "
+                                 "(Pheno_name=, sig=, MIN=, MAX=, perc=[..], q=[..])");
+    if (gwalpha_fmt && analysis != Analysis::gwalpha && analysis != Analysis::pileup2sync)
+        throw std::runtime_error("--phen-format gwalpha_fmt is read by gwalpha and pileup2sync; `" + a.analysis + "` needs the default phenotype file");
+    return analysis;
+}
+
+void check_n_gpus(const Args &a, Analysis analysis) {
+    if (a.n_gpus > 0 && !takes_n_gpus(analysis))
+        throw std::runtime_error("--n-gpus applies to " + analysis_names(takes_n_gpus, " and ") + "; `" + a.analysis + "` runs on one GPU");
+}

@@ -1,0 +1,203 @@
+// cli_popgen.cpp -- fst (popgen/fst.rs:10-261), heterozygosity = pi (popgen/pi.rs:115-190), watterson_estimator
+// (popgen/watterson_theta.rs:191-289), tajima_d (popgen/tajima_d.rs:10-171) and gudmc on the loaded matrix: loci and windows on the
+// host (popgen_plan.h), the per-locus arithmetic and the means on the GPU, the files as written by the reference.
+#include "cli.h"
+#include "popgen_plan.h"
+
+// What pg_gudmc_dev fills, as it lies in one block of doubles (2 values per population, 4 per pair, 6 per row, n^2 w rows) and
+// one of integers (rows per population, the rows' windows): over the device blocks for the call, over their host copies for the writer.
+struct GudmcResults {
+    double *d_mean, *d_sd, *f_mean, *f_sd, *w_mean, *w_sd, *r_d, *r_width, *r_wdev, *r_wp, *r_delta, *r_fp;
+    int64_t *rows, *r_win;
+    static size_t n_f64(size_t n, size_t nw) { return 2 * n + 4 * n * n + 6 * n * n * nw; }
+    static size_t n_i64(size_t n, size_t nw) { return n + n * n * nw; }
+    GudmcResults(double *f, int64_t *i, size_t n, size_t nw) : rows(i), r_win(i + n) {
+        const size_t nn = n * n, rows_all = nn * nw;
+        d_mean = f; d_sd = d_mean + n; f_mean = d_sd + n; f_sd = f_mean + nn; w_mean = f_sd + nn; w_sd = w_mean + nn; r_d = w_sd + nn;
+        r_width = r_d + rows_all; r_wdev = r_width + rows_all; r_wp = r_wdev + rows_all; r_delta = r_wp + rows_all; r_fp = r_delta + rows_all;
+    }
+};
+
+// gudmc (popgen/gudmc.rs:64-462): tajima_d and fst as below, then the fits, widths and p-values on the GPU, one row per
+// (pair, row of population b).
+static int popgen_gudmc(const Args &a, Ctx &gpu, const GenotypesAndPhenotypes &g, const std::vector<double> &pool_sizes, const PopgenPlan &pl, Lap &lap) {
+    const double *G_dev = g.intercept_and_allele_frequencies.get(), *cov_dev = g.coverages.get();
+    const int n = g.n;
+    const int64_t nw = pl.nw();
+    const std::string time = unix_time_string();
+    // The reference reads both tables back from text and takes their labels apart:
+    for (const std::string &c : pl.loc_chr)
+        if (c.find('-') != std::string::npos) // "Window-<chr>_<ini>_<fin>".split("-")[1] (:169)
+            throw std::runtime_error("gudmc: chromosome name `" + c + "` contains `-`; the reference splits its window labels at `-` and fails on it");
+    for (int i = 0; i < n; ++i) {
+        if (g.pool_names[i].find("_vs_") != std::string::npos) // "<a>_vs_<b>".split("_vs_") (:231)
+            throw std::runtime_error("gudmc: pool name `" + g.pool_names[i] + "` contains `_vs_`; the reference splits its pair labels there");
+        for (int j = 0; j < i; ++j)
+            if (g.pool_names[i] == g.pool_names[j]) // position() finds the first of them (:298)
+                throw std::runtime_error("gudmc: pool name `" + g.pool_names[i] + "` occurs twice; the reference matches populations by name");
+    }
+    if (nw <= 0) throw std::runtime_error(NO_WINDOWS);
+    if (!a.popgen_as_documented)
+        std::cerr << "note: gudmc reproduces the reference: the pool sizes are fractions of their sum, so every Tajima's D is NaN, no population has a row "
+                 "and the file is the header alone; --popgen-as-documented uses the pool sizes as written and counts every locus\n";
+    const size_t nn = (size_t)n * n, wn = (size_t)nw * n;
+    // The tajima_d and fst entry points refuse a window whose tail lies before its head, so they see the others (pl.keep) and its
+    // rows stay NaN: mean_axis of the empty slice gives None there and both tables hold NaN (pi.rs:87-90, fst.rs:194-197).
+    const int64_t nk = (int64_t)pl.keep.size();
+    const bool ref = pl.reference_count;
+    const int64_t *c = ref ? pl.kc.data() : nullptr, *sd = ref ? pl.kseed.data() : nullptr, *sl = ref ? pl.kslot.data() : nullptr;
+    std::vector<double> dw(wn, std::nan("")), fw((size_t)nw * nn, std::nan(""));
+    if (nk > 0) {
+        std::vector<double> dk((size_t)nk * n), dm(n), fm(nn), fk((size_t)nk * nn);
+        gpu.ok(pg_tajima_d_dev(gpu.c, G_dev, cov_dev, g.p, n, g.ld, pl.locus_col.data(), pl.L(), pl.kh.data(), pl.kt.data(), c, sd, sl, nk, pool_sizes.data(),
+                               dk.data(), dm.data(), nullptr, nullptr), "gudmc (tajima_d)");
+        gpu.ok(pg_fst_dev(gpu.c, G_dev, cov_dev, g.p, n, g.ld, pl.locus_col.data(), pl.L(), pl.kh.data(), pl.kt.data(), nk, fm.data(), fk.data()), "gudmc (fst)");
+        for (int64_t q = 0; q < nk; ++q) {
+            std::copy(dk.begin() + (size_t)q * n, dk.begin() + (size_t)(q + 1) * n, dw.begin() + (size_t)pl.keep[q] * n);
+            std::copy(fk.begin() + (size_t)q * nn, fk.begin() + (size_t)(q + 1) * nn, fw.begin() + (size_t)pl.keep[q] * nn);
+        }
+    }
+    std::vector<int32_t> wchr(nw);
+    std::vector<uint64_t> wini(nw), wfin(nw);
+    for (int64_t w = 0; w < nw; ++w) { wchr[w] = pl.chr_id[pl.wh[w]]; wini[w] = pl.loc_pos[pl.wh[w]]; wfin[w] = pl.loc_pos[pl.wt[w]]; }
+    // device: [D | Fst] in, GudmcResults out
+    const size_t n_f64 = GudmcResults::n_f64(n, nw), n_i64 = GudmcResults::n_i64(n, nw);
+    DeviceBuf<double> tabs(sizeof(double) * (wn + (size_t)nw * nn), "gudmc: tables"), of(sizeof(double) * n_f64, "gudmc: the rows' values");
+    DeviceBuf<int64_t> oi(sizeof(int64_t) * n_i64, "gudmc: the rows' windows");
+    hip_ok(hipMemcpy(tabs.get(), dw.data(), sizeof(double) * wn, hipMemcpyHostToDevice), "gudmc: H2D");
+    hip_ok(hipMemcpy(tabs.get() + wn, fw.data(), sizeof(double) * (size_t)nw * nn, hipMemcpyHostToDevice), "gudmc: H2D");
+    const GudmcResults o(of.get(), oi.get(), n, nw);
+    gpu.ok(pg_gudmc_dev(gpu.c, tabs.get(), tabs.get() + wn, nw, n, wchr.data(), wini.data(), wfin.data(), a.sigma_threshold,
+                        a.recombination_rate_cm_per_mb, o.rows, o.d_mean, o.d_sd, o.f_mean, o.f_sd, o.w_mean, o.w_sd, o.r_win, o.r_d, o.r_width,
+                        o.r_wdev, o.r_wp, o.r_delta, o.r_fp), "gudmc");
+    std::vector<double> hf(n_f64);
+    std::vector<int64_t> hi(n_i64);
+    hip_ok(hipMemcpy(hf.data(), of.get(), sizeof(double) * n_f64, hipMemcpyDeviceToHost), "gudmc: D2H");
+    hip_ok(hipMemcpy(hi.data(), oi.get(), sizeof(int64_t) * n_i64, hipMemcpyDeviceToHost), "gudmc: D2H");
+    lap("gudmc on the GPU");
+    const GudmcResults h(hf.data(), hi.data(), n, nw);
+    std::vector<int64_t> first(nn + 1, 0); // the first line of every pair (:433-434)
+    for (size_t i = 0; i < nn; ++i) first[i + 1] = first[i] + h.rows[i % n];
+    std::string out = a.output;
+    if (out.empty()) out = basename_no_ext(a.fname) + "-gudmc-" + time + ".csv"; // :383-401
+    FILE *fo = create_new(out);
+    fputs("pop_a,pop_b,chr,pos_ini,pos_fin,mean_tajima_d_pop_b,mean_fst,sd_tajima_d_pop_b,sd_fst,tajima_d_pop_b,tajima_width_pop_b,"
+          "tajima_width_deviation_from_r_pop_b,tajima_width_one_tail_pval_pop_b,fst_delta,fst_delta_one_tail_pval\n", fo);
+    write_rows_parallel(fo, first[nn], a.n_threads, [&](int64_t r, std::string &text) { // :435-455
+        const size_t i = (size_t)(std::upper_bound(first.begin(), first.end(), r) - first.begin()) - 1;
+        const size_t e = i * (size_t)nw + (size_t)(r - first[i]);
+        const int pa = (int)(i / n), pb = (int)(i % n);
+        const int64_t w = h.r_win[e];
+        text += g.pool_names[pa] + "," + g.pool_names[pb] + "," + pl.loc_chr[pl.wh[w]] + "," + std::to_string(pl.loc_pos[pl.wh[w]]) + "," +
+                std::to_string(pl.loc_pos[pl.wt[w]]) + ",";
+        append_roundup_own(text, h.d_mean[pb], 7); text.push_back(',');
+        append_roundup_own(text, h.f_mean[i], 7); text.push_back(',');
+        append_roundup_own(text, h.d_sd[pb], 7); text.push_back(',');
+        append_roundup_own(text, h.f_sd[i], 7); text.push_back(',');
+        append_rust_display(text, h.r_d[e]); text.push_back(',');
+        append_rust_display(text, h.r_width[e]); text.push_back(',');
+        append_rust_display(text, h.r_wdev[e]); text.push_back(',');
+        append_roundup_own(text, h.r_wp[e], 7); text.push_back(',');
+        append_roundup_own(text, h.r_delta[e], 7); text.push_back(',');
+        append_roundup_own(text, h.r_fp[e], 7); text.push_back('\n');
+    });
+    fclose(fo);
+    lap("write CSV");
+    return done_ok(out);
+}
+
+// one row per pool: name, mean across windows, the windows (pi.rs:160-188, watterson_theta.rs:244-287, tajima_d.rs:127-169)
+static int popgen_diversity(const Args &a, Ctx &gpu, const GenotypesAndPhenotypes &g, const std::vector<double> &pool_sizes, const PopgenPlan &pl, Lap &lap, Analysis analysis) {
+    const double *G_dev = g.intercept_and_allele_frequencies.get(), *cov_dev = g.coverages.get();
+    const int n = g.n;
+    const int64_t nw = pl.nw();
+    const std::string win = std::to_string(a.window_size_bp), time = unix_time_string();
+    std::string out = a.output;
+    std::vector<double> pw((size_t)nw * n), pm(n);
+    const char *tag = "-pi-", *what = "heterozygosity"; // pi.rs:135-159
+    if (analysis == Analysis::heterozygosity)
+        gpu.ok(pg_pi_dev(gpu.c, G_dev, cov_dev, g.p, n, g.ld, pl.locus_col.data(), pl.L(), pl.wh.data(), pl.wt.data(), nw, pw.data(), pm.data()), what);
+    else {
+        const bool tajima = analysis == Analysis::tajima_d;
+        tag = tajima ? "-Tajimas_D-" : "-watterson-"; // tajima_d.rs:120-125, watterson_theta.rs:237-242
+        what = tajima ? "tajima_d" : "watterson_estimator";
+        if (!a.popgen_as_documented)
+            std::cerr << "note: " << what << " reproduces the reference: the pool sizes are fractions of their sum, so every value is inf or NaN, "
+                         "and the segregating sites are counted its way; --popgen-as-documented uses the pool sizes as written and counts every locus\n";
+        const bool ref = pl.reference_count;
+        const int64_t *c = ref ? pl.wc.data() : nullptr, *sd = ref ? pl.wseed.data() : nullptr, *sl = ref ? pl.wslot.data() : nullptr;
+        if (tajima)
+            gpu.ok(pg_tajima_d_dev(gpu.c, G_dev, cov_dev, g.p, n, g.ld, pl.locus_col.data(), pl.L(), pl.wh.data(), pl.wt.data(), c, sd, sl, nw, pool_sizes.data(),
+                                   pw.data(), pm.data(), nullptr, nullptr), what);
+        else
+            gpu.ok(pg_watterson_dev(gpu.c, G_dev, g.p, n, g.ld, pl.locus_col.data(), pl.L(), pl.wh.data(), pl.wt.data(), c, sd, sl, nw, pool_sizes.data(), pw.data(),
+                                    pm.data(), nullptr), what);
+    }
+    if (out.empty()) out = basename_no_ext(a.fname) + tag + win + "_bp_windows-" + time + ".csv";
+    lap("windows on the GPU");
+    FILE *fo = create_new(out);
+    std::string line = "Pool,Mean_across_windows";
+    for (int64_t w = 0; w < nw; ++w)
+        line += ",Window-" + pl.loc_chr[pl.wh[w]] + "_" + std::to_string(pl.loc_pos[pl.wh[w]]) + "_" + std::to_string(pl.loc_pos[pl.wt[w]]);
+    fputs((line + "\n").c_str(), fo);
+    for (int i = 0; i < n; ++i) {
+        line = g.pool_names[i] + "," + rust_display(pm[i]);
+        for (int64_t w = 0; w < nw; ++w) line += "," + roundup_own(pw[(size_t)w * n + i], 8);
+        fputs((line + "\n").c_str(), fo);
+    }
+    fclose(fo);
+    lap("write CSV");
+    return done_ok(out);
+}
+
+// fst: the genome-wide means, then one row per window
+static int popgen_fst(const Args &a, Ctx &gpu, const GenotypesAndPhenotypes &g, const std::vector<double> &pool_sizes, const PopgenPlan &pl, Lap &lap) {
+    const double *G_dev = g.intercept_and_allele_frequencies.get(), *cov_dev = g.coverages.get();
+    const int n = g.n;
+    const int64_t nw = pl.nw();
+    const std::string win = std::to_string(a.window_size_bp), time = unix_time_string();
+    std::string out = a.output, out_win;
+    if (out.empty()) { // fst.rs:93-131
+        out = basename_no_ext(a.fname) + "-fst-averaged_across_genome-" + time + ".csv";
+        out_win = basename_no_ext(a.fname) + "-fst-" + win + "_bp_windows-" + time + ".csv";
+    } else
+        out_win = basename_no_ext(out) + "-fst-" + win + "_bp_windows.csv";
+    const size_t nn = (size_t)n * n;
+    std::vector<double> mean(nn), fw((size_t)nw * nn);
+    gpu.ok(pg_fst_dev(gpu.c, G_dev, cov_dev, g.p, n, g.ld, pl.locus_col.data(), pl.L(), pl.wh.data(), pl.wt.data(), nw, mean.data(), fw.data()), "fst");
+    lap("fst on the GPU");
+    FILE *fo = create_new(out);
+    std::string line;
+    for (int i = 0; i < n; ++i) line += "," + g.pool_names[i];
+    fputs((line + "\n").c_str(), fo);
+    for (int i = 0; i < n; ++i) {
+        line = g.pool_names[i];
+        for (int j = 0; j < n; ++j) line += "," + roundup_own(mean[(size_t)i * n + j], 8);
+        fputs((line + "\n").c_str(), fo);
+    }
+    fclose(fo);
+    if (nw <= 0) throw std::runtime_error(NO_WINDOWS); // fst.rs:180, after the genome-wide file has been written
+    fo = create_new(out_win);
+    line = "chr,pos_ini,pos_fin";
+    for (int j = 0; j < n; ++j)
+        for (int k2 = 0; k2 < n; ++k2) line += "," + g.pool_names[j] + "_vs_" + g.pool_names[k2];
+    fputs((line + "\n").c_str(), fo);
+    write_rows_parallel(fo, nw, a.n_threads, [&](int64_t w, std::string &text) {
+        text += pl.loc_chr[pl.wh[w]] + "," + std::to_string(pl.loc_pos[pl.wh[w]]) + "," + std::to_string(pl.loc_pos[pl.wt[w]]);
+        for (size_t q = 0; q < nn; ++q) text += "," + rust_display(fw[(size_t)w * nn + q]);
+        text += "\n";
+    });
+    fclose(fo);
+    lap("write CSV");
+    std::cout << out << " and " << out_win << "\n"; // main.rs:441
+    return done_ok();
+}
+
+int run_popgen(const Args &a, Analysis analysis, Ctx &gpu, const GenotypesAndPhenotypes &g, const std::vector<double> &pool_sizes, Lap &lap) {
+    const bool reference_count = !a.popgen_as_documented && analysis != Analysis::fst && analysis != Analysis::heterozygosity;
+    const PopgenPlan pl = plan_popgen(g.chromosome, g.position, a.window_size_bp, a.window_slide_size_bp, a.min_loci_per_window, reference_count,
+                                      pg_host_sliding_windows, pg_host_watterson_windows);
+    if (analysis == Analysis::gudmc) return popgen_gudmc(a, gpu, g, pool_sizes, pl, lap);
+    if (analysis == Analysis::fst) return popgen_fst(a, gpu, g, pool_sizes, pl, lap);
+    return popgen_diversity(a, gpu, g, pool_sizes, pl, lap, analysis);
+}

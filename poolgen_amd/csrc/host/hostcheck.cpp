@@ -3,8 +3,11 @@
 //   hostcheck phen <file> <delim> <name_col> <size_col> <c1,c2,..>
 //   hostcheck parse <sync> <threads>   : "L n" then one line per locus: chrom pos counts[n*6]
 //   hostcheck gwalpha_phen <file>      : "n sig MIN MAX", the pool names, then "bin q'" per pool (the gwalpha_fmt parser)
+//   hostcheck popgen_plan <window> <slide> <min_loci> <reference_count 0|1> : stdin "chrom pos" per matrix column -> the
+//                                        popgen tools' plan, one array per line
 #include "host_util.h"
 #include "pileup.h"
+#include "popgen_plan.h"
 #include "rank_gate.h"
 #include <atomic>
 #include <thread>
@@ -124,6 +127,19 @@ int main(int argc, char **argv) {
             const auto t0 = std::chrono::steady_clock::now();
             const int64_t kept = pileup_to_sync_file(argv[2], splitc(argv[5]), f, argv[3], std::atoi(argv[4]));
             std::cout << kept << " loci in " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s\n";
+        } else if (mode == "popgen_plan") {
+            // the lines: locus_col, chr_id, wh, wt, the kept windows and, when the reference count is asked for, wc, wseed, wslot
+            if (argc < 6) return 2;
+            std::vector<std::string> lab_chr{"intercept"}; // the labels carry the intercept at [0]
+            std::vector<uint64_t> lab_pos{0};
+            std::string c; uint64_t p;
+            while (std::cin >> c >> p) { lab_chr.push_back(c); lab_pos.push_back(p); }
+            const bool ref = std::atoi(argv[5]) != 0;
+            const PopgenPlan pl = plan_popgen(lab_chr, lab_pos, std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10),
+                                              std::strtoull(argv[4], nullptr, 10), ref, pg_host_sliding_windows, pg_host_watterson_windows);
+            auto row = [](const auto &v) { for (size_t i = 0; i < v.size(); ++i) std::cout << (i ? " " : "") << v[i]; std::cout << "\n"; };
+            row(pl.locus_col); row(pl.chr_id); row(pl.wh); row(pl.wt); row(pl.keep);
+            if (ref) { row(pl.wc); row(pl.wseed); row(pl.wslot); }
         } else if (mode == "ksplit") { // hostcheck ksplit <n> <k> <seed>: the seeded outer folds of the CV harness
             const int64_t n = std::atoll(argv[2]);
             SplitMix64 rng(std::strtoull(argv[4], nullptr, 10));

@@ -1,4 +1,4 @@
-// rank_gate.h -- the go / abort agreement of the CLI's rank threads (`poolgen ... --n-gpus N`, host/main.cpp).
+// rank_gate.h -- the go / abort agreement of the CLI's rank threads (`poolgen ... --n-gpus N`, host/cli_streamed.cpp).
 #pragma once
 #include <condition_variable>
 #include <exception>

@@ -135,3 +135,64 @@ def test_numbers_are_read_like_rust_parse():
            ("u64", "18446744073709551616"), ("i64", "9223372036854775808"), ("i64", "-+1"), ("i64", "3 ")]
     for kind, text in bad:
         assert run("num", kind, text).strip() == "reject", (kind, text)
+
+
+def _fixture_labels(oracle):
+    """the matrix' column labels of tests/golden/test.sync as the reference loader makes them (sync.rs:972-1180, through the
+    oracle): sorted by (chromosome, position), one column per allele that survives the default filter"""
+    rows = []
+    for line in (GOLD / "test.sync").read_text().splitlines():
+        n, chrom, pos, counts = oracle.parse_sync_line(line)
+        if n > 0:
+            rows.append((chrom, pos, counts))
+    labels, f = [], oracle.filt()
+    for c, p, cnt in sorted(rows, key=lambda r: (r[0], r[1])):
+        res = oracle.filter_locus(cnt, [20.0] * 5, f)
+        if res is not None:
+            labels += [(c, p)] * len(res[0])
+    return labels
+
+
+def test_popgen_plan_matches_oracle_and_restatement(oracle):
+    """PopgenPlan (host/popgen_plan.h: what the popgen tools of the CLI settle before the GPU is asked) against count_loci and
+    define_sliding_windows of the oracle, theta_watterson's own loop as restated, and the windows with tail >= head.  Integers
+    only: every comparison is exact.
+
+    define_sliding_windows (helpers.rs:304-391) starts with one slot and always emits it, so with at least one locus it never
+    returns zero windows, whatever min_loci_per_window is: with more loci asked for than there are, the one window is either
+    the whole input or, where the loci lie further apart than the window size, the stale tail of the ditched slot -- no
+    window is then left to compute on, which is what the case `too few, apart` asserts."""
+    import popgen_diversity_restated as D
+    cases = {
+        "one column": ([("c1", 10)], 100, 50, 10),
+        "two columns of one locus": ([("c1", 10), ("c1", 10)], 100, 50, 10),
+        "two loci on two chromosomes": ([("c1", 10), ("c1", 10), ("c2", 5)], 100, 50, 1),
+        "too few, together": ([("c1", 10), ("c1", 40), ("c1", 40), ("c1", 90)], 100, 50, 4),
+        "too few, apart": ([("c1", 10), ("c1", 210), ("c1", 210), ("c1", 410)], 100, 50, 4),
+        "fixture": (_fixture_labels(oracle), 100, 50, 20),                                   # tests/test_gpu_gudmc_cli.py
+    }
+    for name, (labels, win, slide, minl) in cases.items():
+        chrom, pos = ["intercept"] + [c for c, _ in labels], [0] + [p for _, p in labels]
+        idx, lc, lp = oracle.count_loci(chrom, pos)
+        lc, lp = lc[:-1], lp[:-1]
+        head, tail = (a.tolist() for a in oracle.sliding_windows(lc, lp, win, slide, minl))
+        kept = [w for w in range(len(head)) if tail[w] >= head[w]]
+        if name == "too few, together":
+            assert len(lc) < minl and (head, tail) == ([0], [len(lc) - 1])
+        if name == "too few, apart":
+            assert len(lc) < minl and (head, tail) == ([len(lc) - 1], [0]) and kept == []
+        if name == "fixture":                                      # exactly one stale tail, the last window
+            assert len(head) >= 5 and [w for w in range(len(head)) if tail[w] < head[w]] == [len(head) - 1]
+        chr_id = [0]
+        for i in range(1, len(lc)):
+            chr_id.append(chr_id[-1] + (lc[i] != lc[i - 1]))
+        rh, rt, rcov, rseed, rslot, _ = D.watterson_windows(lc, lp, win, slide, minl)
+        assert (rh.tolist(), rt.tolist()) == (head, tail), name
+        stdin = "".join(f"{c} {p}\n" for c, p in labels)
+        for ref in (0, 1):
+            out = run("popgen_plan", win, slide, minl, ref, stdin=stdin).split("\n")[:-1]
+            got = [[int(x) for x in l.split()] for l in out]
+            want = [[i - 1 for i in idx], chr_id, head, tail, kept]
+            if ref:
+                want += [rcov.tolist(), rseed.tolist(), rslot.tolist()]
+            assert got == want, (name, ref)
