@@ -66,7 +66,8 @@ int pg_synchronize(pg_ctx *ctx);
 /* Per-kernel HIP-event timing (used by bench.py for the roofline record). */
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
-                    PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_COUNT = 13 };
+                    PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_CSV = 13,
+                    PG_K_COUNT = 14 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
@@ -442,6 +443,30 @@ int pg_gudmc_dev(pg_ctx *ctx, const double *d_win_dev, const double *fst_win_dev
                  double *width_mean_dev, double *width_sd_dev, int64_t *row_window_dev, double *row_d_dev,
                  double *row_width_dev, double *row_width_from_r_dev, double *row_width_p_dev, double *row_fst_delta_dev,
                  double *row_fst_p_dev);
+
+/* ---------------------------------------------------------------------------------------
+ * sync2csv's writer (FileSyncPhen::write_csv, base/sync.rs:1182-1262): rows [row0, row0 + rows) of the loader's matrix as
+ * the bytes of the allele-frequency CSV, one line per row: "chromosome,position,allele," + the n cells joined by ',' + '\n'
+ * (no header line).  G, col_locus (int64) and col_allele (int32, index into "ATCGND") as pg_load_emit_dev writes them;
+ * per locus its chromosome id (locus_chrom, int32) and position (locus_pos, uint64); the distinct chromosome names as one
+ * byte string (chrom_text) with n_chrom + 1 int32 offsets (chrom_off).  A cell prints as parse_f64_roundup_and_own(x, 6)
+ * (base/helpers.rs:103-117) does for a frequency: NaN -> "NaN"; else k = x * 1e6 rounded half away from zero, "0" for
+ * k = 0, else the decimal of k / 10^6 and, when k % 10^6 != 0, "." and its six digits without trailing zeros.
+ * *bytes is always set to the size the text needs; bytes > cap fails with PG_ERR_INVALID and writes nothing (cap = 0 is a
+ * size query, text may then be NULL).  A cell outside [0, 1] that is not NaN fails the call with PG_ERR_INVALID (*bytes is
+ * set as usual, the text is unspecified); so does a label out of range (the one case without a size: *bytes = 0).  Both
+ * forms behave alike in all of this.  Nothing at or behind text[bytes] is written.
+ * The device form formats on the GPU (three kernels on the context's stream; it synchronises once to read the size, and
+ * the text is complete once the stream has passed the call); the host form is plain C++ on n_threads threads, no context.
+ * ------------------------------------------------------------------------------------- */
+int pg_csv_freq_rows_dev(pg_ctx *ctx, const double *G_dev, int64_t ld, int n, int64_t row0, int64_t rows,
+                         const int64_t *col_locus_dev, const int32_t *col_allele_dev, const int32_t *locus_chrom_dev,
+                         const uint64_t *locus_pos_dev, const char *chrom_text_dev, const int32_t *chrom_off_dev, int n_chrom,
+                         char *text_dev, int64_t cap, int64_t *bytes);
+int pg_host_csv_freq_rows(const double *G, int64_t ld, int n, int64_t row0, int64_t rows, const int64_t *col_locus,
+                          const int32_t *col_allele, const int32_t *locus_chrom, const uint64_t *locus_pos,
+                          const char *chrom_text, const int32_t *chrom_off, int n_chrom, char *text, int64_t cap,
+                          int64_t *bytes, int n_threads);
 
 /* ---------------------------------------------------------------------------------------
  * Host-side pieces of the path (O(n^3), n = pools): exported so that they can be validated

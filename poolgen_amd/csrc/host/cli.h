@@ -253,11 +253,13 @@ struct LoadedMatrix {
     DeviceBuf<double> G, coverages;  // coverages: laid out like the matrix (pg_load_emit_cov_dev); only when asked for
     std::vector<int64_t> col_locus;  // per column: its locus (a row of the counts) ...
     std::vector<int32_t> col_allele; // ... and its allele (an index into ALLELES)
+    DeviceBuf<int64_t> col_locus_dev; // the same two on the device, instead of the host's copies, when asked for (sync2csv formats there)
+    DeviceBuf<int32_t> col_allele_dev;
 };
 
 inline LoadedMatrix load_matrix(Ctx &gpu, const uint32_t *counts_dev, int64_t L, int n, const std::vector<double> &pool_sizes,
                                 const pg_filter &flt, bool keep_p_minus_1, const int64_t *order_dev, const std::vector<int32_t> &pool_map,
-                                int n2, int64_t ld, bool with_coverages) {
+                                int n2, int64_t ld, bool with_coverages, bool labels_on_device = false) {
     LoadedMatrix m;
     gpu.ok(pg_load_plan_dev(gpu.c, counts_dev, L, n, pool_sizes.data(), &flt, keep_p_minus_1 ? 1 : 0, order_dev, &m.p), "load");
     if (m.p <= 0) return m;
@@ -270,6 +272,10 @@ inline LoadedMatrix load_matrix(Ctx &gpu, const uint32_t *counts_dev, int64_t L,
         gpu.ok(pg_load_emit_cov_dev(gpu.c, pool_map.data(), n2, m.G.get(), ld, col_locus_dev.get(), col_allele_dev.get(), m.coverages.get()), "load");
     } else
         gpu.ok(pg_load_emit_dev(gpu.c, pool_map.data(), n2, m.G.get(), ld, col_locus_dev.get(), col_allele_dev.get()), "load");
+    if (labels_on_device) {
+        m.col_locus_dev = std::move(col_locus_dev); m.col_allele_dev = std::move(col_allele_dev);
+        return m;
+    }
     m.col_locus.resize(p); m.col_allele.resize(p);
     hip_ok(hipMemcpy(m.col_locus.data(), col_locus_dev.get(), sizeof(int64_t) * p, hipMemcpyDeviceToHost), "D2H labels");
     hip_ok(hipMemcpy(m.col_allele.data(), col_allele_dev.get(), sizeof(int32_t) * p, hipMemcpyDeviceToHost), "D2H labels");
@@ -317,4 +323,6 @@ GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const SyncBatch &
                                                      bool keep_p_minus_1, bool remove_missing, bool with_coverages, Lap &lap);
 std::string ols_with_covariate(Ctx &gpu, GenotypesAndPhenotypes &g, double xxt_eigen_variance_explained,
                                const std::string &fname_input, const std::string &fname_output, int n_threads, Lap &lap, bool mle);
+std::string sync2csv(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt, bool keep_p_minus_1, const std::string &out,
+                     int64_t slab_rows, Lap &lap);
 int run_popgen(const Args &a, Analysis analysis, Ctx &gpu, const GenotypesAndPhenotypes &g, const std::vector<double> &pool_sizes, Lap &lap);

@@ -44,7 +44,7 @@ static const char *USAGE =
     "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
     "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
     "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d,\n"
-    "          gudmc\n"
+    "          gudmc, sync2csv\n"
     "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
     "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
     "                                     writes A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on pileup-derived\n"
@@ -66,6 +66,8 @@ static const char *USAGE =
     "                                      the polymorphic loci of every window.  Default: the reference's behaviour -- pool sizes as\n"
     "                                      fractions of their sum (its harmonic sums are then empty: every value is inf or NaN) and\n"
     "                                      its count, which looks the flag up at the window's index instead of the locus\n"
+    "      --csv-slab-rows <N>             sync2csv: rows of the table formatted on the GPU, copied and written per turn; default: as\n"
+    "                                      many as hold 256 MB of text at their longest.  The file does not depend on it\n"
     "      --n-threads <1>                 parser / writer threads\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
     "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
@@ -121,6 +123,7 @@ Args parse_args(int argc, char **argv) {
             std::string t;
             while (std::getline(ss, t, ',')) a.gpu_ids.push_back(flag_int(t, k));
         }
+        else if (k == "--csv-slab-rows") a.csv_slab_rows = flag_int(val(), k, 1);
         else if (k == "--k-folds") a.k_folds = flag_int(val(), k, 1);
         else if (k == "--n-reps") a.n_reps = flag_int(val(), k, 1);
         else if (k == "--seed") a.seed = flag_u64(val(), k);
@@ -178,6 +181,10 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
 }
 
 void check_n_gpus(const Args &a, Analysis analysis) {
+    if (analysis == Analysis::sync2csv) { // one table in (chromosome, position) order: the sort is global
+        if (a.n_gpus > 1) throw std::runtime_error("--n-gpus " + std::to_string(a.n_gpus) + ": `sync2csv` sorts the whole table and runs on one GPU");
+        return;
+    }
     if (a.n_gpus > 0 && !takes_n_gpus(analysis))
         throw std::runtime_error("--n-gpus applies to " + analysis_names(takes_n_gpus, " and ") + "; `" + a.analysis + "` runs on one GPU");
 }

@@ -26,7 +26,10 @@ struct Args {
     // the input is cut into one contiguous byte range per GPU, each with its own parser threads.  0 = flag absent.
     int n_gpus = 0;
     std::vector<int> gpu_ids; // device ordinals of the ranks (default 0, 1, .., n_gpus - 1)
+    int64_t csv_slab_rows = 0; // sync2csv: rows formatted per call (0 = as many as CSV_SLAB_BYTES of text hold)
 };
+
+constexpr int64_t CSV_SLAB_BYTES = 256ll << 20; // sync2csv: the text budget of one slab of rows (device buffer + pinned copy)
 
 Args parse_args(int argc, char **argv); // --help prints the usage and ends the process
 pgh::Analysis checked_analysis(const Args &a, bool &gwalpha_fmt); // the analysis `a` names, once its flags agree with one another

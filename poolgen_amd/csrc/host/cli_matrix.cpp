@@ -7,16 +7,21 @@
 // column layout run on the GPU from the parsed counts (pg_load_plan_dev / pg_load_emit[_cov]_dev), and the matrix never
 // exists in host memory.  `remove_missing`: drop the pools without phenotype (what ols_with_covariate does first,
 // gwas/ols.rs:287); the popgen tools keep every pool.
-GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt,
-                                                     bool keep_p_minus_1, bool remove_missing, bool with_coverages, Lap &lap) {
-    const int n = sb.n, k = ph.k;
-    const int64_t L = sb.size();
-    std::vector<int64_t> order(L);
+static std::vector<int64_t> sorted_locus_order(const SyncBatch &sb) { // the (chromosome, position) sort of sync.rs:1092-1101
+    std::vector<int64_t> order(sb.size());
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
         const int c = sb.chrom(x).compare(sb.chrom(y));
         return c != 0 ? c < 0 : sb.pos[x] < sb.pos[y];
     });
+    return order;
+}
+
+GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt,
+                                                     bool keep_p_minus_1, bool remove_missing, bool with_coverages, Lap &lap) {
+    const int n = sb.n, k = ph.k;
+    const int64_t L = sb.size();
+    const std::vector<int64_t> order = sorted_locus_order(sb);
     std::vector<int> keep(n);
     std::iota(keep.begin(), keep.end(), 0);
     if (remove_missing) keep = complete_pools(ph);
@@ -95,3 +100,95 @@ std::string ols_with_covariate(Ctx &gpu, GenotypesAndPhenotypes &g, double xxt_e
     return out;
 }
 
+
+// FileSyncPhen::write_csv (base/sync.rs:1182-1262): the loaded table -- every pool of the phenotype file (:1222, :1236), a row per
+// surviving allele in (chromosome, position) order -- as "#chr,pos,allele,<pools>" and one line of frequencies per row.  The
+// matrix is loaded as for the other analyses and stays in HBM; its text is formatted there too (pg_csv_freq_rows_dev), a slab of
+// rows at a time: format into a device buffer, copy to pinned memory, write.  `out` has been probed by the caller; the file does
+// not depend on slab_rows (0 = what CSV_SLAB_BYTES of text hold).  PGH_TIMING=1 splits the last lap into its three parts.
+std::string sync2csv(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt, bool keep_p_minus_1, const std::string &out,
+                     int64_t slab_rows, Lap &lap) {
+    const int n = sb.n;
+    const int64_t L = sb.size(), ld = n + (n & 1);
+    std::vector<int32_t> pool_map(n);
+    std::iota(pool_map.begin(), pool_map.end(), 0);
+    LoadedMatrix m;
+    {
+        const std::vector<int64_t> order = sorted_locus_order(sb);
+        DeviceBuf<uint32_t> counts_dev(sizeof(uint32_t) * (size_t)L * n * 6, "device memory for the counts");
+        DeviceBuf<int64_t> order_dev(sizeof(int64_t) * L, "device memory");
+        CountsUpload upload;
+        upload(gpu, sb, counts_dev.get());
+        hip_ok(hipMemcpy(order_dev.get(), order.data(), sizeof(int64_t) * L, hipMemcpyHostToDevice), "H2D order");
+        m = load_matrix(gpu, counts_dev.get(), L, n, ph.pool_sizes, flt, keep_p_minus_1, order_dev.get(), pool_map, n, ld, false,
+                        /*labels_on_device=*/true);
+    }
+    if (m.p <= 0) // sync.rs:1220
+        throw std::runtime_error("No data passed the filtering variables. Please decrease minimum depth, and/or minimum allele frequency.");
+    lap("sort + H2D + GPU loader");
+    // the loci's labels and the name table, once
+    std::string names;
+    std::vector<int32_t> name_off(1, 0);
+    size_t longest = 0;
+    for (const std::string &c : sb.chrom_names) {
+        names += c;
+        name_off.push_back((int32_t)names.size());
+        longest = std::max(longest, c.size());
+    }
+    DeviceBuf<int32_t> chrom_dev(sizeof(int32_t) * L, "device memory"), off_dev(sizeof(int32_t) * name_off.size(), "device memory");
+    DeviceBuf<uint64_t> pos_dev(sizeof(uint64_t) * L, "device memory");
+    DeviceBuf<char> names_dev(std::max<size_t>(1, names.size()), "device memory");
+    hip_ok(hipMemcpy(chrom_dev.get(), sb.chrom_id.data(), sizeof(int32_t) * L, hipMemcpyHostToDevice), "H2D labels");
+    hip_ok(hipMemcpy(pos_dev.get(), sb.pos.data(), sizeof(uint64_t) * L, hipMemcpyHostToDevice), "H2D labels");
+    hip_ok(hipMemcpy(off_dev.get(), name_off.data(), sizeof(int32_t) * name_off.size(), hipMemcpyHostToDevice), "H2D labels");
+    if (!names.empty()) hip_ok(hipMemcpy(names_dev.get(), names.data(), names.size(), hipMemcpyHostToDevice), "H2D labels");
+    // a slab's text is at most rows x (longest name + 24 + 9 n) bytes
+    const int64_t row_max = (int64_t)longest + 24 + 9 * (int64_t)n;
+    if (slab_rows <= 0) slab_rows = std::max<int64_t>(1, CSV_SLAB_BYTES / row_max);
+    slab_rows = std::min(slab_rows, m.p);
+    const int64_t cap = slab_rows * row_max;
+    DeviceBuf<char> text_dev((size_t)cap, "device memory for the text");
+    PinnedBuf text_host;
+    if (!text_host.reset((size_t)cap)) throw std::runtime_error("out of pinned host memory for the text");
+    FILE *fo = create_new(out);
+    std::string header = "#chr,pos,allele,";
+    for (int i = 0; i < n; ++i) { header += ph.pool_names[i]; header.push_back(i + 1 < n ? ',' : '\n'); }
+    fputs(header.c_str(), fo);
+    std::fflush(fo);
+    const int fd = fileno(fo);
+    off_t at = (off_t)header.size();
+    double t_format = 0, t_copy = 0, t_write = 0;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); };
+    try {
+        for (int64_t row0 = 0; row0 < m.p; row0 += slab_rows) {
+            const int64_t rows = std::min(slab_rows, m.p - row0);
+            int64_t bytes = 0;
+            auto t0 = now();
+            gpu.ok(pg_csv_freq_rows_dev(gpu.c, m.G.get(), ld, n, row0, rows, m.col_locus_dev.get(), m.col_allele_dev.get(), chrom_dev.get(),
+                                        pos_dev.get(), names_dev.get(), off_dev.get(), (int)sb.chrom_names.size(), text_dev.get(), cap, &bytes),
+                   "sync2csv");
+            gpu.ok(pg_synchronize(gpu.c), "sync2csv");
+            t_format += since(t0); t0 = now();
+            hip_ok(hipMemcpy(text_host.get(), text_dev.get(), (size_t)bytes, hipMemcpyDeviceToHost), "D2H text");
+            t_copy += since(t0); t0 = now();
+            const char *q = static_cast<const char *>(text_host.get());
+            for (size_t left = (size_t)bytes; left > 0;) { // one writer
+                const ssize_t w = ::pwrite(fd, q, left, at);
+                if (w <= 0) throw std::runtime_error("write failed (disk full?)");
+                q += w; at += w; left -= (size_t)w;
+            }
+            t_write += since(t0);
+        }
+    } catch (...) { // no partly written file stays behind: a later run with the same name would be refused
+        fclose(fo);
+        ::unlink(out.c_str());
+        throw;
+    }
+    fclose(fo);
+    if (lap.on)
+        std::fprintf(stderr, "poolgen: %-24s %.3f s  D2H %.3f s  write %.3f s  (%lld rows, %lld bytes)\n", "GPU format", t_format, t_copy, t_write,
+                     (long long)m.p, (long long)at);
+    lap("format + write CSV");
+    return out;
+}

@@ -52,6 +52,11 @@ static int run(int argc, char **argv) {
         if (rc >= 0) return rc;
     }
     if (per_locus(analysis)) return run_batch_streamed(a, ph, gpu, lap, analysis, is_pileup, pf, flt, ranks);
+    std::string csv_out; // sync2csv: the file is refused before any work is done (sync.rs:1191-1216)
+    if (analysis == Analysis::sync2csv) {
+        csv_out = a.output.empty() ? basename_no_ext(a.fname) + "-" + unix_time_string() + "-allele_frequencies.csv" : a.output;
+        probe_output(csv_out);
+    }
     SyncBatch sb;
     if (is_pileup) {
         sb = parse_pileup_file(a.fname, a.n_threads, pf, pinned);
@@ -63,6 +68,8 @@ static int run(int argc, char **argv) {
     }
     if (sb.size() == 0) throw std::runtime_error("no loci in " + a.fname);
     if (sb.n != ph.n) throw std::runtime_error("the number of pools in the sync file and in the phenotype file differ");
+    if (analysis == Analysis::sync2csv) // sync2csv (main.rs:357-366): every pool, whatever its phenotype
+        return done_ok(sync2csv(gpu, sb, ph, flt, a.keep_p_minus_1, csv_out, a.csv_slab_rows, lap));
     const int k = ph.k;
     const bool popgen = pgh::popgen(analysis);
 

@@ -5,9 +5,11 @@
 // coefficients consumed by the device p-value code.  These are O(n^3) with n <= a few hundred;
 // the O(n^2 p) work lives in the HIP kernels.
 #include "pg_common.h"
+#include "pg_csv_cell.h"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
+#include <thread>
 
 namespace {
 
@@ -575,4 +577,90 @@ extern "C" double pg_host_t_two_sided_p(double t_abs, int df) {
     double p = 1.0 - A;
     p = p < 0.0 ? 0.0 : p;
     return p > 1.0 ? 1.0 : p;
+}
+
+// ---- sync2csv's rows on the host: the checker and the baseline of pg_csv_freq_rows_dev (pg_csv.hip), same contract ----------
+namespace {
+struct CsvHostArgs {
+    const double *G; int64_t ld; int n;
+    const int64_t *col_locus; const int32_t *col_allele; const int32_t *locus_chrom; const uint64_t *locus_pos;
+    const char *chrom_text; const int32_t *chrom_off; int n_chrom;
+};
+// the length of row r; with `dst` its text as well.  -1: a label out of range; *bad is set by a cell that is no frequency
+int64_t csv_host_row(const CsvHostArgs &a, int64_t r, char *dst, int *bad) {
+    const int64_t loc = a.col_locus[r];
+    const int al = a.col_allele[r];
+    if (loc < 0 || al < 0 || al >= 6) return -1;
+    const int cid = a.locus_chrom[loc];
+    if (cid < 0 || cid >= a.n_chrom) return -1;
+    const int name0 = a.chrom_off[cid], name_len = a.chrom_off[cid + 1] - name0;
+    if (name_len < 0) return -1;
+    uint64_t pos = a.locus_pos[loc];
+    const int nd = pg_csv_pos_digits(pos);
+    int64_t o = (int64_t)name_len + nd + 4;
+    if (dst) {
+        std::memcpy(dst, a.chrom_text + name0, (size_t)name_len);
+        char *q = dst + name_len;
+        q[0] = ',';
+        for (int i = nd; i >= 1; --i) { q[i] = (char)('0' + (int)(pos % 10)); pos /= 10; }
+        q[nd + 1] = ','; q[nd + 2] = (char)pg_csv_allele(al); q[nd + 3] = ',';
+    }
+    const double *row = a.G + r * a.ld;
+    for (int j = 0; j < a.n; ++j) {
+        uint64_t text;
+        const int len = pg_csv_cell(row[j], &text, bad);
+        if (dst) {
+            for (int i = 0; i < len; ++i) dst[o + i] = (char)(text >> (8 * i));
+            dst[o + len] = j == a.n - 1 ? '\n' : ',';
+        }
+        o += len + 1;
+    }
+    return o;
+}
+} // namespace
+
+extern "C" int pg_host_csv_freq_rows(const double *G, int64_t ld, int n, int64_t row0, int64_t rows, const int64_t *col_locus,
+                                     const int32_t *col_allele, const int32_t *locus_chrom, const uint64_t *locus_pos,
+                                     const char *chrom_text, const int32_t *chrom_off, int n_chrom, char *text, int64_t cap,
+                                     int64_t *bytes, int n_threads) {
+    if (!bytes) return PG_ERR_INVALID;
+    *bytes = 0;
+    if (n < 1 || ld < n || row0 < 0 || rows < 0 || cap < 0 || n_chrom < 1 || (cap > 0 && !text)) return PG_ERR_INVALID;
+    if (rows == 0) return PG_OK;
+    if (!G || !col_locus || !col_allele || !locus_chrom || !locus_pos || !chrom_text || !chrom_off) return PG_ERR_INVALID;
+    const CsvHostArgs a{G + row0 * ld, ld, n, col_locus + row0, col_allele + row0, locus_chrom, locus_pos, chrom_text, chrom_off, n_chrom};
+    const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, rows));
+    const int64_t each = (rows + parts - 1) / parts;
+    std::vector<int64_t> size(parts, 0);
+    std::vector<int> bad(parts, 0);
+    auto on_parts = [&](auto fn) { // fn(part, first row, end row) on a thread per part
+        std::vector<std::thread> th;
+        for (int t = 1; t < parts; ++t) th.emplace_back([&, t] { fn(t, std::min(rows, t * each), std::min(rows, (t + 1) * each)); });
+        fn(0, (int64_t)0, std::min(rows, each));
+        for (auto &x : th) x.join();
+    };
+    on_parts([&](int t, int64_t lo, int64_t hi) { // measure
+        int64_t sum = 0;
+        for (int64_t r = lo; r < hi && sum >= 0; ++r) {
+            const int64_t len = csv_host_row(a, r, nullptr, &bad[t]);
+            sum = len < 0 ? len : sum + len;
+        }
+        size[t] = sum;
+    });
+    int64_t total = 0;
+    for (int t = 0; t < parts; ++t) {
+        if (size[t] < 0) return PG_ERR_INVALID; // (a label out of range: no size either)
+        total += size[t];
+    }
+    *bytes = total;
+    for (int t = 0; t < parts; ++t)
+        if (bad[t]) return PG_ERR_INVALID; // a cell that is no frequency: the size is known, nothing is written
+    if (total > cap) return PG_ERR_INVALID;
+    std::vector<int64_t> at(parts, 0);
+    for (int t = 1; t < parts; ++t) at[t] = at[t - 1] + size[t - 1];
+    on_parts([&](int t, int64_t lo, int64_t hi) { // emit
+        char *dst = text + at[t];
+        for (int64_t r = lo; r < hi; ++r) dst += csv_host_row(a, r, dst, &bad[t]);
+    });
+    return PG_OK;
 }

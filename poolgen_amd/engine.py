@@ -9,6 +9,7 @@ Method names follow the reference operators they stand in for:
   gwalpha              gwas::gwalpha_ls / gwalpha_ml (gwas/gwalpha.rs:281-380)
   gp_ols               gp::ols                       (gp/ols.rs:8-101)
   gudmc                popgen::gudmc                 (popgen/gudmc.rs:64-462)
+  freq_csv             FileSyncPhen::write_csv's rows (base/sync.rs:1182-1262)
 All heavy arguments are torch CUDA tensors (device memory owned by torch); results are
 torch CUDA tensors.  Everything is computed by libpoolgen_hip.so.
 """
@@ -40,6 +41,54 @@ class Filter:
 
 def _host_f64(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def _chrom_table(chrom_names):
+    """The distinct chromosome names as one byte string plus len + 1 int32 offsets."""
+    names = [c.encode() if isinstance(c, str) else bytes(c) for c in chrom_names]
+    off = np.zeros(len(names) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(c) for c in names])
+    text = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8).copy()
+    return text, off
+
+
+def freq_csv_host(G, col_locus, col_allele, chrom_ids, pos, chrom_names, n=None, row0=0, rows=None, n_threads=1, out=None):
+    """Engine.freq_csv on the host (pg_host_csv_freq_rows: plain C++, no GPU): the same arguments as numpy arrays, the text
+    as bytes.  The checker of the device form and the baseline it is measured against.  With `out` (a uint8 array that is large
+    enough) the text is formatted into it by one call, without the size query, and the filled part of `out` is returned."""
+    lib = load_library()
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 2 or not G.flags.c_contiguous:
+        raise ValueError("G must be a C-contiguous p x ld array")
+    p, ld = G.shape
+    n = ld if n is None else int(n)
+    rows = p - row0 if rows is None else int(rows)
+    if not (0 <= row0 and 0 <= rows and row0 + rows <= p):
+        raise ValueError("freq_csv_host: rows out of range")
+    cl = np.ascontiguousarray(col_locus, dtype=np.int64); ca = np.ascontiguousarray(col_allele, dtype=np.int32)
+    ch = np.ascontiguousarray(chrom_ids, dtype=np.int32); po = np.ascontiguousarray(pos, dtype=np.uint64)
+    if len(cl) != p or len(ca) != p or len(ch) != len(po):
+        raise ValueError("freq_csv_host: label arrays do not match")
+    text, off = _chrom_table(chrom_names)
+    args = [G.ctypes.data, ld, n, int(row0), rows, cl.ctypes.data, ca.ctypes.data, ch.ctypes.data, po.ctypes.data,
+            text.ctypes.data, off.ctypes.data, len(off) - 1]
+    need = C.c_int64()
+    if out is not None:
+        if out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("freq_csv_host: out must be a contiguous uint8 array")
+        rc = lib.pg_host_csv_freq_rows(*args, out.ctypes.data, out.size, C.byref(need), int(n_threads))
+        if rc != 0:
+            raise NativeError(f"pg_host_csv_freq_rows failed ({rc}): the text needs {need.value} bytes, out holds {out.size}"
+                              if need.value > out.size else f"pg_host_csv_freq_rows failed ({rc})")
+        return out[:need.value]
+    rc = lib.pg_host_csv_freq_rows(*args, None, 0, C.byref(need), int(n_threads))
+    if rc != 0 and need.value == 0:
+        raise NativeError(f"pg_host_csv_freq_rows failed ({rc}): a label is out of range")
+    out = np.empty(max(need.value, 1), dtype=np.uint8)
+    rc = lib.pg_host_csv_freq_rows(*args, out.ctypes.data, need.value, C.byref(need), int(n_threads))
+    if rc != 0:   # the buffer has the size asked for, so:
+        raise NativeError(f"pg_host_csv_freq_rows failed ({rc}): a cell is no allele frequency (outside [0, 1] and not NaN)")
+    return out[:need.value].tobytes()
 
 
 class Engine:
@@ -402,6 +451,50 @@ class Engine:
                                                G.data_ptr(), ld, col_locus.data_ptr(), col_allele.data_ptr()),
                     "pg_load_emit_dev")
         return G, col_locus, col_allele
+
+    def freq_csv(self, G, col_locus, col_allele, chrom_ids, pos, chrom_names, n: int | None = None, row0: int = 0,
+                 rows: int | None = None, out: torch.Tensor | None = None, validate: bool = True) -> torch.Tensor:
+        """The rows [row0, row0 + rows) of load_frequencies' matrix as the text of sync2csv's file (FileSyncPhen::write_csv,
+        base/sync.rs:1182-1262; no header line), formatted on the GPU: a torch.uint8 tensor on G's device.  chrom_ids / pos:
+        per locus (what col_locus indexes) the chromosome's index into chrom_names and the position.  With `out` (a uint8
+        tensor on the device that is large enough: a slab's buffer) one call formats into it, without the size query, and the
+        filled part of `out` is returned.  validate=False skips the check that col_locus stays inside chrom_ids / pos (two
+        reductions and a synchronisation per call: the library cannot know their length); a caller that formats slab after
+        slab of one table checks once.  The name table of the last call stays on the device for the next one."""
+        p, ld, n = self._g_dims(G, n)
+        rows = p - row0 if rows is None else int(rows)
+        if not (0 <= row0 and 0 <= rows and row0 + rows <= p):
+            raise ValueError("freq_csv: rows out of range")
+        dev = G.device
+        if col_locus.numel() != p or col_allele.numel() != p:
+            raise ValueError("freq_csv: col_locus / col_allele do not match G")
+        ch = torch.as_tensor(np.ascontiguousarray(chrom_ids, dtype=np.int32)).to(dev) if not isinstance(chrom_ids, torch.Tensor) else chrom_ids
+        # (torch has no uint64 arithmetic; the bits are what the kernel reads)
+        po = torch.as_tensor(np.ascontiguousarray(pos, dtype=np.uint64).view(np.int64)).to(dev) if not isinstance(pos, torch.Tensor) else pos
+        if ch.numel() != po.numel():
+            raise ValueError("freq_csv: chrom_ids / pos do not match")
+        if validate and rows and not (0 <= int(col_locus[row0:row0 + rows].min()) and int(col_locus[row0:row0 + rows].max()) < ch.numel()):
+            raise ValueError("freq_csv: col_locus points outside chrom_ids / pos")   # (the library cannot know their length)
+        key = (tuple(chrom_names), dev)
+        if getattr(self, "_csv_names", (None,))[0] != key:
+            text, off = _chrom_table(chrom_names)
+            self._csv_names = (key, torch.as_tensor(text).to(dev), torch.as_tensor(off).to(dev))
+        _, text_dev, off_dev = self._csv_names
+        args = [self._ctx, self._dev(G, torch.float64), ld, n, int(row0), rows, self._dev(col_locus, torch.int64),
+                self._dev(col_allele, torch.int32), self._dev(ch, torch.int32), self._dev(po, torch.int64), text_dev.data_ptr(),
+                off_dev.data_ptr(), off_dev.numel() - 1]
+        need = C.c_int64()
+        if out is not None:
+            self._check(self._lib.pg_csv_freq_rows_dev(*args, self._dev(out, torch.uint8), out.numel(), C.byref(need)),
+                        "pg_csv_freq_rows_dev")
+            return out[:need.value]
+        rc = self._lib.pg_csv_freq_rows_dev(*args, None, 0, C.byref(need))
+        if rc != 0 and need.value == 0:
+            self._check(rc, "pg_csv_freq_rows_dev")
+        out = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        if need.value:
+            self._check(self._lib.pg_csv_freq_rows_dev(*args, out.data_ptr(), need.value, C.byref(need)), "pg_csv_freq_rows_dev")
+        return out
 
     # ---- popgen -------------------------------------------------------------------------------
     def sliding_windows(self, chrom_ids, pos, window_size_bp: int, window_slide_size_bp: int, min_loci_per_window: int):
