@@ -67,7 +67,7 @@ int pg_synchronize(pg_ctx *ctx);
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
                     PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_CSV = 13,
-                    PG_K_COUNT = 14 };
+                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_COUNT = 17 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
@@ -467,6 +467,58 @@ int pg_host_csv_freq_rows(const double *G, int64_t ld, int n, int64_t row0, int6
                           const int32_t *col_allele, const int32_t *locus_chrom, const uint64_t *locus_pos,
                           const char *chrom_text, const int32_t *chrom_off, int n_chrom, char *text, int64_t cap,
                           int64_t *bytes, int n_threads);
+
+/* ---------------------------------------------------------------------------------------
+ * impute (src/imputation/: filtering_missing.rs, mean_imputation.rs, adaptive_ld_knn_imputation.rs; CLI main.rs:125-142,
+ * :367-396) on the loader's matrix: G and cov as pg_load_emit_cov_dev writes them (all alleles kept), locus_col (host, L + 1
+ * entries, 0 .. p) as for the popgen tools.  The steps of impute_mean / impute_aLDkNN are separate entry points; every one
+ * has returned only when its work on the device is done.  All results are bit for bit the reference's: sequential folds where
+ * it folds, ndarray's 8-lane order where it calls sum().
+ * ------------------------------------------------------------------------------------- */
+/* set_missing_by_depth (filtering_missing.rs:15-44), in place: every (pool, locus) with cov < min_depth gets cov = NaN (in every
+ * row of the locus) and NaN frequencies -- except in the LAST locus, whose frequencies stay as they are (the reference's
+ * idx_fin = loci_idx[l - 1] is an empty range; its coverage still goes). */
+int pg_set_missing_by_depth_dev(pg_ctx *ctx, double *G_dev, double *cov_dev, int64_t p, int n, int64_t ld,
+                                const int64_t *locus_col, int64_t L, double min_depth);
+/* The NaN counts the filters sort by (host outputs, either may be NULL): pool_nan[n] over the p rows of G
+ * (filter_out_top_missing_pools, :53-61), locus_nan[L] over the pools of cov (filter_out_top_missing_loci, :136-144; cov_dev
+ * may be NULL when locus_nan is).  missing_rate() (:7-13) is the sum of locus_nan over n * L. */
+int pg_missingness_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                       const int64_t *locus_col, int64_t L, int64_t *pool_nan, int64_t *locus_nan);
+/* The keep rule of both filters (:63-86, :146-170), no GPU: of `count` pools or loci, those with a NaN count > 0 number
+ * n_missing; count - ceil(n_missing * frac) stay: the first of a STABLE ascending sort by NaN count, returned in ascending
+ * index order in keep (room for count).  Returns how many stay; 0 is the reference's "No pools / loci left after filtering";
+ * negative = bad argument. */
+int64_t pg_host_top_missing_keep(const int64_t *nan_count, int64_t count, double frac, int64_t *keep);
+/* G, cov and the column labels restricted to the kept pools (keep_pools: host, n_keep ascending indices) and loci (keep_loci:
+ * host, L_keep ascending indices): G_out / cov_out are p_out x ld_out with the padding columns zeroed, p_out = the columns of
+ * the kept loci = locus_col_out[L_keep] (host, L_keep + 1 entries, written by the call; the caller sizes the outputs from
+ * locus_col).  cov_dev / cov_out_dev, col_locus_dev / col_locus_out_dev and col_allele_dev / col_allele_out_dev are optional
+ * pairs.  Outputs must not overlap inputs. */
+int pg_impute_compact_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                          const int64_t *col_locus_dev, const int32_t *col_allele_dev, const int64_t *locus_col, int64_t L,
+                          const int64_t *keep_pools, int n_keep, const int64_t *keep_loci, int64_t L_keep, double *G_out_dev,
+                          double *cov_out_dev, int64_t ld_out, int64_t *col_locus_out_dev, int32_t *col_allele_out_dev,
+                          int64_t *locus_col_out);
+/* mean_imputation (mean_imputation.rs:6-41), in place: per locus the means of its allele columns over the non-NaN pools (fold
+ * in pool order / count), divided by their sum when that is != 1.0, written into the NaN cells.  A locus missing in every
+ * pool stays NaN. */
+int pg_impute_mean_dev(pg_ctx *ctx, double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L);
+/* adaptive_ld_knn_imputation (adaptive_ld_knn_imputation.rs:174-341) into G_out_dev (p x ld, must not be G_dev: every window
+ * works on its own copy of the INPUT; the copies are written back in window order, so the last window that holds a column
+ * wins, and loci in no window are copied through).  Windows as pg_host_sliding_windows gives them (n_windows = 0: a plain
+ * copy).  Per window and column with missing data: Pearson correlations with every column of the window ("sensible_corr",
+ * correlation_test.rs:7-71), the min(p_w, n_loci_to_estimate_distance) most correlated columns (stable, NaN first), Euclidean
+ * pool distances over them on the window's current state, and per missing pool the adaptive k-nearest-neighbour weighted mean
+ * with the reference's fall-backs (the count of present values over n) and its per-locus renormalisation, quirks included.
+ * k_neighbours > n (the reference panics) fails with PG_ERR_INVALID.  scratch_bytes: device memory for the window copies,
+ * sort keys and distance columns of one batch of windows (0 = 1 GiB; a window that needs more runs alone). */
+int pg_impute_aldknn_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
+                         const int64_t *win_head, const int64_t *win_tail, int64_t n_windows, int64_t n_loci_to_estimate_distance,
+                         int64_t k_neighbours, int64_t scratch_bytes, double *G_out_dev);
+/* The mark both methods end with (mean_imputation.rs:42-59), in place: in every locus with at least one non-NaN coverage the
+ * NaN coverages become +inf. */
+int pg_impute_mark_cov_dev(pg_ctx *ctx, double *cov_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L);
 
 /* ---------------------------------------------------------------------------------------
  * Host-side pieces of the path (O(n^3), n = pools): exported so that they can be validated

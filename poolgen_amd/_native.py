@@ -89,6 +89,13 @@ SIGNATURES = {
     "pg_gudmc_dev": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _d, _d] + [_vp] * 14),
     "pg_csv_freq_rows_dev": (_i, [_vp, _vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64]),
     "pg_host_csv_freq_rows": (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64, _i]),
+    "pg_set_missing_by_depth_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _d]),
+    "pg_missingness_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp]),
+    "pg_host_top_missing_keep": (_i64, [_vp, _i64, _d, _vp]),
+    "pg_impute_compact_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "pg_impute_mean_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i64]),
+    "pg_impute_aldknn_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "pg_impute_mark_cov_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i64]),
     "pg_gp_predict_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i, _vp]),
     "pg_host_sym_eig": (_i, [_vp, _i, _vp, _vp]),
     "pg_host_sym_eig_top": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -99,7 +106,7 @@ SIGNATURES = {
 
 KERNEL_IDS = {"kinship": 0, "kinship_reduce": 1, "sweep": 2, "ols_iter": 3, "pearson": 4,
               "chisq": 5, "gp_xxt": 6, "gp_beta": 7, "sweep_finish": 8, "allreduce": 9, "gp_predict": 10, "fisher": 11,
-              "gwalpha": 12, "csv": 13}
+              "gwalpha": 12, "csv": 13, "impute": 14, "impute_links": 15, "impute_walk": 16}
 
 
 def load_library():

@@ -325,4 +325,8 @@ std::string ols_with_covariate(Ctx &gpu, GenotypesAndPhenotypes &g, double xxt_e
                                const std::string &fname_input, const std::string &fname_output, int n_threads, Lap &lap, bool mle);
 std::string sync2csv(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt, bool keep_p_minus_1, const std::string &out,
                      int64_t slab_rows, Lap &lap);
+void write_freq_csv(Ctx &gpu, const SyncBatch &sb, const std::vector<std::string> &pool_names, const double *G, int64_t ld, int n, int64_t p,
+                    const int64_t *col_locus_dev, const int32_t *col_allele_dev, const std::string &out, int64_t slab_rows, const char *what,
+                    Lap &lap);
+std::string impute(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt, const Args &a, const std::string &out, Lap &lap);
 int run_popgen(const Args &a, Analysis analysis, Ctx &gpu, const GenotypesAndPhenotypes &g, const std::vector<double> &pool_sizes, Lap &lap);

@@ -44,7 +44,7 @@ static const char *USAGE =
     "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
     "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
     "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d,\n"
-    "          gudmc, sync2csv\n"
+    "          gudmc, sync2csv, impute\n"
     "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
     "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
     "                                     writes A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on pileup-derived\n"
@@ -66,7 +66,11 @@ static const char *USAGE =
     "                                      the polymorphic loci of every window.  Default: the reference's behaviour -- pool sizes as\n"
     "                                      fractions of their sum (its harmonic sums are then empty: every value is inf or NaN) and\n"
     "                                      its count, which looks the flag up at the window's index instead of the locus\n"
-    "      --csv-slab-rows <N>             sync2csv: rows of the table formatted on the GPU, copied and written per turn; default: as\n"
+    "      --imputation-method <aLD-kNNi|mean>   impute: adaptive LD-kNN imputation over the --window-* windows, or the mean of the pools\n"
+    "      --min-depth-set-to-missing <5>  --frac-top-missing-pools <0.1>  --frac-top-missing-loci <0.1>   impute: the depth below which\n"
+    "                                      a pool is missing at a locus, and the shares of the pools / loci with missing data dropped\n"
+    "      --n-loci-to-estimate-distance <10>  --k-neighbours <5>   impute, aLD-kNNi: linked columns per column, neighbours per pool\n"
+    "      --csv-slab-rows <N>             sync2csv, impute: rows of the table formatted on the GPU, copied and written per turn; default: as\n"
     "                                      many as hold 256 MB of text at their longest.  The file does not depend on it\n"
     "      --n-threads <1>                 parser / writer threads\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
@@ -124,6 +128,14 @@ Args parse_args(int argc, char **argv) {
             while (std::getline(ss, t, ',')) a.gpu_ids.push_back(flag_int(t, k));
         }
         else if (k == "--csv-slab-rows") a.csv_slab_rows = flag_int(val(), k, 1);
+        else if (k == "--imputation-method") a.imputation_method = val();
+        else if (k == "--min-depth-set-to-missing") {
+            const std::string t = val();
+            if (!parse_f64_strict(t, a.min_depth_set_to_missing)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
+        } else if (k == "--frac-top-missing-pools") a.frac_top_missing_pools = parse_valid_freq(val(), k);
+        else if (k == "--frac-top-missing-loci") a.frac_top_missing_loci = parse_valid_freq(val(), k);
+        else if (k == "--n-loci-to-estimate-distance") a.n_loci_to_estimate_distance = flag_u64(val(), k);
+        else if (k == "--k-neighbours") a.k_neighbours = flag_u64(val(), k);
         else if (k == "--k-folds") a.k_folds = flag_int(val(), k, 1);
         else if (k == "--n-reps") a.n_reps = flag_int(val(), k, 1);
         else if (k == "--seed") a.seed = flag_u64(val(), k);
@@ -171,6 +183,12 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
         throw std::runtime_error("--generate-plots / --output-sig-snps-only call the reference's python scripts and are out of scope here");
     if (a.phen_format != "default" && a.phen_format != "gwalpha_fmt")
         throw std::runtime_error("Invalid phenotype format. Please select: 'default' or 'gwalpha_fmt'"); // phen.rs:161-164
+    if (analysis == Analysis::impute) {
+        if (a.imputation_method != "mean" && a.imputation_method != "aLD-kNNi")
+            throw std::runtime_error("Invalid imputation method `" + a.imputation_method + "`. Please select: 'mean' or 'aLD-kNNi'");
+        if (a.n_loci_to_estimate_distance < 1 || a.k_neighbours < 1)
+            throw std::runtime_error("--n-loci-to-estimate-distance and --k-neighbours must be at least 1");
+    }
     gwalpha_fmt = a.phen_format == "gwalpha_fmt";
     if (analysis == Analysis::gwalpha && !gwalpha_fmt)
         throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "
@@ -181,8 +199,8 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
 }
 
 void check_n_gpus(const Args &a, Analysis analysis) {
-    if (analysis == Analysis::sync2csv) { // one table in (chromosome, position) order: the sort is global
-        if (a.n_gpus > 1) throw std::runtime_error("--n-gpus " + std::to_string(a.n_gpus) + ": `sync2csv` sorts the whole table and runs on one GPU");
+    if (analysis == Analysis::sync2csv || analysis == Analysis::impute) { // one table in (chromosome, position) order: the sort is global
+        if (a.n_gpus > 1) throw std::runtime_error("--n-gpus " + std::to_string(a.n_gpus) + ": `" + a.analysis + "` sorts the whole table and runs on one GPU");
         return;
     }
     if (a.n_gpus > 0 && !takes_n_gpus(analysis))

@@ -26,7 +26,11 @@ struct Args {
     // the input is cut into one contiguous byte range per GPU, each with its own parser threads.  0 = flag absent.
     int n_gpus = 0;
     std::vector<int> gpu_ids; // device ordinals of the ranks (default 0, 1, .., n_gpus - 1)
-    int64_t csv_slab_rows = 0; // sync2csv: rows formatted per call (0 = as many as CSV_SLAB_BYTES of text hold)
+    int64_t csv_slab_rows = 0; // sync2csv, impute: rows formatted per call (0 = as many as CSV_SLAB_BYTES of text hold)
+    // impute (main.rs:125-142)
+    std::string imputation_method = "aLD-kNNi";
+    double min_depth_set_to_missing = 5.0, frac_top_missing_pools = 0.1, frac_top_missing_loci = 0.1;
+    uint64_t n_loci_to_estimate_distance = 10, k_neighbours = 5;
 };
 
 constexpr int64_t CSV_SLAB_BYTES = 256ll << 20; // sync2csv: the text budget of one slab of rows (device buffer + pinned copy)

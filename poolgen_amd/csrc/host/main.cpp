@@ -57,6 +57,10 @@ static int run(int argc, char **argv) {
         csv_out = a.output.empty() ? basename_no_ext(a.fname) + "-" + unix_time_string() + "-allele_frequencies.csv" : a.output;
         probe_output(csv_out);
     }
+    if (analysis == Analysis::impute) { // GenotypesAndPhenotypes::write_csv's default name (sync.rs:1288-1299), probed as early
+        csv_out = a.output.empty() ? "genotypes_and_phenotypes-" + unix_time_string() + "-allele_frequencies.csv" : a.output;
+        probe_output(csv_out);
+    }
     SyncBatch sb;
     if (is_pileup) {
         sb = parse_pileup_file(a.fname, a.n_threads, pf, pinned);
@@ -70,6 +74,8 @@ static int run(int argc, char **argv) {
     if (sb.n != ph.n) throw std::runtime_error("the number of pools in the sync file and in the phenotype file differ");
     if (analysis == Analysis::sync2csv) // sync2csv (main.rs:357-366): every pool, whatever its phenotype
         return done_ok(sync2csv(gpu, sb, ph, flt, a.keep_p_minus_1, csv_out, a.csv_slab_rows, lap));
+    if (analysis == Analysis::impute) // impute (main.rs:367-396): every pool, all alleles, coverages
+        return done_ok(impute(gpu, sb, ph, flt, a, csv_out, lap));
     const int k = ph.k;
     const bool popgen = pgh::popgen(analysis);
 

@@ -41,7 +41,7 @@ struct LocusCountsAndPhenotypes { // structs_and_traits.rs:131-136
 enum class Analysis {
     chisq_test, pearson_corr, ols_iter, fisher_exact_test, gwalpha,
     ols_iter_with_kinship, mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d, gudmc,
-    sync2csv, pileup2sync
+    sync2csv, impute, pileup2sync
 };
 // ... by name, in the order in which the CLI's messages list them: the one place where the names are written out
 struct AnalysisName { const char *name; Analysis id; };
@@ -51,7 +51,8 @@ constexpr AnalysisName ANALYSES[] = {
     {"ols_iter_with_kinship", Analysis::ols_iter_with_kinship}, {"mle_iter_with_kinship", Analysis::mle_iter_with_kinship},
     {"genomic_prediction_cross_validation", Analysis::genomic_prediction_cross_validation}, {"fst", Analysis::fst},
     {"heterozygosity", Analysis::heterozygosity}, {"watterson_estimator", Analysis::watterson_estimator},
-    {"tajima_d", Analysis::tajima_d}, {"gudmc", Analysis::gudmc}, {"sync2csv", Analysis::sync2csv}};
+    {"tajima_d", Analysis::tajima_d}, {"gudmc", Analysis::gudmc}, {"sync2csv", Analysis::sync2csv},
+    {"impute", Analysis::impute}};
 inline bool per_locus(Analysis a) { return a <= Analysis::gwalpha; }
 inline bool popgen(Analysis a) { return a >= Analysis::fst && a <= Analysis::gudmc; } // all pools, coverages, windows (main.rs:427-502)
 inline bool counts_only(Analysis a) { return a == Analysis::chisq_test || a == Analysis::fisher_exact_test; } // one row per locus, no phenotype used

@@ -10,12 +10,14 @@ Method names follow the reference operators they stand in for:
   gp_ols               gp::ols                       (gp/ols.rs:8-101)
   gudmc                popgen::gudmc                 (popgen/gudmc.rs:64-462)
   freq_csv             FileSyncPhen::write_csv's rows (base/sync.rs:1182-1262)
+  impute               imputation::impute_mean / impute_aLDkNN (imputation/*.rs)
 All heavy arguments are torch CUDA tensors (device memory owned by torch); results are
 torch CUDA tensors.  Everything is computed by libpoolgen_hip.so.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -37,6 +39,12 @@ class Filter:
     def to_c(self) -> PgFilter:
         return PgFilter(int(self.remove_ns), 0, int(self.min_coverage_depth),
                         float(self.min_allele_frequency), float(self.max_missingness_rate))
+
+
+def _sensible_round(x: float, digits: int) -> float:
+    """sensible_round (base/helpers.rs): round half away from zero at `digits` decimals"""
+    f = 10.0 ** digits
+    return math.copysign(math.floor(abs(x) * f + 0.5), x) / f
 
 
 def _host_f64(a) -> np.ndarray:
@@ -495,6 +503,139 @@ class Engine:
         if need.value:
             self._check(self._lib.pg_csv_freq_rows_dev(*args, out.data_ptr(), need.value, C.byref(need)), "pg_csv_freq_rows_dev")
         return out
+
+    # ---- imputation (src/imputation/) ------------------------------------------------------------
+    def _impute_args(self, M, locus_col, n):
+        p, ld, n = self._g_dims(M, n)
+        lc = np.ascontiguousarray(locus_col, dtype=np.int64)
+        return p, ld, n, lc, len(lc) - 1
+
+    def set_missing_by_depth(self, G, cov, locus_col, min_depth: float = 5.0, n: int | None = None):
+        """set_missing_by_depth (filtering_missing.rs:15-44), in place on G and cov (cov laid out like G, as load_frequencies
+        returns it): cov < min_depth -> NaN coverage and NaN frequencies; the last locus keeps its frequencies, as written."""
+        p, ld, n, lc, L = self._impute_args(G, locus_col, n)
+        assert cov.shape == G.shape
+        self._check(self._lib.pg_set_missing_by_depth_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64),
+                                                          p, n, ld, lc.ctypes.data, L, float(min_depth)), "pg_set_missing_by_depth_dev")
+
+    def missingness(self, G, cov, locus_col, n: int | None = None):
+        """(NaN frequencies per pool [n], NaN coverages per locus [L]): what the two filters sort by (:53-61, :136-144)."""
+        p, ld, n, lc, L = self._impute_args(G, locus_col, n)
+        assert cov.shape == G.shape
+        pool_nan = np.empty(n, dtype=np.int64); locus_nan = np.empty(L, dtype=np.int64)
+        self._check(self._lib.pg_missingness_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
+                                                 lc.ctypes.data, L, pool_nan.ctypes.data, locus_nan.ctypes.data), "pg_missingness_dev")
+        return pool_nan, locus_nan
+
+    @staticmethod
+    def top_missing_keep(nan_count, frac: float, what: str = "pools") -> np.ndarray:
+        """The keep rule of filter_out_top_missing_pools / _loci (:63-86, :146-170) from NaN counts: the kept indices,
+        ascending.  An empty result is the reference's error."""
+        counts = np.ascontiguousarray(nan_count, dtype=np.int64)
+        keep = np.empty(max(len(counts), 1), dtype=np.int64)
+        left = load_library().pg_host_top_missing_keep(counts.ctypes.data, len(counts), float(frac), keep.ctypes.data)
+        if left < 0:
+            raise ValueError("top_missing_keep: bad argument")
+        if left == 0:
+            raise NativeError(f"No {what} left after filtering, please reduce 'frac_top_missing_{what}'")
+        return keep[:left].copy()
+
+    def impute_compact(self, G, cov, locus_col, keep_pools, keep_loci, col_locus=None, col_allele=None, n: int | None = None):
+        """G, cov and the column labels of the kept pools and loci -> (G, cov, locus_col, col_locus, col_allele) of the kept
+        part (labels None where none were given)."""
+        p, ld, n, lc, L = self._impute_args(G, locus_col, n)
+        kp = np.ascontiguousarray(keep_pools, dtype=np.int64); kl = np.ascontiguousarray(keep_loci, dtype=np.int64)
+        if len(kl) == 0 or len(kp) == 0 or kl.min() < 0 or kl.max() >= L:
+            raise ValueError("impute_compact: nothing kept, or a locus out of range")
+        p_out = int((lc[kl + 1] - lc[kl]).sum())
+        n_out = len(kp)
+        ld_out = n_out + (n_out & 1)
+        dev = G.device
+        G2 = torch.empty((p_out, ld_out), dtype=torch.float64, device=dev)
+        cov2 = torch.empty((p_out, ld_out), dtype=torch.float64, device=dev) if cov is not None else None
+        cl2 = torch.empty(p_out, dtype=torch.int64, device=dev) if col_locus is not None else None
+        ca2 = torch.empty(p_out, dtype=torch.int32, device=dev) if col_allele is not None else None
+        lc2 = np.empty(len(kl) + 1, dtype=np.int64)
+        ptr = lambda t, dt: self._dev(t, dt) if t is not None else None
+        self._check(self._lib.pg_impute_compact_dev(self._ctx, self._dev(G, torch.float64), ptr(cov, torch.float64), p, n, ld,
+                                                    ptr(col_locus, torch.int64), ptr(col_allele, torch.int32), lc.ctypes.data, L,
+                                                    kp.ctypes.data, n_out, kl.ctypes.data, len(kl), G2.data_ptr(),
+                                                    ptr(cov2, torch.float64), ld_out, ptr(cl2, torch.int64), ptr(ca2, torch.int32),
+                                                    lc2.ctypes.data), "pg_impute_compact_dev")
+        return G2, cov2, lc2, cl2, ca2
+
+    def impute_mean(self, G, locus_col, n: int | None = None):
+        """mean_imputation (mean_imputation.rs:6-41), in place."""
+        p, ld, n, lc, L = self._impute_args(G, locus_col, n)
+        self._check(self._lib.pg_impute_mean_dev(self._ctx, self._dev(G, torch.float64), p, n, ld, lc.ctypes.data, L), "pg_impute_mean_dev")
+
+    def impute_aldknn(self, G, locus_col, win_head, win_tail, n_loci_to_estimate_distance: int = 10, k_neighbours: int = 5,
+                      scratch_bytes: int = 0, n: int | None = None) -> torch.Tensor:
+        """adaptive_ld_knn_imputation (adaptive_ld_knn_imputation.rs:174-341) -> the imputed copy of G.  scratch_bytes bounds
+        the device memory of one batch of windows (0: 1 GiB)."""
+        p, ld, n, lc, L = self._impute_args(G, locus_col, n)
+        wh = np.ascontiguousarray(win_head, dtype=np.int64); wt = np.ascontiguousarray(win_tail, dtype=np.int64)
+        out = torch.empty_like(G)
+        self._check(self._lib.pg_impute_aldknn_dev(self._ctx, self._dev(G, torch.float64), p, n, ld, lc.ctypes.data, L, wh.ctypes.data,
+                                                   wt.ctypes.data, len(wh), int(n_loci_to_estimate_distance), int(k_neighbours),
+                                                   int(scratch_bytes), out.data_ptr()), "pg_impute_aldknn_dev")
+        return out
+
+    def impute_mark_cov(self, cov, locus_col, n: int | None = None):
+        """NaN coverages of the loci that have a coverage at all become +inf (mean_imputation.rs:42-59), in place."""
+        p, ld, n, lc, L = self._impute_args(cov, locus_col, n)
+        self._check(self._lib.pg_impute_mark_cov_dev(self._ctx, self._dev(cov, torch.float64), p, n, ld, lc.ctypes.data, L),
+                    "pg_impute_mark_cov_dev")
+
+    def impute(self, G, cov, locus_col, chrom_ids=None, pos=None, method: str = "mean", min_depth_set_to_missing: float = 5.0,
+               frac_top_missing_pools: float = 0.1, frac_top_missing_loci: float = 0.1, window_size_bp: int = 100,
+               window_slide_size_bp: int = 50, min_loci_per_window: int = 10, n_loci_to_estimate_distance: int = 10,
+               k_neighbours: int = 5, col_locus=None, col_allele=None, scratch_bytes: int = 0, n: int | None = None):
+        """impute_mean / impute_aLDkNN (mean_imputation.rs:65-162, adaptive_ld_knn_imputation.rs:371-477) from the loaded
+        matrix to the table the writer prints: missing by depth, the sparsest pools and loci out, the imputation, the coverage
+        mark, the loci still missing everywhere out.  G and cov are not modified.  chrom_ids / pos: per locus, for the windows
+        of "aLD-kNNi".  Returns a dict: G, cov (imputed, kept part), pools and loci (kept indices into the input), locus_col,
+        col_locus / col_allele (labels of the kept columns when given), missing_rate (percent after every step, as the
+        reference prints them)."""
+        if method not in ("mean", "aLD-kNNi"):
+            raise ValueError("impute: method must be 'mean' or 'aLD-kNNi'")
+        rates = []
+
+        def note(G_, cov_, lc_):
+            ln = self.missingness(G_, cov_, lc_, n=n_now)[1]
+            rates.append(_sensible_round(float(ln.sum()) * 100.0 / float(n_now * len(ln)), 2))
+            return ln
+
+        n_now = self._g_dims(G, n)[2]
+        G = G.clone(); cov = cov.clone()
+        lc = np.ascontiguousarray(locus_col, dtype=np.int64)
+        note(G, cov, lc)
+        self.set_missing_by_depth(G, cov, lc, min_depth_set_to_missing, n=n_now)
+        pool_nan, locus_nan = self.missingness(G, cov, lc, n=n_now)
+        rates.append(_sensible_round(float(locus_nan.sum()) * 100.0 / float(n_now * len(locus_nan)), 2))
+        pools = self.top_missing_keep(pool_nan, frac_top_missing_pools, "pools")
+        all_loci = np.arange(len(lc) - 1, dtype=np.int64)
+        G, cov, lc, col_locus, col_allele = self.impute_compact(G, cov, lc, pools, all_loci, col_locus, col_allele, n=n_now)
+        n_now = len(pools)
+        locus_nan = note(G, cov, lc)
+        loci = self.top_missing_keep(locus_nan, frac_top_missing_loci, "loci")
+        G, cov, lc, col_locus, col_allele = self.impute_compact(G, cov, lc, np.arange(n_now), loci, col_locus, col_allele, n=n_now)
+        note(G, cov, lc)
+        if method == "mean":
+            self.impute_mean(G, lc, n=n_now)
+        else:
+            if chrom_ids is None or pos is None:
+                raise ValueError("impute: aLD-kNNi needs chrom_ids and pos of the loci")
+            ch = np.ascontiguousarray(chrom_ids, dtype=np.int32)[loci]; po = np.ascontiguousarray(pos, dtype=np.uint64)[loci]
+            head, tail = self.sliding_windows(ch, po, window_size_bp, window_slide_size_bp, min_loci_per_window)
+            G = self.impute_aldknn(G, lc, head, tail, n_loci_to_estimate_distance, k_neighbours, scratch_bytes, n=n_now)
+        self.impute_mark_cov(cov, lc, n=n_now)
+        locus_nan = note(G, cov, lc)
+        keep2 = self.top_missing_keep(locus_nan, 1.0, "loci")
+        G, cov, lc, col_locus, col_allele = self.impute_compact(G, cov, lc, np.arange(n_now), keep2, col_locus, col_allele, n=n_now)
+        note(G, cov, lc)
+        return dict(G=G, cov=cov, pools=pools, loci=loci[keep2], locus_col=lc, col_locus=col_locus, col_allele=col_allele,
+                    missing_rate=rates)
 
     # ---- popgen -------------------------------------------------------------------------------
     def sliding_windows(self, chrom_ids, pos, window_size_bp: int, window_slide_size_bp: int, min_loci_per_window: int):
