@@ -67,7 +67,7 @@ int pg_synchronize(pg_ctx *ctx);
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
                     PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_CSV = 13,
-                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_COUNT = 17 };
+                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_COUNT = 18 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
@@ -467,6 +467,61 @@ int pg_host_csv_freq_rows(const double *G, int64_t ld, int n, int64_t row0, int6
                           const int32_t *col_allele, const int32_t *locus_chrom, const uint64_t *locus_pos,
                           const char *chrom_text, const int32_t *chrom_off, int n_chrom, char *text, int64_t cap,
                           int64_t *bytes, int n_threads);
+
+/* ---------------------------------------------------------------------------------------
+ * vcf2sync's reader (base/vcf.rs: lparse :12-68, filter :117-178, vcf_to_sync :182-230, per_chunk :268-300): a slab of VCF
+ * text -- it starts at a line start, its last line may lack the newline -- to the allele counts of the loci the filter
+ * keeps, in file order.  pool_sizes (host, n_sizes <= 2048 of them) and the three thresholds are FilterStats'.
+ * Outputs, `kept` rows each:
+ *   counts    uint32, kept x n_pools x 6, the six numbers of a pool in the order vcf_to_sync writes them (A:T:C:G:D:N; the
+ *             sync reader reads the same positions back as A,T,C,G,N,D: quirk 13 of SURVEY.md)
+ *   pos       uint64;  ref: the reference character ('D' for anything that is not one character)
+ *   line_off  the byte offset of the line in the slab;  chrom_len: the length of its first field (the chromosome's name)
+ * info->kept, data_lines (lines that do not start with '#'), n_pools (the sample fields of the data lines; 0 without data
+ * lines), chrom_line_off (the last line that begins with "#CHROM", or -1).
+ * Capacities: cap_loci rows of pos / ref / line_off / chrom_len, cap_counts elements of counts.  info->kept and n_pools are
+ * always set; more rows or elements than the capacities hold fails with PG_ERR_INVALID and writes nothing (capacities of 0
+ * are the size query, the output pointers may then be NULL).  Nothing at or behind the stated capacities is written.
+ * Where the reference panics the call fails with PG_ERR_INVALID: info->err_line_off is the offset of the FIRST such line in
+ * file order, info->err_reason the smallest pg_vcf_reason that holds of it (else -1 and 0); kept and n_pools are then 0.
+ * Three reasons are deliberate deviations (the reference would go on): PG_VCF_E_COUNT32, PG_VCF_E_HIGH_BYTE, PG_VCF_E_POOLS.
+ * The result does not depend on where a text is cut into slabs (the caller compares n_pools between slabs).
+ * The device form parses on the GPU (index, parse, scan, emit on the context's stream; it synchronises to read the sizes,
+ * and the rows are complete once the stream has passed the call); the host form is plain C++ on n_threads threads, no
+ * context, and gives the same bytes.
+ * ------------------------------------------------------------------------------------- */
+enum pg_vcf_reason {
+    PG_VCF_E_EMPTY = 1,      /* an empty line (per_chunk indexes its first byte) */
+    PG_VCF_E_SHORT = 2,      /* a data line under 20 bytes (per_chunk slices &line[0..20] for its message before it parses) */
+    PG_VCF_E_LONG = 3,       /* a line of 2^31 bytes or more (this library's limit) */
+    PG_VCF_E_FIELDS = 4,     /* fewer than 9 tab-separated fields */
+    PG_VCF_E_POS = 5,        /* POS is no u64 */
+    PG_VCF_E_HIGH_BYTE = 6,  /* deviation: a byte >= 0x80 in REF or ALT (no UTF-8 decoding here) */
+    PG_VCF_E_AD_KEY = 7,     /* FORMAT has no AD, or more than one */
+    PG_VCF_E_POOLS = 8,      /* deviation: more samples than pool sizes, or not as many as the first data line has */
+    PG_VCF_E_SUBFIELDS = 9,  /* a sample with too few ':' pieces to hold AD */
+    PG_VCF_E_AD_VALUE = 10,  /* an AD value that is no u64 ("." among them) */
+    PG_VCF_E_COUNT32 = 11,   /* deviation: an AD value above 2^32 - 1 (the counts are 32-bit) */
+    PG_VCF_E_NO_SAMPLES = 12,/* no sample fields on a line that passes the breadth rule (to_counts indexes pool 0) */
+    PG_VCF_E_AD_RAGGED = 13, /* a pool with fewer AD values than pool 0, on a line that passes the breadth rule */
+    PG_VCF_E_ALLELE_OOB = 14 /* a kept line whose first A/T/C/G/D/N allele has no AD column in pool 0 */
+};
+typedef struct {
+    int64_t kept;
+    int64_t data_lines;
+    int64_t chrom_line_off;
+    int64_t err_line_off;
+    int32_t n_pools;
+    int32_t err_reason;
+} pg_vcf_info;
+int pg_vcf_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t bytes, const double *pool_sizes, int n_sizes,
+                     uint64_t min_coverage_depth, double min_coverage_breadth, double min_allele_frequency,
+                     uint32_t *counts_dev, uint64_t *pos_dev, uint8_t *ref_dev, int64_t *line_off_dev, int32_t *chrom_len_dev,
+                     int64_t cap_loci, int64_t cap_counts, pg_vcf_info *info);
+int pg_host_vcf_parse(const char *text, int64_t bytes, const double *pool_sizes, int n_sizes, uint64_t min_coverage_depth,
+                      double min_coverage_breadth, double min_allele_frequency, uint32_t *counts, uint64_t *pos, uint8_t *ref,
+                      int64_t *line_off, int32_t *chrom_len, int64_t cap_loci, int64_t cap_counts, pg_vcf_info *info,
+                      int n_threads);
 
 /* ---------------------------------------------------------------------------------------
  * impute (src/imputation/: filtering_missing.rs, mean_imputation.rs, adaptive_ld_knn_imputation.rs; CLI main.rs:125-142,

@@ -315,9 +315,9 @@ struct GenotypesAndPhenotypes {
 
 
 // ---- the analyses: cli_streamed.cpp (run_kinship_streamed: -1 = load the whole file instead), cli_matrix.cpp, cli_popgen.cpp ----
-int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, bool is_pileup, const PileupFilter &pf, const pg_filter &flt,
+int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, InputKind kind, const PileupFilter &pf, const pg_filter &flt,
                          const RankSetup &rs);
-int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analysis op, bool is_pileup, const PileupFilter &pf,
+int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analysis op, InputKind kind, const PileupFilter &pf,
                        const pg_filter &flt, const RankSetup &rs);
 GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt,
                                                      bool keep_p_minus_1, bool remove_missing, bool with_coverages, Lap &lap);

@@ -42,13 +42,14 @@ static bool takes_n_gpus(Analysis a) { return per_locus(a) || a == Analysis::ols
 // (the help text also names analyses in prose, here and at the --window-*, --popgen-as-documented and --n-gpus flags)
 static const char *USAGE =
     "poolgen <analysis> -f <input> -p <phenotypes.csv> [flags]      (MI355X build of the per-locus regression path)\n"
-    "analyses: pileup2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
+    "analyses: pileup2sync, vcf2sync, fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
     "          mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d,\n"
     "          gudmc, sync2csv, impute\n"
-    "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup (converted in memory: exactly what pileup2sync followed by the\n"
-    "                                     analysis on its sync file gives -- including the reference's column quirk: pileup2sync\n"
-    "                                     writes A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on pileup-derived\n"
-    "                                     counts the default N removal drops the DELETION column and --keep-ns keeps it)\n"
+    "  -f, --fname <file>                 *.sync, or *.pileup / *.mpileup / *.vcf (converted in memory: exactly what pileup2sync or vcf2sync\n"
+    "                                     followed by the analysis on its sync file gives -- including the reference's column quirk: both\n"
+    "                                     write A:T:C:G:DEL:N, the sync reader labels the columns A,T,C,G,N,DEL, so on such counts the\n"
+    "                                     default N removal drops the DELETION column and --keep-ns keeps it).  A VCF is parsed on the\n"
+    "                                     GPU (the AD field of every sample; vcf2sync needs a GPU too) and taken by one GPU\n"
     "  -p, --phen-fname <file>            delimited file: pool name, pool size, trait value(s)\n"
     "  -o, --output <file>                must not exist; default: derived from the input name and the time\n"
     "      --phen-delim <,>  --phen-name-col <0>  --phen-pool-size-col <1>  --phen-value-col <2[,3..]>\n"
@@ -199,6 +200,8 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
 }
 
 void check_n_gpus(const Args &a, Analysis analysis) {
+    if (a.n_gpus > 1 && input_kind(a.fname) == InputKind::vcf) // its pieces are parsed on the device that analyses them; sharing them out is left for later
+        throw std::runtime_error("--n-gpus " + std::to_string(a.n_gpus) + ": a VCF input is taken by one GPU; convert it with vcf2sync first to use several");
     if (analysis == Analysis::sync2csv || analysis == Analysis::impute) { // one table in (chromosome, position) order: the sort is global
         if (a.n_gpus > 1) throw std::runtime_error("--n-gpus " + std::to_string(a.n_gpus) + ": `" + a.analysis + "` sorts the whole table and runs on one GPU");
         return;

@@ -78,7 +78,7 @@ struct KinRank {
 };
 
 // ---- phase A, per rank: parse piece c + 1 || H2D + loader + partial kinship of piece c -----------------------
-static void kin_load_pieces(KinRank &K, RankGate &gate, const Args &a, const Phen &ph, const PiecedInput &in, bool is_pileup, const PileupFilter &pf,
+static void kin_load_pieces(KinRank &K, RankGate &gate, const Args &a, const Phen &ph, const PiecedInput &in, InputKind kind, const PileupFilter &pf,
                             const pg_filter &flt, const RankSetup &rs, const std::vector<int32_t> &pool_map, int n2, int64_t ld) {
     const int n = ph.n, R = rs.n_ranks;
     auto clk = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -92,7 +92,7 @@ static void kin_load_pieces(KinRank &K, RankGate &gate, const Args &a, const Phe
         gate.pass([&] { gpu.ok(pg_comm_init_rank(gpu.c, rs.id, R, K.rank), "RCCL communicator"); });
     if (K.c0 >= K.c1) return;
     // (the pinned slots, the counts and the 16-bit scratch live to the end of this phase only)
-    PieceReader pieces(in.mf, in.cuts, K.c0, K.c1, K.device, K.threads, is_pileup, pf, n, true);
+    PieceReader pieces(in.mf, in.cuts, K.c0, K.c1, K.device, K.threads, kind, pf, n, true);
     std::vector<double> S_piece((size_t)n2 * n2);
     DeviceBuf<uint32_t> counts_dev;
     CountsUpload upload;
@@ -167,7 +167,7 @@ static void kin_fit_pieces(KinRank &K, RankGate &gate, const RankSetup &rs, cons
     K.Gs.clear();
 }
 
-static int kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, size_t chunk_bytes, bool is_pileup, const PileupFilter &pf,
+static int kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, size_t chunk_bytes, InputKind kind, const PileupFilter &pf,
                             const pg_filter &flt, const RankSetup &rs) {
     const int R = rs.n_ranks, n = ph.n, k = ph.k;
     const PiecedInput in(a.fname, chunk_bytes, R);
@@ -187,7 +187,7 @@ static int kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, 
         K.gpu = rank_ctx(r, K.device, gpu0, K.own);
     }
     RankGate gate(R);
-    run_ranks(R, [&](int r) { kin_load_pieces(ranks[r], gate, a, ph, in, is_pileup, pf, flt, rs, pool_map, n2, ld); });
+    run_ranks(R, [&](int r) { kin_load_pieces(ranks[r], gate, a, ph, in, kind, pf, flt, rs, pool_map, n2, ld); });
     if (std::getenv("PGH_TIMING"))
         for (const KinRank &K : ranks)
             std::fprintf(stderr, "poolgen: rank %d (GPU %d, pieces %d..%d, %d parser threads): waited for the parser %.3f s, host bookkeeping %.3f s, copies + device %.3f s\n",
@@ -240,13 +240,13 @@ static int kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, 
     return done_ok(out);
 }
 
-int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, bool is_pileup, const PileupFilter &pf, const pg_filter &flt,
+int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, InputKind kind, const PileupFilter &pf, const pg_filter &flt,
                          const RankSetup &rs) {
     bool automatic = false;
     const size_t piece = piece_bytes(a, true, rs.n_ranks, &automatic);
     if (piece == 0) return -1;
     try {
-        return kinship_streamed(a, ph, gpu0, lap, piece, is_pileup, pf, flt, rs);
+        return kinship_streamed(a, ph, gpu0, lap, piece, kind, pf, flt, rs);
     } catch (const UnsortedInput &) { // falls back to the whole-file path unless the pieces were asked for explicitly
         if (!automatic || a.n_gpus > 0) throw;
     }
@@ -258,7 +258,7 @@ int run_kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, boo
 // the file is taken in pieces whatever its size -- the worker threads parse piece c + 1 into one of two pinned buffers
 // (16-bit counts when they fit) while the GPU takes piece c and its rows are formatted and appended, in file order
 // (sync.rs:927-946).  Nothing of the size of the input is ever allocated, pinned or copied in one go.
-int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analysis op, bool is_pileup, const PileupFilter &pf,
+int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analysis op, InputKind kind, const PileupFilter &pf,
                        const pg_filter &flt, const RankSetup &rs) {
     const int R = rs.n_ranks;
     const PiecedInput in(a.fname, piece_bytes(a, false, R), R);
@@ -303,7 +303,7 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
         Ctx &gpu = *rank_ctx(r, device, gpu0, own);
         const int c0 = in.first[r], c1 = in.first[r + 1];
         if (c0 >= c1) return;
-        PieceReader pieces(in.mf, in.cuts, c0, c1, device, threads, is_pileup, pf, 0, !subset);
+        PieceReader pieces(in.mf, in.cuts, c0, c1, device, threads, kind, pf, 0, !subset);
         FILE *fo = nullptr;
         DeviceBuf<uint32_t> counts_dev;
         DeviceBuf<int32_t> n_out_dev, ids_dev;

@@ -1,10 +1,11 @@
 // main.cpp -- `poolgen`, the command line over libpoolgen_hip.so: run() reads the flags (cli_args.h) and the phenotype file,
-// answers pileup2sync on the host, sets up the ranks and hands over to the analysis' translation unit -- the drivers that take
+// answers pileup2sync on the host and vcf2sync with the GPU's parser, sets up the ranks and hands over to the analysis' translation unit -- the drivers that take
 // the input in pieces (cli_streamed.cpp), or the loaded matrix (cli_matrix.cpp) and on it the popgen tools (cli_popgen.cpp), the
 // cross-validation (gp_cv.h) or the kinship GWAS.  Parsing / formatting / ordering follow the reference (base/sync.rs:606-970,
 // :972-1180; gwas/ols.rs:255-275, :372-433); anything else the reference CLI offers is out of scope and reported as such.
 #include "cli.h"
 #include "gp_cv.h"
+#include "vcf.h"
 #include <cstring>
 
 static int run(int argc, char **argv) {
@@ -31,27 +32,33 @@ static int run(int argc, char **argv) {
         std::cerr << kept << " loci written\n";
         return done_ok(out);
     }
+    if (analysis == Analysis::vcf2sync) { // main.rs:226-238; the text is parsed on the GPU (no GPU: an error, there is no host fallback)
+        std::string out = a.output;
+        if (out.empty()) out = basename_no_ext(a.fname) + "-" + unix_time_string() + ".sync"; // vcf.rs:317-337
+        probe_output(out);                                                                    // :339, before any work
+        check_n_gpus(a, analysis);
+        const int64_t kept = vcf_to_sync_file(a.gpu_ids.empty() ? 0 : a.gpu_ids[0], a.fname, pf, out, a.n_threads);
+        lap("vcf2sync");
+        std::cerr << kept << " loci written\n";
+        return done_ok(out);
+    }
     check_n_gpus(a, analysis);
     const RankSetup ranks = rank_setup(a, analysis == Analysis::ols_iter_with_kinship);
     Ctx gpu(ranks.devices[0]); // first: the pinned allocator below needs a HIP context
     lap("start-up");
     // A pileup input (*.pileup / *.mpileup) is converted in memory -- the counts pileup2sync would write and the
     // sync reader would read back, without the text in between (an extension: the reference needs the sync file).
-    auto ends_with = [](const std::string &x, const char *suf) {
-        const size_t m = std::strlen(suf);
-        return x.size() >= m && x.compare(x.size() - m, m, suf) == 0;
-    };
-    const bool is_pileup = ends_with(a.fname, ".pileup") || ends_with(a.fname, ".mpileup");
+    const InputKind kind = input_kind(a.fname); // a VCF input likewise: the counts vcf2sync would write, parsed on the GPU
     pg_filter flt{};
     flt.remove_ns = a.keep_ns ? 0 : 1;
     flt.min_coverage_depth = a.min_coverage_depth;
     flt.min_allele_frequency = a.min_allele_frequency;
     flt.max_missingness_rate = a.max_missingness_rate;
     if (analysis == Analysis::ols_iter_with_kinship) { // in pieces where the input is large or several GPUs take it
-        const int rc = run_kinship_streamed(a, ph, gpu, lap, is_pileup, pf, flt, ranks);
+        const int rc = run_kinship_streamed(a, ph, gpu, lap, kind, pf, flt, ranks);
         if (rc >= 0) return rc;
     }
-    if (per_locus(analysis)) return run_batch_streamed(a, ph, gpu, lap, analysis, is_pileup, pf, flt, ranks);
+    if (per_locus(analysis)) return run_batch_streamed(a, ph, gpu, lap, analysis, kind, pf, flt, ranks);
     std::string csv_out; // sync2csv: the file is refused before any work is done (sync.rs:1191-1216)
     if (analysis == Analysis::sync2csv) {
         csv_out = a.output.empty() ? basename_no_ext(a.fname) + "-" + unix_time_string() + "-allele_frequencies.csv" : a.output;
@@ -62,9 +69,12 @@ static int run(int argc, char **argv) {
         probe_output(csv_out);
     }
     SyncBatch sb;
-    if (is_pileup) {
+    if (kind == InputKind::pileup) {
         sb = parse_pileup_file(a.fname, a.n_threads, pf, pinned);
         lap("pileup -> counts");
+    } else if (kind == InputKind::vcf) {
+        sb = parse_vcf_file(ranks.devices[0], a.fname, a.n_threads, pf, pinned);
+        lap("vcf -> counts");
     } else {
         // the analyses on the loaded matrix copy the counts themselves: 16-bit counts when they fit
         sb = parse_sync_file(a.fname, a.n_threads, pinned, /*compact16=*/true);

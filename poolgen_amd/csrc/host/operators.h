@@ -41,12 +41,12 @@ struct LocusCountsAndPhenotypes { // structs_and_traits.rs:131-136
 enum class Analysis {
     chisq_test, pearson_corr, ols_iter, fisher_exact_test, gwalpha,
     ols_iter_with_kinship, mle_iter_with_kinship, genomic_prediction_cross_validation, fst, heterozygosity, watterson_estimator, tajima_d, gudmc,
-    sync2csv, impute, pileup2sync
+    sync2csv, impute, pileup2sync, vcf2sync
 };
 // ... by name, in the order in which the CLI's messages list them: the one place where the names are written out
 struct AnalysisName { const char *name; Analysis id; };
 constexpr AnalysisName ANALYSES[] = {
-    {"pileup2sync", Analysis::pileup2sync}, {"fisher_exact_test", Analysis::fisher_exact_test}, {"chisq_test", Analysis::chisq_test},
+    {"pileup2sync", Analysis::pileup2sync}, {"vcf2sync", Analysis::vcf2sync}, {"fisher_exact_test", Analysis::fisher_exact_test}, {"chisq_test", Analysis::chisq_test},
     {"pearson_corr", Analysis::pearson_corr}, {"ols_iter", Analysis::ols_iter}, {"gwalpha", Analysis::gwalpha},
     {"ols_iter_with_kinship", Analysis::ols_iter_with_kinship}, {"mle_iter_with_kinship", Analysis::mle_iter_with_kinship},
     {"genomic_prediction_cross_validation", Analysis::genomic_prediction_cross_validation}, {"fst", Analysis::fst},

@@ -4,8 +4,10 @@
 #include "gpu_mem.h"
 #include "host_util.h"
 #include "pileup.h"
+#include "vcf.h"
 #include <cstdlib>
 #include <future>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -45,13 +47,14 @@ public:
 
 // Pieces [c0, c1) of `mf` between `cuts`, in turn.  The counts of piece c live in pinned slot c & 1 (two buffers that grow on
 // demand), so the batch next() returned is valid until next() is called again.  expect_n / compact16: see parse_sync_buffer; a
-// pileup piece is converted in memory with `pf`.
+// pileup piece is converted in memory with `pf`, a VCF piece on the device with the thresholds of `pf`.
 class PieceReader {
     const MappedFile &mf_;
     const std::vector<size_t> &cuts_;
     int c_;
     const int c1_, device_, threads_;
-    const bool is_pileup_;
+    const InputKind kind_;
+    std::unique_ptr<VcfReader> vcf_; // a VCF piece is parsed on the rank's device, by a context of the parser's own
     const PileupFilter &pf_;
     const int expect_n_;
     const bool compact16_;
@@ -65,16 +68,19 @@ class PieceReader {
         SyncAlloc al;
         al.alloc = [s = &slot_[c & 1]](size_t bytes) { return s->reserve(bytes); };
         al.release = [](void *) {};
-        SyncBatch parsed = is_pileup_ ? parse_pileup_buffer(b, e, threads_, pf_, al) : parse_sync_buffer(b, e, threads_, expect_n_, al, compact16_);
+        SyncBatch parsed = kind_ == InputKind::vcf      ? vcf_->parse(b, e, al, "the VCF input", threads_)
+                           : kind_ == InputKind::pileup ? parse_pileup_buffer(b, e, threads_, pf_, al)
+                                                        : parse_sync_buffer(b, e, threads_, expect_n_, al, compact16_);
         drop_parsed_text_(b, e);
         return parsed;
     }
     void start() { if (c_ < c1_) next_ = std::async(std::launch::async, [this, c = c_] { return parse(c); }); }
 public:
-    PieceReader(const MappedFile &mf, const std::vector<size_t> &cuts, int c0, int c1, int device, int threads, bool is_pileup,
+    PieceReader(const MappedFile &mf, const std::vector<size_t> &cuts, int c0, int c1, int device, int threads, InputKind kind,
                 const PileupFilter &pf, int expect_n, bool compact16)
-        : mf_(mf), cuts_(cuts), c_(c0), c1_(c1), device_(device), threads_(threads), is_pileup_(is_pileup), pf_(pf), expect_n_(expect_n),
+        : mf_(mf), cuts_(cuts), c_(c0), c1_(c1), device_(device), threads_(threads), kind_(kind), pf_(pf), expect_n_(expect_n),
           compact16_(compact16) {
+        if (kind_ == InputKind::vcf) vcf_ = std::make_unique<VcfReader>(device_, pf_);
         start();
     }
     bool more() const { return c_ < c1_; }

@@ -171,20 +171,7 @@ bool PileupConverter::decode(const char *b, const char *e, Locus &L) const {
 bool PileupConverter::convert(const char *b, const char *e, std::string &out) const {
     Locus L;
     if (!decode(b, e, L)) return false;
-    // ---- pileup_to_sync (:348-371): chr, pos, ref, then A:T:C:G:D:N per pool -----------------------------
-    out.append(L.chrom, L.chrom_len);
-    out.push_back('\t');
-    char num[24];
-    auto put = [&](uint64_t v) { out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); };
-    put(L.pos);
-    out.push_back('\t');
-    out.push_back((char)L.ref);
-    for (int i = 0; i < L.n; ++i)
-        for (int j = 0; j < 6; ++j) {
-            out.push_back(j == 0 ? '\t' : ':');
-            put(L.counts[(size_t)i * 6 + j]);
-        }
-    out.push_back('\n');
+    append_sync_line(out, L.chrom, L.chrom_len, L.pos, L.ref, L.n, L.counts); // pileup_to_sync (:348-371)
     return true;
 }
 
@@ -354,6 +341,16 @@ SyncBatch parse_pileup_buffer(const char *bb, const char *be, int n_threads, con
     sb.chrom_id.resize(w);
     sb.pos.resize(w);
     return sb;
+}
+
+InputKind input_kind(const std::string &fname) {
+    auto ends_with = [&](const char *suf) {
+        const size_t m = std::strlen(suf);
+        return fname.size() >= m && fname.compare(fname.size() - m, m, suf) == 0;
+    };
+    if (ends_with(".pileup") || ends_with(".mpileup")) return InputKind::pileup;
+    if (ends_with(".vcf")) return InputKind::vcf;
+    return InputKind::sync;
 }
 
 } // namespace pgh

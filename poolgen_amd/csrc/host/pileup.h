@@ -1,11 +1,16 @@
 // pileup.h -- samtools mpileup text -> sync lines, the `pileup2sync` front end (base/pileup.rs:11-371, :373-545).
 #pragma once
+#include <charconv>
 #include <cstdint>
 #include <string>
 #include <vector>
 #include "host_util.h"
 
 namespace pgh {
+
+// What the input is, by the name of the file: *.pileup / *.mpileup, *.vcf, anything else is a sync file.
+enum class InputKind { sync, pileup, vcf };
+InputKind input_kind(const std::string &fname);
 
 struct PileupFilter {            // the FilterStats fields PileupLine::filter reads (pileup.rs:239-337)
     bool remove_ns = true;                 // !--keep-ns
@@ -44,6 +49,25 @@ private:
     unsigned char column_[256]; // allele byte -> count column (A,T,C,G,D,N = 0..5), through the lower-case remap when asked for
     unsigned char special_[128]; // 1 for the read codes that are not a base: + - ^ $
 };
+
+// The line of a kept locus in a sync file: chr, pos, ref, then the six counts of every pool joined by ':' (pileup_to_sync,
+// pileup.rs:348-371; vcf_to_sync, vcf.rs:212-229, writes the same).  The one writer of such lines: pileup2sync and vcf2sync.
+template <typename T>
+inline void append_sync_line(std::string &out, const char *chrom, size_t chrom_len, uint64_t pos, unsigned char ref, int n, const T *counts) {
+    out.append(chrom, chrom_len);
+    out.push_back('\t');
+    char num[24];
+    auto put = [&](uint64_t v) { out.append(num, (size_t)(std::to_chars(num, num + sizeof num, v).ptr - num)); };
+    put(pos);
+    out.push_back('\t');
+    out.push_back((char)ref);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < 6; ++j) {
+            out.push_back(j == 0 ? '\t' : ':');
+            put(counts[(size_t)i * 6 + j]);
+        }
+    out.push_back('\n');
+}
 
 // Whole file with `n_threads` workers over byte ranges split at line starts; loci in file order; header
 // "#chr\tpos\tref\t<pool names>" (pileup.rs:519-521); refuses to overwrite (create_new, :511-517).  Returns the

@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._native import KERNEL_IDS, NativeError, PgFilter, load_library
+from ._native import KERNEL_IDS, NativeError, PgFilter, PgVcfInfo, load_library
 
 ALLELES = "ATCGND"  # base/sync.rs:134 reader order
 
@@ -97,6 +97,51 @@ def freq_csv_host(G, col_locus, col_allele, chrom_ids, pos, chrom_names, n=None,
     if rc != 0:   # the buffer has the size asked for, so:
         raise NativeError(f"pg_host_csv_freq_rows failed ({rc}): a cell is no allele frequency (outside [0, 1] and not NaN)")
     return out[:need.value].tobytes()
+
+
+VCF_REASONS = {1: "empty line", 2: "data line under 20 bytes", 3: "line of 2^31 bytes or more", 4: "fewer than 9 fields", 5: "POS is no u64",
+               6: "byte >= 0x80 in REF or ALT", 7: "not exactly one AD in FORMAT", 8: "number of samples", 9: "sample without an AD piece",
+               10: "AD value is no u64", 11: "AD value above 2^32 - 1", 12: "no samples", 13: "fewer AD values than pool 0",
+               14: "allele without an AD column"}
+
+
+class VcfError(NativeError):
+    """A VCF line at which the reference's vcf2sync panics (or one of the documented deviations): `offset` is the byte offset of
+    the first such line of the text, `reason` a pg_vcf_reason."""
+
+    def __init__(self, what, offset, reason):
+        super().__init__(f"{what}: the line at byte {offset} of the text: {VCF_REASONS.get(reason, reason)}")
+        self.offset, self.reason = int(offset), int(reason)
+
+
+def _vcf_result(info, counts, pos, ref, off, clen):
+    k, n = info.kept, info.n_pools
+    return {"counts": counts[:k * n * 6].reshape(k, n, 6), "pos": pos[:k], "ref": ref[:k], "line_off": off[:k], "chrom_len": clen[:k],
+            "data_lines": int(info.data_lines), "n_pools": int(n), "chrom_line_off": int(info.chrom_line_off)}
+
+
+def vcf_parse_host(text, pool_sizes, min_coverage_depth=1, min_coverage_breadth=1.0, min_allele_frequency=0.001, n_threads=1):
+    """Engine.vcf_parse on the host (pg_host_vcf_parse: plain C++, no GPU): the same dictionary, of numpy arrays."""
+    lib = load_library()
+    t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+    ps = _host_f64(pool_sizes)
+    info = PgVcfInfo()
+    args = [t.ctypes.data if t.size else None, t.size, ps.ctypes.data, len(ps), int(min_coverage_depth), float(min_coverage_breadth),
+            float(min_allele_frequency)]
+    rc = lib.pg_host_vcf_parse(*args, None, None, None, None, None, 0, 0, C.byref(info), int(n_threads))
+    if info.err_reason:
+        raise VcfError("pg_host_vcf_parse", info.err_line_off, info.err_reason)
+    k, n = info.kept, info.n_pools
+    if rc != 0 and k == 0:
+        raise NativeError(f"pg_host_vcf_parse failed ({rc}): bad arguments")
+    counts = np.empty(k * n * 6, dtype=np.uint32); pos = np.empty(k, dtype=np.uint64); ref = np.empty(k, dtype=np.uint8)
+    off = np.empty(k, dtype=np.int64); clen = np.empty(k, dtype=np.int32)
+    if k:
+        rc = lib.pg_host_vcf_parse(*args, counts.ctypes.data, pos.ctypes.data, ref.ctypes.data, off.ctypes.data, clen.ctypes.data, k,
+                                   counts.size, C.byref(info), int(n_threads))
+        if rc != 0:
+            raise NativeError(f"pg_host_vcf_parse failed ({rc})")
+    return _vcf_result(info, counts, pos, ref, off, clen)
 
 
 class Engine:
@@ -503,6 +548,39 @@ class Engine:
         if need.value:
             self._check(self._lib.pg_csv_freq_rows_dev(*args, out.data_ptr(), need.value, C.byref(need)), "pg_csv_freq_rows_dev")
         return out
+
+    def vcf_parse(self, text, pool_sizes, min_coverage_depth: int = 1, min_coverage_breadth: float = 1.0,
+                  min_allele_frequency: float = 0.001):
+        """A slab of VCF text -- bytes, a NumPy uint8 array or a torch uint8 tensor (on the device it is parsed in place); it starts
+        at a line start, its last line may lack the newline -- to what vcf2sync keeps of it (base/vcf.rs), parsed on the GPU.
+        A dictionary: counts (kept x n_pools x 6, the six in the order vcf_to_sync writes them; the uint32 bits as int32, as the
+        loader takes them), pos (the uint64 bits as int64: torch has no uint64 arithmetic), ref (uint8), line_off (int64), chrom_len (int32) as tensors on the device, and
+        the integers data_lines, n_pools, chrom_line_off.  A line at which the reference panics raises VcfError."""
+        dev = torch.device("cuda", self.device)
+        if isinstance(text, torch.Tensor):
+            t = text.to(dev)
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError("vcf_parse: text must be a contiguous uint8 tensor")
+        else:
+            a = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+            t = torch.from_numpy(a.copy()).to(dev)
+        ps = _host_f64(pool_sizes)
+        info = PgVcfInfo()
+        args = [self._ctx, t.data_ptr() if t.numel() else None, t.numel(), ps.ctypes.data, len(ps), int(min_coverage_depth),
+                float(min_coverage_breadth), float(min_allele_frequency)]
+        rc = self._lib.pg_vcf_parse_dev(*args, None, None, None, None, None, 0, 0, C.byref(info))
+        if info.err_reason:
+            raise VcfError("pg_vcf_parse_dev", info.err_line_off, info.err_reason)
+        k, n = info.kept, info.n_pools
+        if rc != 0 and k == 0:
+            self._check(rc, "pg_vcf_parse_dev")
+        counts = torch.empty(k * n * 6, dtype=torch.int32, device=dev)
+        pos = torch.empty(k, dtype=torch.int64, device=dev); ref = torch.empty(k, dtype=torch.uint8, device=dev)
+        off = torch.empty(k, dtype=torch.int64, device=dev); clen = torch.empty(k, dtype=torch.int32, device=dev)
+        if k:
+            self._check(self._lib.pg_vcf_parse_dev(*args, counts.data_ptr(), pos.data_ptr(), ref.data_ptr(), off.data_ptr(), clen.data_ptr(),
+                                                   k, counts.numel(), C.byref(info)), "pg_vcf_parse_dev")
+        return _vcf_result(info, counts, pos, ref, off, clen)
 
     # ---- imputation (src/imputation/) ------------------------------------------------------------
     def _impute_args(self, M, locus_col, n):
