@@ -67,7 +67,7 @@ int pg_synchronize(pg_ctx *ctx);
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
                     PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_CSV = 13,
-                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_COUNT = 18 };
+                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_SYNC = 18, PG_K_COUNT = 19 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
@@ -522,6 +522,49 @@ int pg_host_vcf_parse(const char *text, int64_t bytes, const double *pool_sizes,
                       double min_coverage_breadth, double min_allele_frequency, uint32_t *counts, uint64_t *pos, uint8_t *ref,
                       int64_t *line_off, int32_t *chrom_len, int64_t cap_loci, int64_t cap_counts, pg_vcf_info *info,
                       int n_threads);
+
+/* ---------------------------------------------------------------------------------------
+ * The sync reader (base/sync.rs: String::lparse :100-156, as the CLI's parse_sync_buffer restates it): a slab of sync text --
+ * it starts at a line start, its last line may lack the newline, the pointer may have any alignment -- to the counts of its
+ * loci, in file order.  expect_n: 0 = the pool count is that of the first data line of the slab, else the required count
+ * (at most 4096; more is PG_ERR_INVALID before anything is launched).
+ * The rules.  A line ends at '\n', one trailing '\r' is dropped.  A line starting with '#' is skipped.  A number is an
+ * optional '+' and 1-19 decimal digits.  A line whose second field is no number is skipped, provided it has a second tab.
+ * A pool is six or more numbers separated by ':'; the first six are stored (each at most 2^32 - 1), further ones are checked
+ * and ignored.  The FIRST line of the slab that does not start with '#' fixes the pool count (its fields minus three) and
+ * must have four fields or more and expect_n pools, even where its position is no number and the line is then skipped.
+ * Outputs, `kept` rows each:
+ *   counts    uint32, kept x n_pools x 6, the first six numbers of every pool at the positions they have in the text
+ *   pos       uint64;  line_off: the byte offset of the line in the slab;  chrom_len: the length of its first field
+ * info->kept, data_lines (lines that are not empty and do not start with '#'), n_pools (0 without such a line).
+ * Capacities as for pg_vcf_parse_dev: cap_loci rows, cap_counts elements; 0 is the size query; too small a buffer fails with
+ * PG_ERR_INVALID and writes nothing; nothing at or behind the stated capacities is written.
+ * Where the CLI's host parser throws the call fails with PG_ERR_INVALID: info->err_line_off is the FIRST such line in file
+ * order, info->err_reason the smallest pg_sync_reason that holds of it (of the pools only the first n_pools are looked at);
+ * else -1 and 0.  kept and n_pools are then 0.
+ * The device form works on the context's stream out of the context's workspace and synchronises only to read sizes; the rows
+ * are complete once the stream has passed the call.  The host form is plain C++ on n_threads threads, needs no context, and
+ * gives the same bytes.
+ * ------------------------------------------------------------------------------------- */
+enum pg_sync_reason {
+    PG_SYNC_E_EMPTY = 1,   /* an empty line (or one that is only '\r') */
+    PG_SYNC_E_FIELDS = 2,  /* fewer than four tab-separated fields */
+    PG_SYNC_E_COUNT = 3,   /* a count that is no number, or a pool with fewer than six */
+    PG_SYNC_E_COUNT32 = 4, /* one of a pool's first six counts is above 2^32 - 1 */
+    PG_SYNC_E_POOLS = 5,   /* another number of pools than the first data line's or expect_n, or more than 4096 */
+    PG_SYNC_E_LONG = 6     /* a line of 2^31 bytes or more (this library's limit) */
+};
+typedef struct {
+    int64_t kept;
+    int64_t data_lines;
+    int64_t err_line_off;
+    int32_t n_pools;
+    int32_t err_reason;
+} pg_sync_info;
+int pg_sync_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t bytes, int expect_n, uint32_t *counts_dev, uint64_t *pos_dev,
+                      int64_t *line_off_dev, int32_t *chrom_len_dev, int64_t cap_loci, int64_t cap_counts, pg_sync_info *info);
+int pg_host_sync_parse(const char *text, int64_t bytes, int expect_n, uint32_t *counts, uint64_t *pos, int64_t *line_off,
+                       int32_t *chrom_len, int64_t cap_loci, int64_t cap_counts, pg_sync_info *info, int n_threads);
 
 /* ---------------------------------------------------------------------------------------
  * impute (src/imputation/: filtering_missing.rs, mean_imputation.rs, adaptive_ld_knn_imputation.rs; CLI main.rs:125-142,

@@ -74,6 +74,8 @@ static const char *USAGE =
     "      --csv-slab-rows <N>             sync2csv, impute: rows of the table formatted on the GPU, copied and written per turn; default: as\n"
     "                                      many as hold 256 MB of text at their longest.  The file does not depend on it\n"
     "      --n-threads <1>                 parser / writer threads\n"
+    "      --sync-parser <host|gpu>        who parses a *.sync input: the host's --n-threads threads (the default), or the GPU that analyses\n"
+    "                                      it (the text goes over the link, the counts stay on the device).  The output is the same\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
     "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
     "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
@@ -130,6 +132,7 @@ Args parse_args(int argc, char **argv) {
         }
         else if (k == "--csv-slab-rows") a.csv_slab_rows = flag_int(val(), k, 1);
         else if (k == "--imputation-method") a.imputation_method = val();
+        else if (k == "--sync-parser") a.sync_parser = val();
         else if (k == "--min-depth-set-to-missing") {
             const std::string t = val();
             if (!parse_f64_strict(t, a.min_depth_set_to_missing)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
@@ -190,6 +193,10 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
         if (a.n_loci_to_estimate_distance < 1 || a.k_neighbours < 1)
             throw std::runtime_error("--n-loci-to-estimate-distance and --k-neighbours must be at least 1");
     }
+    if (a.sync_parser != "host" && a.sync_parser != "gpu")
+        throw std::runtime_error("Invalid value `" + a.sync_parser + "` for --sync-parser. Please select: 'host' or 'gpu'");
+    if (a.sync_parser == "gpu" && input_kind(a.fname) != InputKind::sync)
+        throw std::runtime_error("--sync-parser gpu applies to a *.sync input; `" + a.fname + "` is converted by its own reader");
     gwalpha_fmt = a.phen_format == "gwalpha_fmt";
     if (analysis == Analysis::gwalpha && !gwalpha_fmt)
         throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "

@@ -92,7 +92,7 @@ static void kin_load_pieces(KinRank &K, RankGate &gate, const Args &a, const Phe
         gate.pass([&] { gpu.ok(pg_comm_init_rank(gpu.c, rs.id, R, K.rank), "RCCL communicator"); });
     if (K.c0 >= K.c1) return;
     // (the pinned slots, the counts and the 16-bit scratch live to the end of this phase only)
-    PieceReader pieces(in.mf, in.cuts, K.c0, K.c1, K.device, K.threads, kind, pf, n, true);
+    PieceReader pieces(in.mf, in.cuts, K.c0, K.c1, K.device, K.threads, kind, pf, n, true, a.sync_parser == "gpu" ? SyncOnGpu::device : SyncOnGpu::no);
     std::vector<double> S_piece((size_t)n2 * n2);
     DeviceBuf<uint32_t> counts_dev;
     CountsUpload upload;
@@ -112,9 +112,13 @@ static void kin_load_pieces(KinRank &K, RankGate &gate, const Args &a, const Phe
             K.last_pos = sb.pos[l];
         }
         K.t_host += clk() - t0; t0 = clk();
-        counts_dev.reserve(sizeof(uint32_t) * (size_t)sb.L * n * 6, "device memory for the counts");
-        upload(gpu, sb, counts_dev.get());
-        LoadedMatrix piece = load_matrix(gpu, counts_dev.get(), sb.L, n, ph.pool_sizes, flt, a.keep_p_minus_1, nullptr, pool_map, n2, ld, false);
+        const uint32_t *counts = sb.counts_dev; // --sync-parser gpu: the piece's counts are on the device already
+        if (!counts) {
+            counts_dev.reserve(sizeof(uint32_t) * (size_t)sb.L * n * 6, "device memory for the counts");
+            upload(gpu, sb, counts_dev.get());
+            counts = counts_dev.get();
+        }
+        LoadedMatrix piece = load_matrix(gpu, counts, sb.L, n, ph.pool_sizes, flt, a.keep_p_minus_1, nullptr, pool_map, n2, ld, false);
         const int64_t pc = piece.p;
         if (pc == 0) continue;
         const double *G = piece.G.get();
@@ -295,7 +299,8 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
     std::vector<int64_t> totals(R, 0);
     std::vector<std::string> part(R);
     for (int r = 0; r < R; ++r) part[r] = R == 1 ? out : out + ".rank" + std::to_string(r) + ".tmp";
-    auto cleanup_parts = [&] { if (R > 1) for (auto &f : part) ::unlink(f.c_str()); };
+    std::vector<char> created(R, 0); // the part files this run made: a run that fails leaves none of them behind, one rank's output included
+    auto cleanup_parts = [&] { for (int r = 0; r < R; ++r) if (R > 1 || created[r]) ::unlink(part[r].c_str()); };
     try {
     run_ranks(R, [&](int r) {
         const int device = rs.devices[r], threads = rs.threads[r];
@@ -303,7 +308,9 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
         Ctx &gpu = *rank_ctx(r, device, gpu0, own);
         const int c0 = in.first[r], c1 = in.first[r + 1];
         if (c0 >= c1) return;
-        PieceReader pieces(in.mf, in.cuts, c0, c1, device, threads, kind, pf, 0, !subset);
+        // --sync-parser gpu: the counts stay on the device, except where pools are dropped on the host below
+        const SyncOnGpu sync_gpu = a.sync_parser != "gpu" ? SyncOnGpu::no : subset ? SyncOnGpu::host : SyncOnGpu::device;
+        PieceReader pieces(in.mf, in.cuts, c0, c1, device, threads, kind, pf, 0, !subset, sync_gpu);
         FILE *fo = nullptr;
         DeviceBuf<uint32_t> counts_dev;
         DeviceBuf<int32_t> n_out_dev, ids_dev;
@@ -322,7 +329,7 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
             totals[r] += L;
             if (L > cap_loci) {
                 cap_loci = L + L / 8;
-                counts_dev.reset(sizeof(uint32_t) * (size_t)cap_loci * n * 6, "device memory for the counts");
+                if (!sb.counts_dev) counts_dev.reset(sizeof(uint32_t) * (size_t)cap_loci * n * 6, "device memory for the counts");
                 n_out_dev.reset(sizeof(int32_t) * cap_loci);
                 ids_dev.reset(sizeof(int32_t) * cap_loci * PG_MAX_OUT);
                 mf_dev.reset(sizeof(double) * cap_loci * PG_MAX_OUT);
@@ -334,22 +341,23 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
                 for (int64_t l = 0; l < L; ++l)
                     for (int i = 0; i < n2; ++i) std::memcpy(&counts2[((size_t)l * n2 + i) * 6], &sb.counts[((size_t)l * n + keep[i]) * 6], 24);
                 hip_ok(hipMemcpy(counts_dev.get(), counts2.data(), sizeof(uint32_t) * counts2.size(), hipMemcpyHostToDevice), "H2D counts");
-            } else
+            } else if (!sb.counts_dev)
                 upload(gpu, sb, counts_dev.get());
+            const uint32_t *counts = sb.counts_dev ? sb.counts_dev : counts_dev.get();
             if (gwa) // sig, MIN, MAX: rows 0..2 of the matrix' third column (gwalpha.rs:214-216)
-                gpu.ok(pg_gwalpha_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), gw_q.data(), ph.phen[2], ph.phen[5], ph.phen[8], &flt, gw_method,
+                gpu.ok(pg_gwalpha_batch_dev(gpu.c, counts, L, n2, ps.data(), gw_q.data(), ph.phen[2], ph.phen[5], ph.phen[8], &flt, gw_method,
                                             n_out_dev.get(), ids_dev.get(), mf_dev.get(), stat_dev.get(), nullptr, nullptr, nullptr), "gwalpha");
             else if (op == Analysis::fisher_exact_test)
-                gpu.ok(pg_fisher_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, n_out_dev.get(), ids_dev.get(), stat_dev.get(), pv_dev.get()),
+                gpu.ok(pg_fisher_batch_dev(gpu.c, counts, L, n2, ps.data(), &flt, n_out_dev.get(), ids_dev.get(), stat_dev.get(), pv_dev.get()),
                        "fisher_exact_test");
             else if (op == Analysis::chisq_test)
-                gpu.ok(pg_chisq_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, n_out_dev.get(), ids_dev.get(), stat_dev.get(), pv_dev.get()),
+                gpu.ok(pg_chisq_batch_dev(gpu.c, counts, L, n2, ps.data(), &flt, n_out_dev.get(), ids_dev.get(), stat_dev.get(), pv_dev.get()),
                        "chisq_test");
             else if (op == Analysis::pearson_corr)
-                gpu.ok(pg_pearson_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, Y.data(), k, n_out_dev.get(), ids_dev.get(), mf_dev.get(),
+                gpu.ok(pg_pearson_batch_dev(gpu.c, counts, L, n2, ps.data(), &flt, Y.data(), k, n_out_dev.get(), ids_dev.get(), mf_dev.get(),
                                             stat_dev.get(), pv_dev.get()), "pearson_corr");
             else
-                gpu.ok(pg_ols_iter_batch_dev(gpu.c, counts_dev.get(), L, n2, ps.data(), &flt, Y.data(), k, n_out_dev.get(), ids_dev.get(), mf_dev.get(),
+                gpu.ok(pg_ols_iter_batch_dev(gpu.c, counts, L, n2, ps.data(), &flt, Y.data(), k, n_out_dev.get(), ids_dev.get(), mf_dev.get(),
                                              stat_dev.get(), pv_dev.get()), "ols_iter");
             n_out.resize(L); ids.resize((size_t)L * PG_MAX_OUT); mfq.resize((size_t)L * PG_MAX_OUT);
             stat.resize((size_t)L * per_stat); pv.resize((size_t)L * per_stat);
@@ -365,6 +373,7 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
             if (!gwa) hip_ok(hipMemcpy(pv.data(), pv_dev.get(), sizeof(double) * L * per_stat_used, hipMemcpyDeviceToHost), "D2H results");
             if (!fo) {
                 fo = create_new(part[r]);
+                created[r] = 1;
                 if (R == 1) fputs(header, fo);
             }
             write_rows_parallel(fo, L, threads, [&](int64_t l, std::string &line) {
@@ -378,7 +387,7 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
     } catch (...) { cleanup_parts(); throw; }
     int64_t total = 0;
     for (int64_t t : totals) total += t;
-    if (total == 0) { cleanup_parts(); throw std::runtime_error("no loci in " + a.fname); }
+    if (total == 0) { cleanup_parts(); throw std::runtime_error("no loci in " + a.fname); } // (no part was made)
     if (R > 1) { // header + the ranks' parts in rank order = file order
         FILE *fo = create_new(out);
         fputs(header, fo);

@@ -247,7 +247,8 @@ SyncBatch &SyncBatch::operator=(SyncBatch &&o) noexcept {
         n = o.n; L = o.L;
         chrom_id = std::move(o.chrom_id); chrom_names = std::move(o.chrom_names); pos = std::move(o.pos);
         counts = o.counts; counts16 = o.counts16; release = std::move(o.release);
-        o.counts = nullptr; o.counts16 = nullptr; o.L = 0;
+        counts_dev = o.counts_dev;
+        o.counts = nullptr; o.counts16 = nullptr; o.counts_dev = nullptr; o.L = 0;
     }
     return *this;
 }

@@ -54,6 +54,8 @@ struct SyncBatch {
     uint32_t *counts = nullptr;             // L x n x 6, the device layout ...
     uint16_t *counts16 = nullptr;           // ... or, when asked for and every count fits, 16-bit (half the bytes to pin and to copy)
     std::function<void(void *)> release;   // empty = free()
+    const uint32_t *counts_dev = nullptr;   // optional: the counts are on the device instead (32-bit, owned by the reader that
+                                            // parsed them there: --sync-parser gpu); counts and counts16 are then null
     int64_t size() const { return L; }
     const std::string &chrom(int64_t l) const { return chrom_names[chrom_id[l]]; }
     size_t counts_bytes() const { return (counts16 ? sizeof(uint16_t) : sizeof(uint32_t)) * (size_t)L * n * 6; }

@@ -5,6 +5,7 @@
 // :972-1180; gwas/ols.rs:255-275, :372-433); anything else the reference CLI offers is out of scope and reported as such.
 #include "cli.h"
 #include "gp_cv.h"
+#include "sync_reader.h"
 #include "vcf.h"
 #include <cstring>
 
@@ -75,6 +76,9 @@ static int run(int argc, char **argv) {
     } else if (kind == InputKind::vcf) {
         sb = parse_vcf_file(ranks.devices[0], a.fname, a.n_threads, pf, pinned);
         lap("vcf -> counts");
+    } else if (a.sync_parser == "gpu") { // the text parsed on the GPU, the counts copied back: the batch below, 32-bit
+        sb = parse_sync_file_gpu(ranks.devices[0], a.fname, a.n_threads, pinned);
+        lap("parse sync (gpu)");
     } else {
         // the analyses on the loaded matrix copy the counts themselves: 16-bit counts when they fit
         sb = parse_sync_file(a.fname, a.n_threads, pinned, /*compact16=*/true);

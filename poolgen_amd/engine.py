@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._native import KERNEL_IDS, NativeError, PgFilter, PgVcfInfo, load_library
+from ._native import KERNEL_IDS, NativeError, PgFilter, PgSyncInfo, PgVcfInfo, load_library
 
 ALLELES = "ATCGND"  # base/sync.rs:134 reader order
 
@@ -142,6 +142,47 @@ def vcf_parse_host(text, pool_sizes, min_coverage_depth=1, min_coverage_breadth=
         if rc != 0:
             raise NativeError(f"pg_host_vcf_parse failed ({rc})")
     return _vcf_result(info, counts, pos, ref, off, clen)
+
+
+SYNC_REASONS = {1: "empty line", 2: "fewer than four tab-separated fields", 3: "a count is no valid integer, or a pool has fewer than six",
+                4: "count above 2^32 - 1", 5: "number of pools", 6: "line of 2^31 bytes or more"}
+
+
+class SyncError(NativeError):
+    """A sync line at which the CLI's host parser throws: `offset` is the byte offset of the first such line of the text,
+    `reason` a pg_sync_reason."""
+
+    def __init__(self, what, offset, reason):
+        super().__init__(f"{what}: the line at byte {offset} of the text: {SYNC_REASONS.get(reason, reason)}")
+        self.offset, self.reason = int(offset), int(reason)
+
+
+def _sync_result(info, counts, pos, off, clen):
+    k, n = info.kept, info.n_pools
+    return {"counts": counts[:k * n * 6].reshape(k, n, 6), "pos": pos[:k], "line_off": off[:k], "chrom_len": clen[:k],
+            "data_lines": int(info.data_lines), "n_pools": int(n)}
+
+
+def sync_parse_host(text, expect_n=0, n_threads=1):
+    """Engine.sync_parse on the host (pg_host_sync_parse: plain C++, no GPU): the same dictionary, of numpy arrays."""
+    lib = load_library()
+    t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+    info = PgSyncInfo()
+    args = [t.ctypes.data if t.size else None, t.size, int(expect_n)]
+    rc = lib.pg_host_sync_parse(*args, None, None, None, None, 0, 0, C.byref(info), int(n_threads))
+    if info.err_reason:
+        raise SyncError("pg_host_sync_parse", info.err_line_off, info.err_reason)
+    k, n = info.kept, info.n_pools
+    if rc != 0 and k == 0:
+        raise NativeError(f"pg_host_sync_parse failed ({rc}): bad arguments")
+    counts = np.empty(k * n * 6, dtype=np.uint32); pos = np.empty(k, dtype=np.uint64)
+    off = np.empty(k, dtype=np.int64); clen = np.empty(k, dtype=np.int32)
+    if k:
+        rc = lib.pg_host_sync_parse(*args, counts.ctypes.data, pos.ctypes.data, off.ctypes.data, clen.ctypes.data, k, counts.size,
+                                    C.byref(info), int(n_threads))
+        if rc != 0:
+            raise NativeError(f"pg_host_sync_parse failed ({rc})")
+    return _sync_result(info, counts, pos, off, clen)
 
 
 class Engine:
@@ -581,6 +622,36 @@ class Engine:
             self._check(self._lib.pg_vcf_parse_dev(*args, counts.data_ptr(), pos.data_ptr(), ref.data_ptr(), off.data_ptr(), clen.data_ptr(),
                                                    k, counts.numel(), C.byref(info)), "pg_vcf_parse_dev")
         return _vcf_result(info, counts, pos, ref, off, clen)
+
+    def sync_parse(self, text, expect_n: int = 0):
+        """A slab of sync text -- bytes, a NumPy uint8 array or a torch uint8 tensor (on the device it is parsed in place); it starts
+        at a line start, its last line may lack the newline -- to the counts of its loci, parsed on the GPU.  expect_n: the pool
+        count every line must have (0: that of the first data line).  A dictionary: counts (kept x n_pools x 6, the uint32 bits as
+        int32, as the loader takes them), pos (the uint64 bits as int64), line_off (int64), chrom_len (int32) as tensors on the
+        device, and the integers data_lines, n_pools.  A line at which the CLI's host parser throws raises SyncError."""
+        dev = torch.device("cuda", self.device)
+        if isinstance(text, torch.Tensor):
+            t = text.to(dev)
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError("sync_parse: text must be a contiguous uint8 tensor")
+        else:
+            a = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+            t = torch.from_numpy(a.copy()).to(dev)
+        info = PgSyncInfo()
+        args = [self._ctx, t.data_ptr() if t.numel() else None, t.numel(), int(expect_n)]
+        rc = self._lib.pg_sync_parse_dev(*args, None, None, None, None, 0, 0, C.byref(info))
+        if info.err_reason:
+            raise SyncError("pg_sync_parse_dev", info.err_line_off, info.err_reason)
+        k, n = info.kept, info.n_pools
+        if rc != 0 and k == 0:
+            self._check(rc, "pg_sync_parse_dev")
+        counts = torch.empty(k * n * 6, dtype=torch.int32, device=dev)
+        pos = torch.empty(k, dtype=torch.int64, device=dev)
+        off = torch.empty(k, dtype=torch.int64, device=dev); clen = torch.empty(k, dtype=torch.int32, device=dev)
+        if k:
+            self._check(self._lib.pg_sync_parse_dev(*args, counts.data_ptr(), pos.data_ptr(), off.data_ptr(), clen.data_ptr(), k, counts.numel(),
+                                                    C.byref(info)), "pg_sync_parse_dev")
+        return _sync_result(info, counts, pos, off, clen)
 
     # ---- imputation (src/imputation/) ------------------------------------------------------------
     def _impute_args(self, M, locus_col, n):
