@@ -94,7 +94,21 @@ int pg_locus_op_stats(const pg_ctx *ctx, int64_t *loci, int64_t *listed);
  * default -x 0.75 on uncentred allele-frequency kinships, where lambda_1 carries ~98 % of the trace),
  * pg_ols_sweep_dev closes the fits from those sums instead of reading G a second time; for m > 0 the
  * sums are ignored and the regular sweep runs.  Results are the same either way (same formula,
- * different summation order).  pg_set_phenotypes(ctx, 0, NULL, 0) switches the behaviour off. */
+ * different summation order).  pg_set_phenotypes(ctx, 0, NULL, 0) switches the behaviour off.
+ * What the sums stand for, and for how long:
+ *   - they belong to the pointer and shape (G_dev, p, n, ld) of the LAST kinship pass and to the phenotypes announced here;
+ *   - the matrix must be unchanged from that pass until the sweep.  The library drops the sums when one of its own calls
+ *     writes into that matrix (pg_load_emit_dev, pg_load_emit_cov_dev, pg_impute_mean_dev, pg_set_missing_by_depth_dev,
+ *     pg_impute_compact_dev, pg_impute_aldknn_dev); it cannot see the caller's own writes, nor a matrix that was freed and
+ *     another allocated at the same address;
+ *   - ONE pg_ols_sweep_dev uses them: the next call of the sweep after the kinship pass leaves them invalid, whatever its
+ *     arguments and also when it fails a check, and a second sweep reads G again.  The sweep that pg_gp_proxy_dev (and
+ *     pg_gp_penalised_dev with iterative_proxy) runs inside counts as that call.
+ *   - pg_ols_kinship_dev / pg_ols_kinship_sharded_dev announce their Y themselves, for the length of the call: the sums they
+ *     make are invalid when the call returns, and the call opts nobody in -- a later pg_kinship_partial_dev fuses only if
+ *     the caller announced phenotypes himself.  An announcement of the caller's stays in force across such a call when it
+ *     was for the same phenotypes; when the call replaced it with other phenotypes it is over, and the two-pass path runs
+ *     until the caller announces again. */
 int pg_set_phenotypes(pg_ctx *ctx, int n, const double *Y, int k);
 /* S_dev: n x n fp64, row-major, full symmetric sum_l g_l g_l^T over this call's p columns. */
 int pg_kinship_partial_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld,
@@ -328,7 +342,9 @@ int pg_gp_ridge_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t 
  *                                          picked by the norms of pg_gp_proxy_dev's coefficients (fitted once on
  *                                          row_idx, :543, :656), the amounts by the fit's own norms (:262-283).
  * alphas_out[k] (host, optional), lambdas_out[k]; perf_out (optional) n_reps x n_folds x A x L x k, A = 1 or L.
- * With iterative_proxy the covariate state of ctx (pg_covariates_set / pg_kinship_set) is overwritten.
+ * The covariate state of ctx (pg_covariates_set / pg_kinship_set) is gone afterwards, with or without iterative_proxy:
+ * pg_ols_sweep_dev fails with PG_ERR_STATE until it is set again (the same holds after pg_gp_ols_dev, pg_gp_ridge_dev and
+ * pg_mle_kinship_dev, whose coefficient passes use the same device table).
  * XXt_host_or_null: the full-data X X^T of pg_gp_xxt_dev (host, n x n) when the caller already has it -- a harness that
  * fits many models on the same genotypes computes it once. */
 int pg_gp_penalised_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y,
@@ -338,7 +354,8 @@ int pg_gp_penalised_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int6
 /* gp::ols_iterative_with_kinship_pca_covariate (gp/ols.rs:104-199): proxy_dev (1+p) x k on the device, row 0 = the
  * trait means over the training pools, row 1+l = the locus coefficient of y ~ [1 | PC1 | g_l] on the training pools
  * (PC1: leading eigenvector of the reference's centred X X^T of those pools, :115-141, with its two indexing quirks:
- * columns = intercept and all loci but the last; means over the first n_rows pools).  Overwrites ctx's covariates. */
+ * columns = intercept and all loci but the last; means over the first n_rows pools).  Overwrites ctx's covariates and leaves
+ * none: pg_ols_sweep_dev fails with PG_ERR_STATE until pg_covariates_set / pg_kinship_set is called again. */
 int pg_gp_proxy_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y, int k,
                     const int64_t *row_idx, int n_rows, const double *XXt_host_or_null, double *proxy_dev);
 /* yhat (n x k, host) = X beta for EVERY pool, X = [1 | G^T], beta (1+p) x k on the device: the prediction step of

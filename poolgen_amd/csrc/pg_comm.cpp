@@ -126,10 +126,9 @@ extern "C" int pg_allreduce_sum_dev(pg_ctx *ctx, double *buf_dev, int64_t count)
 
 // The sharded ols_iter_with_kinship of one rank: this rank's contiguous slab of loci in, this rank's
 // slab of results out.  p_total = the number of columns over ALL ranks (the reference divides by it, gwas/ols.rs:295).
-extern "C" int pg_ols_kinship_sharded_dev(pg_ctx *ctx, const double *G_dev, int64_t p_local, int64_t p_total, int n, int64_t ld,
-                                          const double *Y, int k, double var_explained, int force_m, int *m_out, double *K_out,
-                                          double *beta_dev, double *var_dev, double *pval_dev) {
-    if (!ctx) return PG_ERR_INVALID;
+static int ols_kinship_sharded_dev(pg_ctx *ctx, PhScope &ph, const double *G_dev, int64_t p_local, int64_t p_total, int n, int64_t ld,
+                                   const double *Y, int k, double var_explained, int force_m, int *m_out, double *K_out,
+                                   double *beta_dev, double *var_dev, double *pval_dev) {
     PG_CHECK(ctx, p_total >= p_local && p_local > 0, "ols_kinship_sharded: p_total (%lld) < p_local (%lld)", (long long)p_total,
              (long long)p_local);
     // Without a communicator the all-reduce below is the identity: a slab that is not the whole matrix would silently give
@@ -140,7 +139,7 @@ extern "C" int pg_ols_kinship_sharded_dev(pg_ctx *ctx, const double *G_dev, int6
     PG_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "ols_kinship_sharded");
     if (rc) return rc;
-    rc = pg_set_phenotypes(ctx, force_m > 0 ? 0 : n, force_m > 0 ? nullptr : Y, force_m > 0 ? 0 : k);
+    rc = ph.announce(force_m > 0 ? 0 : n, force_m > 0 ? nullptr : Y, force_m > 0 ? 0 : k);
     if (rc) return rc;
     rc = pg_kinship_partial_dev(ctx, G_dev, p_local, n, ld, ctx->S_dev);
     if (rc) return rc;
@@ -149,4 +148,13 @@ extern "C" int pg_ols_kinship_sharded_dev(pg_ctx *ctx, const double *G_dev, int6
     rc = pg_kinship_set(ctx, ctx->S_dev, p_total, n, Y, k, var_explained, force_m, m_out, K_out, nullptr);
     if (rc) return rc;
     return pg_ols_sweep_dev(ctx, G_dev, p_local, n, ld, beta_dev, var_dev, pval_dev);
+}
+
+extern "C" int pg_ols_kinship_sharded_dev(pg_ctx *ctx, const double *G_dev, int64_t p_local, int64_t p_total, int n, int64_t ld,
+                                          const double *Y, int k, double var_explained, int force_m, int *m_out, double *K_out,
+                                          double *beta_dev, double *var_dev, double *pval_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    PhScope ph(ctx); // the announcement and the fused sums of this call end with it
+    return ols_kinship_sharded_dev(ctx, ph, G_dev, p_local, p_total, n, ld, Y, k, var_explained, force_m, m_out, K_out, beta_dev,
+                                   var_dev, pval_dev);
 }

@@ -55,6 +55,7 @@ public:
         bytes_ = 0;
     }
     T *get() const { return p_; }
+    size_t bytes() const { return bytes_; } // the capacity: it changes exactly when reserve() replaced the block, whose contents are then gone
     operator T *() const { return p_; } // the context's buffers are read as the plain pointers they replace
 };
 
@@ -82,6 +83,8 @@ struct pg_ctx {
     // speculative intercept-only sums produced by the kinship pass (see pg_set_phenotypes)
     std::vector<double> ph_Y;    // n x k row-major copy of the phenotypes announced up front
     int ph_n = 0, ph_k = 0;
+    bool ph_armed = false;       // the announcement is in force: the caller's own pg_set_phenotypes, or a composed call while it runs
+    int64_t ph_serial = 0;       // counts the announcements that replaced ph_Y (a composed call sees whether it replaced the caller's)
     DevBuf<double> ph_ytil_dev; // k x 256 centred phenotypes, zero padded
     double ph_syy[4] = {0, 0, 0, 0};
     DevBuf<double> spec_dev;  // p x (2 + k): sum g', sum g'^2, sum g' ytil_t   (g' = g - g[0])
@@ -110,6 +113,15 @@ struct pg_ctx {
     int comm_size = 1, comm_rank = 0;
 };
 
+// The fused sums describe the p x ld doubles at spec_G as the kinship pass read them: a library call that is about to write
+// `bytes` at `dst` drops them when the two ranges overlap (a null dst or 0 bytes writes nothing).
+inline void pg_spec_written(pg_ctx *ctx, const void *dst, size_t bytes) {
+    if (!ctx->spec_valid || !dst || !bytes) return;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(dst), b = reinterpret_cast<uintptr_t>(ctx->spec_G);
+    const uintptr_t bl = (uintptr_t)ctx->spec_p * (uintptr_t)ctx->spec_ld * sizeof(double);
+    if (a < b + bl && b < a + bytes) ctx->spec_valid = false;
+}
+
 #define PG_HIP(ctx, call)                                                                     \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
@@ -131,6 +143,26 @@ enum pg_switch_id {
     PG_SW_COUNT
 };
 const char *pg_switch(pg_switch_id id);
+
+// pg_set_phenotypes without the opt-in: the centred phenotypes on the device (ph_*), ph_armed untouched (pg_kinship.hip).  The
+// composed calls announce through PhScope, so that their announcement ends with them: a caller who never called
+// pg_set_phenotypes is not opted in afterwards, and one who did stays opted in only if his phenotypes were not replaced.
+int pg_phenotypes_upload(pg_ctx *ctx, int n, const double *Y, int k);
+struct PhScope {
+    pg_ctx *ctx;
+    bool armed;
+    int64_t serial;
+    explicit PhScope(pg_ctx *c) : ctx(c), armed(c->ph_armed), serial(c->ph_serial) {}
+    int announce(int n, const double *Y, int k) {
+        const int rc = pg_phenotypes_upload(ctx, n, Y, k);
+        ctx->ph_armed = rc == PG_OK && ctx->ph_n > 0;
+        return rc;
+    }
+    ~PhScope() {
+        ctx->ph_armed = armed && ctx->ph_serial == serial;
+        ctx->spec_valid = false; // the fused sums of a composed call are its own sweep's: gone on every return, a failed one included
+    }
+};
 
 int pg_ws_reserve(pg_ctx *ctx, size_t bytes);
 int pg_pin_reserve(pg_ctx *ctx, size_t bytes);

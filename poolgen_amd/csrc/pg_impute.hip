@@ -497,6 +497,8 @@ extern "C" int pg_set_missing_by_depth_dev(pg_ctx *ctx, double *G_dev, double *c
     if (rc) return rc;
     PG_CHECK(ctx, cov_dev, "set_missing_by_depth: null argument");
     PG_HIP(ctx, hipSetDevice(ctx->device));
+    pg_spec_written(ctx, G_dev, sizeof(double) * (size_t)p * ld);
+    pg_spec_written(ctx, cov_dev, sizeof(double) * (size_t)p * ld);
     DevBuf<int64_t> lc;
     if ((rc = upload(ctx, lc, locus_col, (size_t)L + 1, "set_missing_by_depth"))) return rc;
     pg_prof_begin(ctx, PG_K_IMPUTE);
@@ -582,6 +584,8 @@ extern "C" int pg_impute_compact_dev(pg_ctx *ctx, const double *G_dev, const dou
     if ((rc = upload(ctx, rows_dev, rows.data(), rows.size(), "impute_compact"))) return rc;
     if ((rc = upload(ctx, pools_dev, pools.data(), pools.size(), "impute_compact"))) return rc;
     const int64_t p_out = (int64_t)rows.size();
+    pg_spec_written(ctx, G_out_dev, sizeof(double) * (size_t)p_out * ld_out);
+    pg_spec_written(ctx, cov_out_dev, sizeof(double) * (size_t)p_out * ld_out);
     pg_prof_begin(ctx, PG_K_IMPUTE);
     hipLaunchKernelGGL(k_compact, dim3(blocks_of((size_t)p_out * ld_out, 256)), dim3(256), 0, ctx->stream, G_dev, cov_dev, ld, col_locus_dev,
                        col_allele_dev, rows_dev.get(), p_out, pools_dev.get(), n_keep, ld_out, G_out_dev, cov_out_dev, col_locus_out_dev,
@@ -615,6 +619,7 @@ extern "C" int pg_impute_mean_dev(pg_ctx *ctx, double *G_dev, int64_t p, int n, 
     }
     PG_CHECK(ctx, max_alleles <= 1024, "impute_mean: a locus with %lld allele columns (at most 1024)", (long long)max_alleles);
     PG_HIP(ctx, hipSetDevice(ctx->device));
+    pg_spec_written(ctx, G_dev, sizeof(double) * (size_t)p * ld);
     DevBuf<int64_t> lc, list, wide_dev;
     if ((rc = upload(ctx, lc, locus_col, (size_t)L + 1, "impute_mean"))) return rc;
     pg_prof_begin(ctx, PG_K_IMPUTE);
@@ -669,6 +674,7 @@ extern "C" int pg_impute_aldknn_dev(pg_ctx *ctx, const double *G_dev, int64_t p,
     const int k_links = (int)n_loci_to_estimate_distance;
     const size_t budget = scratch_bytes > 0 ? (size_t)scratch_bytes : (size_t)1 << 30;
     PG_HIP(ctx, hipSetDevice(ctx->device));
+    pg_spec_written(ctx, G_out_dev, sizeof(double) * (size_t)p * ld);
     PG_HIP(ctx, hipMemcpyAsync(G_out_dev, G_dev, sizeof(double) * (size_t)p * ld, hipMemcpyDeviceToDevice, ctx->stream));
     if (n_windows == 0) return PG_OK;
 

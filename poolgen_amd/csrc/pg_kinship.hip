@@ -795,7 +795,7 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     if ((ldsld & 31) != 16) ldsld += 16;
     // fused speculative intercept-only sums: only in the single-block path and with phenotypes announced
     const size_t fuse_lds = (size_t)2 * KIN_KC * ldsld * 8 + ((size_t)KIN_FUSE_MAXK * 256 + (size_t)KIN_WAVES * 4 * 64) * 8;
-    const bool fuse = allow_fuse && fuse_lds <= 160 * 1024 && P.nb == 1 && ctx->ph_n == n && ctx->ph_k >= 1 && ctx->ph_k <= KIN_FUSE_MAXK &&
+    const bool fuse = allow_fuse && ctx->ph_armed && fuse_lds <= 160 * 1024 && P.nb == 1 && ctx->ph_n == n && ctx->ph_k >= 1 && ctx->ph_k <= KIN_FUSE_MAXK &&
                       ctx->ph_ytil_dev != nullptr;
     P.ytil = nullptr; P.spec = nullptr; P.k = 0;
     ctx->spec_valid = false;
@@ -835,11 +835,11 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     le = fuse ? pick(std::true_type{}) : pick(std::false_type{});
     PG_HIP(ctx, le);
     pg_prof_end(ctx);
-    if (fuse) {
+    PG_HIP(ctx, hipGetLastError());
+    if (fuse) { // (behind the check: a launch the device refused leaves no sums)
         ctx->spec_G = G; ctx->spec_p = p; ctx->spec_ld = ld; ctx->spec_n = n; ctx->spec_k = ctx->ph_k;
         ctx->spec_valid = true;
     }
-    PG_HIP(ctx, hipGetLastError());
     pg_prof_begin(ctx, PG_K_KINSHIP_REDUCE);
     hipLaunchKernelGGL(k_kinship_reduce, dim3((n + 63) / 64, n), dim3(256), 0, ctx->stream,
                        P.slabs, nslab, P.npad, n, add_intercept ? 1.0 : 0.0, S, KC);
@@ -864,10 +864,17 @@ extern "C" int pg_gp_xxt_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n,
 
 extern "C" int pg_set_phenotypes(pg_ctx *ctx, int n, const double *Y, int k) {
     if (!ctx) return PG_ERR_INVALID;
+    const int rc = pg_phenotypes_upload(ctx, n, Y, k);
+    ctx->ph_armed = rc == PG_OK && ctx->ph_n > 0; // the caller's own opt-in (or its end)
+    return rc;
+}
+
+int pg_phenotypes_upload(pg_ctx *ctx, int n, const double *Y, int k) {
     ctx->spec_valid = false;
     if (n > 0 && Y && ctx->ph_n == n && ctx->ph_k == k && ctx->ph_ytil_dev && ctx->ph_Y.size() == (size_t)n * k &&
         std::memcmp(ctx->ph_Y.data(), Y, sizeof(double) * n * k) == 0)
         return PG_OK; // same phenotypes as last time: the centred copy is already on the device
+    if (ctx->ph_n > 0) ++ctx->ph_serial; // an announcement goes
     ctx->ph_n = 0; ctx->ph_k = 0; ctx->ph_Y.clear();
     if (n == 0 || !Y) return PG_OK; // switched off
     PG_CHECK(ctx, n >= 2 && k >= 1, "set_phenotypes: bad shape n=%d k=%d", n, k);

@@ -2935,6 +2935,8 @@ int load_emit(pg_ctx *ctx, const int32_t *pool_map, int n_out, double *G_dev, in
         for (int i = 0; i < n; ++i) PG_CHECK(ctx, pool_map[i] >= -1 && pool_map[i] < n_out, "load_emit: pool_map[%d] out of range", i);
     if (ctx->load_total == 0) return PG_OK;
     PG_HIP(ctx, hipSetDevice(ctx->device));
+    pg_spec_written(ctx, G_dev, sizeof(double) * (size_t)ctx->load_total * ld);
+    pg_spec_written(ctx, cov_dev, sizeof(double) * (size_t)ctx->load_total * ld);
     char *ws = static_cast<char *>(ctx->ws.get());
     int32_t *pmap_dev = nullptr;
     if (pool_map) {

@@ -1262,6 +1262,11 @@ extern "C" int pg_kinship_set(pg_ctx *ctx, const double *S_dev, int64_t p_total,
 extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld,
                                 double *beta_dev, double *var_dev, double *pval_dev) {
     if (!ctx) return PG_ERR_INVALID;
+    // One call of the sweep consumes the fused sums, whether or not it is the one they were made for and whether or not it gets past
+    // its checks: the library cannot see a caller's own writes to G, so it vouches for the sums only from the kinship pass to the
+    // next sweep (include/poolgen_hip.h, pg_set_phenotypes).
+    const bool sums = ctx->spec_valid;
+    ctx->spec_valid = false;
     if (ctx->st_m < 0 || ctx->st_n != n)
         return pg_fail(ctx, PG_ERR_STATE, "sweep: call pg_kinship_set / pg_covariates_set for n=%d first", n);
     PG_CHECK(ctx, G_dev && beta_dev && var_dev && pval_dev, "sweep: null pointer");
@@ -1286,8 +1291,9 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
     P.D.ntiles = (nsr + 63) / 64;
     P.D.m1 = ctx->st_m + 1; P.D.k = ctx->st_k;
     P.D.dfe = (double)n - (double)(ctx->st_m + 2);
-    if (ctx->st_m == 0 && ctx->spec_valid && ctx->spec_G == G_dev && ctx->spec_p == p && ctx->spec_n == n &&
-        ctx->spec_ld == ld && ctx->spec_k == ctx->st_k && ctx->ph_n == n && ctx->st_Y_matches_ph) {
+    const bool fused = ctx->st_m == 0 && sums && ctx->spec_G == G_dev && ctx->spec_p == p && ctx->spec_n == n &&
+                       ctx->spec_ld == ld && ctx->spec_k == ctx->st_k && ctx->ph_n == n && ctx->st_Y_matches_ph;
+    if (fused) {
         // m = 0: the kinship pass already formed the sums of the intercept-only fits from its read of G
         pg_prof_begin(ctx, PG_K_SWEEP_FINISH);
         if (ctx->st_k == 1) {
@@ -1315,11 +1321,9 @@ extern "C" int pg_ols_sweep_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
     return with_cols(ctx, ctx->st_cols, [&](auto c) { return launch_sweep<decltype(c)::value>(ctx, P, grid); });
 }
 
-extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld,
-                                  const double *Y, int k, double var_explained, int force_m,
-                                  int *m_out, double *K_out, double *beta_dev, double *var_dev,
-                                  double *pval_dev) {
-    if (!ctx) return PG_ERR_INVALID;
+static int ols_kinship_dev(pg_ctx *ctx, PhScope &ph, const double *G_dev, int64_t p, int n, int64_t ld, const double *Y, int k,
+                           double var_explained, int force_m, int *m_out, double *K_out, double *beta_dev, double *var_dev,
+                           double *pval_dev) {
     PG_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     // ---- the lazy route: a caller that does not want K may not need it formed at all ----------------------------------------------
@@ -1364,13 +1368,22 @@ extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, i
     rc = ctx->S_dev.reserve(ctx, sizeof(double) * n * n, "ols_kinship");
     if (rc) return rc;
     double *S_dev = ctx->S_dev;
-    rc = pg_set_phenotypes(ctx, n, Y, k);
+    rc = ph.announce(n, Y, k);
     if (rc) return rc;
     rc = pg_launch_kinship(ctx, G_dev, p, n, ld, S_dev, false, PG_K_KINSHIP, true);
     if (rc) return rc;
     rc = pg_kinship_set(ctx, S_dev, p, n, Y, k, var_explained, force_m, m_out, K_out, nullptr);
     if (rc) return rc;
     return pg_ols_sweep_dev(ctx, G_dev, p, n, ld, beta_dev, var_dev, pval_dev);
+}
+
+extern "C" int pg_ols_kinship_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld,
+                                  const double *Y, int k, double var_explained, int force_m,
+                                  int *m_out, double *K_out, double *beta_dev, double *var_dev,
+                                  double *pval_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    PhScope ph(ctx); // the announcement and the fused sums of this call end with it
+    return ols_kinship_dev(ctx, ph, G_dev, p, n, ld, Y, k, var_explained, force_m, m_out, K_out, beta_dev, var_dev, pval_dev);
 }
 
 namespace {
@@ -1637,6 +1650,9 @@ extern "C" int pg_gp_proxy_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int 
                            rows_dev.get(), nr, ld2, Gs_own.get());
     rc = pg_covariates_set(ctx, nr, ev.data(), 1, Ys.data(), k);
     if (!rc) rc = pg_ols_sweep_dev(ctx, Gs, p, nr, ld2, proxy_dev + k, scratch.get(), scratch.get());
+    // [1 | PC1] of the training pools is this call's own design, not one the caller set: no later sweep may fit against it
+    ctx->st_m = -1;
+    ctx->st_Y.clear();
     if (rc) return rc;
     // y ~ a0 + b0 PC1 for the constant loci
     ProxyFix F{};

@@ -375,11 +375,11 @@ extern "C" int pg_sync_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t byte
     const size_t o_local = off; off = up16(off + 4 * (size_t)lines);
     const size_t o_bsk = off; off = up16(off + 8 * (size_t)nbk);
     const size_t o_bok = off; off = up16(off + 8 * (size_t)nbk);
-    const void *before = ctx->ws.get();
+    const size_t before = ctx->ws.bytes();
     rc = pg_ws_reserve(ctx, off);
     if (rc) return rc;
     pg_prof_begin(ctx, PG_K_SYNC | PG_PROF_CONT);
-    if (ctx->ws.get() != before) PG_HIP(ctx, count_lines()); // the workspace grew and moved: its front part again (the same numbers)
+    if (ctx->ws.bytes() != before) PG_HIP(ctx, count_lines()); // the workspace was replaced by a larger block (wherever that one lies): its front part again (the same numbers)
     char *ws = static_cast<char *>(ctx->ws.get());
     SyncCtl *ctl = reinterpret_cast<SyncCtl *>(ws + o_ctl);
     int64_t *start = reinterpret_cast<int64_t *>(ws + o_start), *bsk = reinterpret_cast<int64_t *>(ws + o_bsk), *bok = reinterpret_cast<int64_t *>(ws + o_bok);
