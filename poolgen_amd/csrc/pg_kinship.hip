@@ -40,6 +40,7 @@ constexpr int KIN_PPT = (KIN_KC * 128 + KIN_THREADS - 1) / KIN_THREADS;  // 16-b
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int uint4_t __attribute__((ext_vector_type(4)));
+typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
 
 // v + (v shifted by a DPP control) on the VALU only: the generic __shfl_xor goes through ds_bpermute,
 // whose latency would stall the issuing wave in the middle of the MFMA stream.
@@ -166,7 +167,9 @@ struct KinParams {
 // only the 8-pool strip needs reads of its own.  200 pools: 5 200 instead of 5 824 matrix cycles per 4 loci.
 // SKIP (run-time tile tables only): see KinParams::skip_dead -- a template parameter because even a never-taken branch around an
 // item keeps the compiler from running the fragment reads ahead of the MFMAs (measured: +8..10 % at 224 and 500 pools).
-template <bool FUSE, bool SPEC13, int SMALL = 0, bool SKIP = false> // SMALL bits: 1 = diagonal tiles on 4 x 4 blocks, 2 = 8-pool last column (n <= 200) on 4 x 4 blocks
+// ODDN (13-tile shape only): the pool count may be odd, so the staging zeroes the second half of a row's last piece; the instance
+// for even pool counts carries no such select in its stage loop.
+template <bool FUSE, bool SPEC13, int SMALL = 0, bool SKIP = false, bool ODDN = true> // SMALL bits: 1 = diagonal tiles on 4 x 4 blocks, 2 = 8-pool last column (n <= 200) on 4 x 4 blocks
 __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
@@ -398,7 +401,7 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
     // round trip of the next stage hide behind them.
     // W >= 0 (SPEC13 kernels: one block of 13 tiles, 193..208 pools, LDS pitch 208): the body is
     // instantiated once per wave with COMPILE-TIME tile coordinates, so every fragment address is
-    // "lane base + immediate" (no per-item address arithmetic, A/B pairs merge into ds_read2_b64).
+    // "lane base + immediate" (no per-item address arithmetic; the buffer parity is compile-time as well, see below).
     // W = -1: run-time tile tables, any shape.
     // TPW = tile slots per wave actually run (2..6): a work-group with few tiles (small n, or a
     // diagonal block pair) would otherwise spend most of its matrix-core time on dead slots.
@@ -422,36 +425,45 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
             // operands are already in registers, and the first reads of the next stage hide behind them.
             constexpr int NC = kin13_ncols(W), NT = kin13_ntiles(W);
             static_assert(NC <= KIN13_MAXC && KS % 2 == 0, "fragment sets alternate with the k-step parity");
+            // Both stage buffers, every k-step and every tile column are COMPILE-TIME offsets from a per-lane base that is set once:
+            // the stage loop runs two stages per trip (buffer 0, then buffer 1), so a fragment, strip, rotated-diagonal, staging-store
+            // or fused-sum row address is "base register + immediate" (2 x 16 x 208 x 8 = 53 248 bytes: inside the 16-bit offset
+            // field of the LDS instructions) and no address is rebuilt per stage.
+            constexpr int LD13 = 208, BUF13 = KIN_KC * LD13; // row pitch and doubles per stage buffer of the 13-tile shape
+            // One ds_read_b64 per operand, its whole offset in the instruction: left to itself the compiler pairs the reads into
+            // ds_read2_b64, whose two 8-bit offsets reach 2 040 bytes -- a k-step is 6 656 bytes from the next -- and pays for every
+            // pair with a v_add_u32 that builds its base (or, the bases being loop-invariant now, with a register each: 297 spills).
+            auto ldv = [](const double *q) __attribute__((always_inline)) { return *(const volatile __attribute__((address_space(3))) double *)q; };
             double fr[2][KIN13_MAXC];
-            const double *lb = lds + kq * ldsld + fi;
+            const double *lb = lds + kq * LD13 + fi;
             // which of this wave's tiles are strip tiles (r, 12), r < 12
             constexpr bool has_strip = [] { bool h = false; for (int u = 0; u < 6; ++u) h = h || (KIN13_T[W][u][0] >= 0 && KIN13_T[W][u][0] < 12 && KIN13_T[W][u][1] == 12); return h; }();
             double bs[2][2];                          // strip B operands: pools 192 + 4 c + (lane & 3), c = 0, 1
-            const double *lbs = lds + kq * ldsld + 192 + (lane & 3);
+            const double *lbs = lds + kq * LD13 + 192 + (lane & 3);
             // diagonal tiles: the B operands of the block diagonals d = 1, 2 = the tile's fragment rotated by 4 d lanes inside its
             // 16-lane row.  Read from LDS at the rotated address (a DPP rotation is VALU work on the port the MFMAs issue from:
             // measured, it ate the saving)
             constexpr int ND = (SMALL & 1) ? kin13_ndiag(W) : 0;
             double bd[2][ND > 0 ? ND : 1][2];
-            const double *lbr1 = lds + kq * ldsld + ((fi + 4) & 15), *lbr2 = lds + kq * ldsld + ((fi + 8) & 15);
-            auto load_set = [&](const double *bufbase, auto sc, auto pc) __attribute__((always_inline)) {
+            const double *lbr1 = lds + kq * LD13 + ((fi + 4) & 15), *lbr2 = lds + kq * LD13 + ((fi + 8) & 15);
+            auto load_set = [&](auto bc, auto sc, auto pc) __attribute__((always_inline)) {
                 constexpr int s2 = decltype(sc)::value, par = decltype(pc)::value;
+                constexpr int o = decltype(bc)::value * BUF13 + 4 * s2 * LD13; // buffer and k-step
                 static_for<NC>([&](auto cc) __attribute__((always_inline)) {
                     constexpr int ci = decltype(cc)::value;
-                    fr[par][ci] = bufbase[4 * s2 * 208 + 16 * kin13_col(W, ci)];
+                    fr[par][ci] = ldv(lb + (o + 16 * kin13_col(W, ci)));
                 });
                 if constexpr ((SMALL & 2) != 0 && has_strip) {
-                    const double *bb = lbs + (bufbase - lb);
-                    bs[par][0] = bb[4 * s2 * 208];
-                    bs[par][1] = bb[4 * s2 * 208 + 4];
+                    bs[par][0] = ldv(lbs + o);
+                    bs[par][1] = ldv(lbs + (o + 4));
                 }
                 if constexpr (ND > 0) {
                     static_for<NT>([&](auto uc) __attribute__((always_inline)) {
                         constexpr int u = decltype(uc)::value;
                         if constexpr (KIN13_T[W][u][0] == KIN13_T[W][u][1]) {
                             constexpr int di = kin13_diag_index(W, u);
-                            bd[par][di][0] = (lbr1 + (bufbase - lb))[4 * s2 * 208 + 16 * KIN13_T[W][u][0]];
-                            bd[par][di][1] = (lbr2 + (bufbase - lb))[4 * s2 * 208 + 16 * KIN13_T[W][u][0]];
+                            bd[par][di][0] = ldv(lbr1 + (o + 16 * KIN13_T[W][u][0]));
+                            bd[par][di][1] = ldv(lbr2 + (o + 16 * KIN13_T[W][u][0]));
                         }
                     });
                 }
@@ -475,27 +487,120 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                     }
                 });
             };
-            if (nstages > 0) load_set(lb, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            // ---- staging of this wave's pieces.  193..208 pools are 97..104 pieces per locus row, 1552..1664 per stage, so with the
+            // wave known at compile time piece r of its lanes is on in every lane (kind 2: no predicate at all), in no lane (kind 0: the
+            // piece does not exist for this wave -- no load, no store, no registers) or decided per lane (kind 1: under the exec mask).
+            // The byte offset of a piece is a kept register that advances by one stage per load.
+            constexpr auto st_kind = [](int r) { const int t0 = W * 64 + r * KIN_THREADS; return t0 + 63 < KIN_KC * 97 ? 2 : (t0 >= KIN_KC * 104 ? 0 : 1); };
+            uint4_t sreg[KIN_PPT];
+            uint32_t voff[KIN_PPT];
+            uint4_t *sdst[KIN_PPT];
+#pragma unroll
+            for (int r = 0; r < KIN_PPT; ++r) {
+                sreg[r] = (uint4_t){0u, 0u, 0u, 0u};
+                voff[r] = st_voff[r];
+                sdst[r] = reinterpret_cast<uint4_t *>(&lds[st_loc[r] * LD13 + st_lcol[r]]); // 16-byte aligned: even column, pitch 208
+            }
+            auto st_load = [&]() __attribute__((always_inline)) { // the pieces of the NEXT stage
+                static_for<KIN_PPT>([&](auto rc) __attribute__((always_inline)) {
+                    constexpr int r = decltype(rc)::value;
+                    if constexpr (st_kind(r) == 2) {
+                        voff[r] += stage_stride;
+                        sreg[r] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[r], 0, 0);
+                    } else if constexpr (st_kind(r) == 1) {
+                        if (st_on[r]) {
+                            voff[r] += stage_stride;
+                            sreg[r] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[r], 0, 0);
+                        }
+                    }
+                });
+            };
+            auto st_store = [&](auto bc) __attribute__((always_inline)) {
+                constexpr int B = decltype(bc)::value;
+                static_for<KIN_PPT>([&](auto rc) __attribute__((always_inline)) {
+                    constexpr int r = decltype(rc)::value;
+                    if constexpr (st_kind(r) != 0) {
+                        uint4_t v = sreg[r];
+                        if constexpr (ODDN) { // the last piece of a row of an odd pool count carries one pool
+                            if (!st_two[r]) { v.z = 0u; v.w = 0u; }
+                        }
+                        if (st_kind(r) == 2 || st_on[r]) sdst[r][B * (BUF13 / 2)] = v;
+                    }
+                });
+            };
+            // ---- FUSE: the per-locus sums of locus W of the stage (see spec_pass), with the row a compile-time offset from the lane's
+            // pool pointer.  A lane of the fourth 64-pool group that lies past the last pool reads column 0, the shift itself: its
+            // d is +0.0 as in spec_pass, without a clamp or a select.  The sums leave through a buffer descriptor that ends with this
+            // workgroup's loci (a locus past the end is out of range and dropped by the hardware), offset and lane predicate kept.
+            const double *srow = lds + lane, *srow3 = lds + (lane + 192 < P.n ? lane + 192 : 0);
+            const bool sp_on = (lane & 15) == 15 && (lane >> 4) < NV;
+            uint32_t sp_voff = (uint32_t)((W * NV + (lane >> 4)) * 8);
+            const uint32_t sp_stride = (uint32_t)(KIN_KC * NV * 8);
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
+                FUSE ? P.spec + l_begin * NV : nullptr, 0, FUSE ? (int)(uint32_t)((uint64_t)(l_end > l_begin ? l_end - l_begin : 0) * NV * 8) : 0, 0x00020000);
+            const double *sc13 = scratch + (lane >> 4) * 64 + (lane & 15);
+            auto spec13 = [&](auto bc) __attribute__((always_inline)) {
+                static_for<KIN_KC / KIN_WAVES>([&](auto jc) __attribute__((always_inline)) {
+                    constexpr int jl = decltype(jc)::value;
+                    constexpr int ro = decltype(bc)::value * BUF13 + (W + KIN_WAVES * jl) * LD13;
+                    const double shift = ldv(lds + ro); // same address in every lane: an LDS broadcast
+                    double s1 = 0.0, s2 = 0.0, sy[KIN_FUSE_MAXK], d[4];
+#pragma unroll
+                    for (int t = 0; t < KIN_FUSE_MAXK; ++t) sy[t] = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        d[j] = (j < 3 ? ldv(srow + (ro + 64 * j)) : ldv(srow3 + ro)) - shift;
+                        s1 += d[j];
+                        s2 = fma(d[j], d[j], s2);
+                        sy[0] = fma(d[j], yreg[0][j], sy[0]);
+                    }
+                    const bool two = P.k > 1; // wave-uniform
+                    if (two) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) sy[1] = fma(d[j], yreg[1][j], sy[1]);
+                    }
+                    scratch[lane] = s1;
+                    scratch[64 + lane] = s2;
+                    scratch[2 * 64 + lane] = sy[0];
+                    if (two) scratch[3 * 64 + lane] = sy[1];
+                    __builtin_amdgcn_wave_barrier();
+                    double tot = (sc13[0] + sc13[16]) + (sc13[32] + sc13[48]);
+                    tot = dpp_add<0x111, 0xf>(tot); // row_shr:1
+                    tot = dpp_add<0x112, 0xf>(tot); // row_shr:2
+                    tot = dpp_add<0x114, 0xf>(tot); // row_shr:4
+                    tot = dpp_add<0x118, 0xf>(tot); // row_shr:8 -> lane 15 of row v holds value v
+                    if (sp_on)
+                        __builtin_amdgcn_raw_buffer_store_b64((uint2_t){(uint32_t)__double2loint(tot), (uint32_t)__double2hiint(tot)}, srsrc,
+                                                              sp_voff + (uint32_t)(KIN_WAVES * jl * 8) * (uint32_t)NV, 0, 0);
+                    __builtin_amdgcn_wave_barrier();
+                });
+                sp_voff += sp_stride;
+            };
             constexpr int spec_step = (W / 4) % KS; // FUSE: the four waves of a SIMD do their per-locus sums in different k-steps
-            for (int c = 0; c < nstages; ++c) {
-                const bool more = (c + 1) < nstages;
-                if (more) stage_load(c + 1);
-                const double *buf = lds + (c & 1) * bufsz;
-                const double *b0 = lb + (c & 1) * bufsz;
-                const double *b1 = lb + ((c + 1) & 1) * bufsz;
+            auto stage = [&](auto bc, const auto more) __attribute__((always_inline)) {
+                constexpr int B = decltype(bc)::value;
+                if (more) st_load();
                 static_for<KS>([&](auto sc) __attribute__((always_inline)) {
                     constexpr int s2 = decltype(sc)::value;
-                    if constexpr (FUSE && s2 == spec_step) spec_pass(buf, l_begin + (int64_t)c * KIN_KC);
+                    if constexpr (FUSE && s2 == spec_step) spec13(bc);
                     if constexpr (s2 + 1 < KS) {
-                        load_set(b0, std::integral_constant<int, s2 + 1>{}, std::integral_constant<int, (s2 + 1) & 1>{});
+                        load_set(bc, std::integral_constant<int, s2 + 1>{}, std::integral_constant<int, (s2 + 1) & 1>{});
                     } else {
-                        if (more) stage_store((c + 1) & 1);
+                        if (more) st_store(std::integral_constant<int, B ^ 1>{});
                         __syncthreads();
-                        if (more) load_set(b1, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+                        if (more) load_set(std::integral_constant<int, B ^ 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
                     }
                     mfma_set(std::integral_constant<int, s2 & 1>{});
                 });
+            };
+            if (nstages > 0) load_set(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            // two stages per trip (inside the loop the first always has a successor); an odd stage count ends with a peeled stage
+            int c = 0;
+            for (; c + 1 < nstages; c += 2) {
+                stage(std::integral_constant<int, 0>{}, std::true_type{});
+                stage(std::integral_constant<int, 1>{}, c + 2 < nstages);
             }
+            if (c < nstages) stage(std::integral_constant<int, 0>{}, std::false_type{});
             double *slab = P.slabs + (size_t)bx * P.npad * P.npad;
             static_for<NT>([&](auto uc) __attribute__((always_inline)) {
                 constexpr int u = decltype(uc)::value;
@@ -530,16 +635,7 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                 constexpr int ao = 4 * s * 208 + 16 * kin_tri_ti(t, 13);
                 constexpr int bo = 4 * s * 208 + 16 * kin_tri_tj(t, 13);
                 fa[q % R] = bufbase[ao];
-#ifdef KIN_EXP_HALF
-                fb[q % R] = fa[q % R]; // experiment: half the LDS reads (wrong numbers, timing only)
-                (void)bo;
-#elif defined(KIN_EXP_QUARTER)
-                if constexpr (q % 2 == 0) fa[q % R] = bufbase[ao]; else fa[q % R] = fa[(q + R - 1) % R];
-                fb[q % R] = fa[q % R];
-                (void)bo;
-#else
                 fb[q % R] = bufbase[bo];
-#endif
             } else {
                 if constexpr (SKIP) { if (!live[u]) return; } // (wave-uniform) a slot beyond this wave's tiles: neither its reads nor its matrix cycles
                 const double *row = bufbase + 4 * s * ldsld;
@@ -830,7 +926,9 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     auto pick = [&](auto fz) -> hipError_t {
         constexpr bool FZ = decltype(fz)::value;
         if (!spec13) return P.skip_dead ? launch(k_kinship_syrk<FZ, false, 0, true>) : launch(k_kinship_syrk<FZ, false, 0, false>);
-        return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3>) : launch(k_kinship_syrk<FZ, true, 1>);
+        // (an even pool count, the headline among them, runs the instance without the odd-tail zeroing in its stage loop)
+        if (n & 1) return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3>) : launch(k_kinship_syrk<FZ, true, 1>);
+        return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3, false, false>) : launch(k_kinship_syrk<FZ, true, 1, false, false>);
     };
     le = fuse ? pick(std::true_type{}) : pick(std::false_type{});
     PG_HIP(ctx, le);
