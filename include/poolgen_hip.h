@@ -67,7 +67,7 @@ int pg_synchronize(pg_ctx *ctx);
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
                     PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_CSV = 13,
-                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_SYNC = 18, PG_K_COUNT = 19 };
+                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_SYNC = 18, PG_K_PILEUP = 19, PG_K_COUNT = 20 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
@@ -582,6 +582,65 @@ int pg_sync_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t bytes, int expe
                       int64_t *line_off_dev, int32_t *chrom_len_dev, int64_t cap_loci, int64_t cap_counts, pg_sync_info *info);
 int pg_host_sync_parse(const char *text, int64_t bytes, int expect_n, uint32_t *counts, uint64_t *pos, int64_t *line_off,
                        int32_t *chrom_len, int64_t cap_loci, int64_t cap_counts, pg_sync_info *info, int n_threads);
+
+/* ---------------------------------------------------------------------------------------
+ * pileup2sync's reader (base/pileup.rs: String::lparse :11-168, PileupLine::filter :240-334, to_counts :172-215, as the CLI's
+ * PileupConverter::decode restates them): a slab of samtools mpileup text -- it starts at a line start, its last line may
+ * lack the newline, the pointer may have any alignment -- to the allele counts of the loci the filter keeps, in file order.
+ * pool_sizes (host, n_sizes of them; more than 4096 is PG_ERR_INVALID before anything is launched), remove_ns,
+ * keep_lowercase_reference, max_base_error_rate and the three thresholds are FilterStats' fields.
+ * The rules.  A line ends at '\n', one trailing '\r' is dropped; there are no comments, and an empty line has too few fields.
+ * A number is an optional '+' and 1-19 decimal digits.  Pools are triples of fields (coverage, reads, qualities) behind the
+ * third field; a line with another number of pools than n_sizes is checked in full and then dropped.  A pool of coverage 0 is
+ * not looked at beyond its coverage.  In the read string '+' / '-' start a decimal length (leading zeros are skipped; the
+ * first non-digit ends the number and is the first of the `length` bytes skipped, the skip stops at the field end), '^'
+ * skips the byte behind it, '$' is dropped; '.' and ',' are the reference byte as the line writes it, every other byte goes
+ * through lparse's table (anything unknown is N).  Read j pairs with quality byte j: a quality below 33 drops the line, a
+ * quality whose error rate 10^(-(q-33)/10) exceeds max_base_error_rate makes the read an N, and Ns vanish under remove_ns.
+ * Then the breadth rule on the sums that are left (ceil(min_coverage_breadth x n_sizes) pools of min_coverage_depth or more)
+ * and the frequency rule on column T, q = the sum in pool order of the separately rounded (count / sum) x pool_size; a pool
+ * with nothing left makes q NaN, which passes.
+ * Outputs, `kept` rows each:
+ *   counts    uint32, kept x n_sizes x 6 at the positions pileup_to_sync writes (A:T:C:G:D:N)
+ *   pos       uint64;  ref: the reference byte
+ *   line_off  the byte offset of the line in the slab;  chrom_len: the length of its first field (the chromosome's name)
+ * info->kept, lines (all lines of the slab).  Capacities as for pg_vcf_parse_dev: cap_loci rows, cap_counts elements; 0 is the
+ * size query; too small a buffer fails with PG_ERR_INVALID and writes nothing; nothing at or behind the capacities is written.
+ * Where the reference panics the call fails with PG_ERR_INVALID: info->err_line_off is the FIRST such line in file order,
+ * info->err_reason a pg_pileup_reason (else -1 and 0), kept is then 0.  A pool reports the first defect its walk meets (COV,
+ * RAGGED, INDEL, MISMATCH in that order), the line the smallest code among its first three fields' and its pools'.
+ * The result does not depend on where a text is cut into slabs at line starts.
+ * The device form works on the context's stream out of the context's workspace (index, scan, parse, scan, emit) and
+ * synchronises only to read sizes; the rows are complete once the stream has passed the call.  The host form is plain C++ on
+ * n_threads threads, needs no context, and gives the same bytes and the same info.
+ * ------------------------------------------------------------------------------------- */
+enum pg_pileup_reason {
+    PG_PILEUP_E_LONG = 1,    /* a line of 2^31 bytes or more (this library's limit) */
+    PG_PILEUP_E_FIELDS = 2,  /* fewer than three tab-separated fields (an empty line too) */
+    PG_PILEUP_E_POS = 3,     /* the position is no number */
+    PG_PILEUP_E_REF = 4,     /* the reference allele is not one byte below 0x80 */
+    PG_PILEUP_E_COV = 5,     /* a pool's coverage is no number */
+    PG_PILEUP_E_RAGGED = 6,  /* a pool without its read or its quality field */
+    PG_PILEUP_E_INDEL = 7,   /* coverage > 0: a non-digit where the length behind '+' / '-' must start */
+    PG_PILEUP_E_MISMATCH = 8 /* coverage > 0: the reads or the quality bytes are not as many as the coverage says */
+};
+typedef struct {
+    int64_t kept;
+    int64_t lines;
+    int64_t err_line_off;
+    int32_t err_reason;
+    int32_t reserved;
+} pg_pileup_info;
+int pg_pileup_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t bytes, const double *pool_sizes, int n_sizes, int remove_ns,
+                        int keep_lowercase_reference, double max_base_error_rate, uint64_t min_coverage_depth,
+                        double min_coverage_breadth, double min_allele_frequency, uint32_t *counts_dev, uint64_t *pos_dev,
+                        uint8_t *ref_dev, int64_t *line_off_dev, int32_t *chrom_len_dev, int64_t cap_loci, int64_t cap_counts,
+                        pg_pileup_info *info);
+int pg_host_pileup_parse(const char *text, int64_t bytes, const double *pool_sizes, int n_sizes, int remove_ns,
+                         int keep_lowercase_reference, double max_base_error_rate, uint64_t min_coverage_depth,
+                         double min_coverage_breadth, double min_allele_frequency, uint32_t *counts, uint64_t *pos, uint8_t *ref,
+                         int64_t *line_off, int32_t *chrom_len, int64_t cap_loci, int64_t cap_counts, pg_pileup_info *info,
+                         int n_threads);
 
 /* ---------------------------------------------------------------------------------------
  * impute (src/imputation/: filtering_missing.rs, mean_imputation.rs, adaptive_ld_knn_imputation.rs; CLI main.rs:125-142,

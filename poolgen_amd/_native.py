@@ -48,6 +48,16 @@ class PgSyncInfo(C.Structure):
     ]
 
 
+class PgPileupInfo(C.Structure):
+    _fields_ = [
+        ("kept", C.c_int64),
+        ("lines", C.c_int64),
+        ("err_line_off", C.c_int64),
+        ("err_reason", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _u64 = C.c_uint64
 _pi, _pd, _pi64 = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int64)
@@ -112,6 +122,8 @@ SIGNATURES = {
     "pg_host_csv_freq_rows": (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64, _i]),
     "pg_vcf_parse_dev": (_i, [_vp, _vp, _i64, _vp, _i, _u64, _d, _d, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "pg_host_vcf_parse": (_i, [_vp, _i64, _vp, _i, _u64, _d, _d, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i]),
+    "pg_pileup_parse_dev": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _d, _u64, _d, _d, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "pg_host_pileup_parse": (_i, [_vp, _i64, _vp, _i, _i, _i, _d, _u64, _d, _d, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i]),
     "pg_sync_parse_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "pg_host_sync_parse": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i]),
     "pg_set_missing_by_depth_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _d]),
@@ -131,7 +143,7 @@ SIGNATURES = {
 
 KERNEL_IDS = {"kinship": 0, "kinship_reduce": 1, "sweep": 2, "ols_iter": 3, "pearson": 4,
               "chisq": 5, "gp_xxt": 6, "gp_beta": 7, "sweep_finish": 8, "allreduce": 9, "gp_predict": 10, "fisher": 11,
-              "gwalpha": 12, "csv": 13, "impute": 14, "impute_links": 15, "impute_walk": 16, "vcf": 17, "sync": 18}
+              "gwalpha": 12, "csv": 13, "impute": 14, "impute_links": 15, "impute_walk": 16, "vcf": 17, "sync": 18, "pileup": 19}
 
 
 def load_library():

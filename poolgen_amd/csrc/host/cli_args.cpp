@@ -76,6 +76,8 @@ static const char *USAGE =
     "      --n-threads <1>                 parser / writer threads\n"
     "      --sync-parser <host|gpu>        who parses a *.sync input: the host's --n-threads threads (the default), or the GPU that analyses\n"
     "                                      it (the text goes over the link, the counts stay on the device).  The output is the same\n"
+    "      --pileup-parser <host|gpu>      who parses a *.pileup / *.mpileup input, pileup2sync's included: the host's --n-threads threads (the\n"
+    "                                      default), or the GPU (the text goes over the link, the counts come back).  The output is the same\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
     "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
     "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
@@ -133,6 +135,7 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--csv-slab-rows") a.csv_slab_rows = flag_int(val(), k, 1);
         else if (k == "--imputation-method") a.imputation_method = val();
         else if (k == "--sync-parser") a.sync_parser = val();
+        else if (k == "--pileup-parser") a.pileup_parser = val();
         else if (k == "--min-depth-set-to-missing") {
             const std::string t = val();
             if (!parse_f64_strict(t, a.min_depth_set_to_missing)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
@@ -197,6 +200,10 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
         throw std::runtime_error("Invalid value `" + a.sync_parser + "` for --sync-parser. Please select: 'host' or 'gpu'");
     if (a.sync_parser == "gpu" && input_kind(a.fname) != InputKind::sync)
         throw std::runtime_error("--sync-parser gpu applies to a *.sync input; `" + a.fname + "` is converted by its own reader");
+    if (a.pileup_parser != "host" && a.pileup_parser != "gpu")
+        throw std::runtime_error("Invalid value `" + a.pileup_parser + "` for --pileup-parser. Please select: 'host' or 'gpu'");
+    if (a.pileup_parser == "gpu" && input_kind(a.fname) != InputKind::pileup)
+        throw std::runtime_error("--pileup-parser gpu applies to a *.pileup / *.mpileup input; `" + a.fname + "` is read by its own reader");
     gwalpha_fmt = a.phen_format == "gwalpha_fmt";
     if (analysis == Analysis::gwalpha && !gwalpha_fmt)
         throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "

@@ -92,7 +92,8 @@ static void kin_load_pieces(KinRank &K, RankGate &gate, const Args &a, const Phe
         gate.pass([&] { gpu.ok(pg_comm_init_rank(gpu.c, rs.id, R, K.rank), "RCCL communicator"); });
     if (K.c0 >= K.c1) return;
     // (the pinned slots, the counts and the 16-bit scratch live to the end of this phase only)
-    PieceReader pieces(in.mf, in.cuts, K.c0, K.c1, K.device, K.threads, kind, pf, n, true, a.sync_parser == "gpu" ? SyncOnGpu::device : SyncOnGpu::no);
+    PieceReader pieces(in.mf, in.cuts, K.c0, K.c1, K.device, K.threads, kind, pf, n, true, a.sync_parser == "gpu" ? SyncOnGpu::device : SyncOnGpu::no,
+                       a.pileup_parser == "gpu");
     std::vector<double> S_piece((size_t)n2 * n2);
     DeviceBuf<uint32_t> counts_dev;
     CountsUpload upload;
@@ -310,7 +311,7 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
         if (c0 >= c1) return;
         // --sync-parser gpu: the counts stay on the device, except where pools are dropped on the host below
         const SyncOnGpu sync_gpu = a.sync_parser != "gpu" ? SyncOnGpu::no : subset ? SyncOnGpu::host : SyncOnGpu::device;
-        PieceReader pieces(in.mf, in.cuts, c0, c1, device, threads, kind, pf, 0, !subset, sync_gpu);
+        PieceReader pieces(in.mf, in.cuts, c0, c1, device, threads, kind, pf, 0, !subset, sync_gpu, a.pileup_parser == "gpu");
         FILE *fo = nullptr;
         DeviceBuf<uint32_t> counts_dev;
         DeviceBuf<int32_t> n_out_dev, ids_dev;

@@ -1,10 +1,11 @@
 // main.cpp -- `poolgen`, the command line over libpoolgen_hip.so: run() reads the flags (cli_args.h) and the phenotype file,
-// answers pileup2sync on the host and vcf2sync with the GPU's parser, sets up the ranks and hands over to the analysis' translation unit -- the drivers that take
+// answers pileup2sync on the host (or, with --pileup-parser gpu, with the GPU's parser) and vcf2sync with the GPU's parser, sets up the ranks and hands over to the analysis' translation unit -- the drivers that take
 // the input in pieces (cli_streamed.cpp), or the loaded matrix (cli_matrix.cpp) and on it the popgen tools (cli_popgen.cpp), the
 // cross-validation (gp_cv.h) or the kinship GWAS.  Parsing / formatting / ordering follow the reference (base/sync.rs:606-970,
 // :972-1180; gwas/ols.rs:255-275, :372-433); anything else the reference CLI offers is out of scope and reported as such.
 #include "cli.h"
 #include "gp_cv.h"
+#include "pileup_reader.h"
 #include "sync_reader.h"
 #include "vcf.h"
 #include <cstring>
@@ -25,10 +26,16 @@ static int run(int argc, char **argv) {
     SyncAlloc pinned;
     pinned.alloc = PinnedBuf::alloc;
     pinned.release = PinnedBuf::release;
-    if (analysis == Analysis::pileup2sync) { // main.rs:212-225; text to text, no GPU involved
+    if (analysis == Analysis::pileup2sync) { // main.rs:212-225; text to text, no GPU involved unless --pileup-parser gpu asks for it
         std::string out = a.output;
         if (out.empty()) out = basename_no_ext(a.fname) + "-" + unix_time_string() + ".sync"; // pileup.rs:478-494
-        const int64_t kept = pileup_to_sync_file(a.fname, ph.pool_names, pf, out, a.n_threads);
+        int64_t kept;
+        if (a.pileup_parser == "gpu") {
+            probe_output(out); // before any work
+            check_n_gpus(a, analysis);
+            kept = pileup_to_sync_file_gpu(a.gpu_ids.empty() ? 0 : a.gpu_ids[0], a.fname, ph.pool_names, pf, out, a.n_threads);
+        } else
+            kept = pileup_to_sync_file(a.fname, ph.pool_names, pf, out, a.n_threads);
         lap("pileup2sync");
         std::cerr << kept << " loci written\n";
         return done_ok(out);
@@ -70,7 +77,10 @@ static int run(int argc, char **argv) {
         probe_output(csv_out);
     }
     SyncBatch sb;
-    if (kind == InputKind::pileup) {
+    if (kind == InputKind::pileup && a.pileup_parser == "gpu") {
+        sb = parse_pileup_file_gpu(ranks.devices[0], a.fname, a.n_threads, pf, pinned);
+        lap("pileup -> counts (gpu)");
+    } else if (kind == InputKind::pileup) {
         sb = parse_pileup_file(a.fname, a.n_threads, pf, pinned);
         lap("pileup -> counts");
     } else if (kind == InputKind::vcf) {

@@ -4,6 +4,7 @@
 #include "gpu_mem.h"
 #include "host_util.h"
 #include "pileup.h"
+#include "pileup_reader.h"
 #include "sync_reader.h"
 #include "vcf.h"
 #include <cstdlib>
@@ -50,7 +51,8 @@ public:
 // demand), so the batch next() returned is valid until next() is called again.  expect_n / compact16: see parse_sync_buffer; a
 // pileup piece is converted in memory with `pf`, a VCF piece on the device with the thresholds of `pf`.  sync_gpu (a sync input
 // only): the text of a piece is parsed on the rank's device; SyncOnGpu::device leaves the counts there (counts_dev of the batch,
-// in device slot c & 1 of the reader), SyncOnGpu::host copies them back into the pinned slot.
+// in device slot c & 1 of the reader), SyncOnGpu::host copies them back into the pinned slot.  pileup_gpu (a pileup input only): the
+// text of a piece is parsed on the rank's device and the counts come back into the pinned slot.
 enum class SyncOnGpu { no, device, host };
 
 class PieceReader {
@@ -61,6 +63,7 @@ class PieceReader {
     const InputKind kind_;
     std::unique_ptr<VcfReader> vcf_; // a VCF piece is parsed on the rank's device, by a context of the parser's own
     std::unique_ptr<SyncReader> sync_; // --sync-parser gpu: a sync piece likewise
+    std::unique_ptr<PileupReader> pileup_; // --pileup-parser gpu: a pileup piece likewise
     const SyncOnGpu sync_gpu_;
     const PileupFilter &pf_;
     const int expect_n_;
@@ -78,6 +81,7 @@ class PieceReader {
         SyncBatch parsed = sync_ && sync_gpu_ == SyncOnGpu::device ? sync_->parse_dev(b, e, expect_n_, c & 1, mf_.data(), "the sync input", threads_)
                            : sync_                                  ? sync_->parse_host(b, e, expect_n_, al, mf_.data(), "the sync input", threads_)
                            : kind_ == InputKind::vcf      ? vcf_->parse(b, e, al, "the VCF input", threads_)
+                           : pileup_                      ? pileup_->parse(b, e, al, mf_.data(), "the pileup input", threads_)
                            : kind_ == InputKind::pileup ? parse_pileup_buffer(b, e, threads_, pf_, al)
                                                         : parse_sync_buffer(b, e, threads_, expect_n_, al, compact16_);
         drop_parsed_text_(b, e);
@@ -86,11 +90,12 @@ class PieceReader {
     void start() { if (c_ < c1_) next_ = std::async(std::launch::async, [this, c = c_] { return parse(c); }); }
 public:
     PieceReader(const MappedFile &mf, const std::vector<size_t> &cuts, int c0, int c1, int device, int threads, InputKind kind,
-                const PileupFilter &pf, int expect_n, bool compact16, SyncOnGpu sync_gpu = SyncOnGpu::no)
+                const PileupFilter &pf, int expect_n, bool compact16, SyncOnGpu sync_gpu = SyncOnGpu::no, bool pileup_gpu = false)
         : mf_(mf), cuts_(cuts), c_(c0), c1_(c1), device_(device), threads_(threads), kind_(kind), sync_gpu_(sync_gpu), pf_(pf), expect_n_(expect_n),
           compact16_(compact16) {
         if (kind_ == InputKind::vcf) vcf_ = std::make_unique<VcfReader>(device_, pf_);
         if (kind_ == InputKind::sync && sync_gpu_ != SyncOnGpu::no) sync_ = std::make_unique<SyncReader>(device_);
+        if (kind_ == InputKind::pileup && pileup_gpu) pileup_ = std::make_unique<PileupReader>(device_, pf_);
         start();
     }
     bool more() const { return c_ < c1_; }

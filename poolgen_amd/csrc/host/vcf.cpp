@@ -1,6 +1,7 @@
 // vcf.cpp -- see vcf.h.  The device does the parsing; what is left here is per slab (copies, capacities) and per KEPT locus
 // (the chromosome's name, the sync line).
 #include "vcf.h"
+#include "parsed_rows.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -23,22 +24,6 @@ VcfReader::VcfReader(int device, const PileupFilter &f) : device_(device), f_(f)
 VcfReader::~VcfReader() {
     if (ctx_) pg_destroy(ctx_);
 }
-
-namespace {
-// offsets of the four per-locus arrays inside one block of `loci` rows, behind `counts` elements: 16-byte aligned each
-struct RowLayout {
-    size_t counts, pos, off, clen, ref, bytes;
-    RowLayout(int64_t loci, int64_t ncounts) {
-        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        counts = 0;
-        pos = up(sizeof(uint32_t) * (size_t)ncounts);
-        off = pos + up(sizeof(uint64_t) * (size_t)loci);
-        clen = off + up(sizeof(int64_t) * (size_t)loci);
-        ref = clen + up(sizeof(int32_t) * (size_t)loci);
-        bytes = ref + up((size_t)loci) + 16;
-    }
-};
-} // namespace
 
 SyncBatch VcfReader::parse(const char *b, const char *e, const SyncAlloc &alloc, const std::string &what, int n_threads, std::string *sync_text,
                            std::string *chrom_line) {
@@ -104,37 +89,7 @@ SyncBatch VcfReader::parse(const char *b, const char *e, const SyncAlloc &alloc,
             char *rows = static_cast<char *>(pin_rows_.reserve(lay.bytes));
             if (!rows) throw std::runtime_error("out of pinned memory for the rows of " + what);
             hip_ok(hipMemcpy(rows, rows_dev_.get(), lay.ref + (size_t)k, hipMemcpyDeviceToHost), "copy of the rows of a slab");
-            const uint32_t *c = reinterpret_cast<const uint32_t *>(rows + lay.counts);
-            const uint64_t *pos = reinterpret_cast<const uint64_t *>(rows + lay.pos);
-            const int64_t *off = reinterpret_cast<const int64_t *>(rows + lay.off);
-            const int32_t *clen = reinterpret_cast<const int32_t *>(rows + lay.clen);
-            const uint8_t *ref = reinterpret_cast<const uint8_t *>(rows + lay.ref);
-            counts.insert(counts.end(), c, c + (size_t)k * n * 6);
-            sb.pos.insert(sb.pos.end(), pos, pos + k);
-            std::vector<std::string> &nm = sb.chrom_names;
-            for (int64_t i = 0; i < k; ++i) { // the chromosome's name: the one before, most of the time
-                const char *name = s + off[i];
-                const size_t len = (size_t)clen[i];
-                if (last < 0 || nm[last].size() != len || std::memcmp(nm[last].data(), name, len) != 0) {
-                    last = -1;
-                    for (size_t j = 0; j < nm.size(); ++j)
-                        if (nm[j].size() == len && std::memcmp(nm[j].data(), name, len) == 0) { last = (int)j; break; }
-                    if (last < 0) { nm.emplace_back(name, len); last = (int)nm.size() - 1; }
-                }
-                sb.chrom_id.push_back(last);
-            }
-            if (sync_text) {
-                const int parts = (int)std::min<int64_t>(n_threads, k);
-                std::vector<std::string> text(parts);
-                std::vector<std::thread> th;
-                for (int t = 0; t < parts; ++t)
-                    th.emplace_back([&, t] {
-                        for (int64_t i = k * t / parts; i < k * (t + 1) / parts; ++i)
-                            append_sync_line(text[t], s + off[i], (size_t)clen[i], pos[i], ref[i], n, c + (size_t)i * n * 6);
-                    });
-                for (auto &x : th) x.join();
-                for (const std::string &t : text) *sync_text += t;
-            }
+            append_parsed_rows(rows, lay, k, n, s, sb, counts, last, n_threads, sync_text);
         }
         s = z;
     }

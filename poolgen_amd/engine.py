@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._native import KERNEL_IDS, NativeError, PgFilter, PgSyncInfo, PgVcfInfo, load_library
+from ._native import KERNEL_IDS, NativeError, PgFilter, PgPileupInfo, PgSyncInfo, PgVcfInfo, load_library
 
 ALLELES = "ATCGND"  # base/sync.rs:134 reader order
 
@@ -183,6 +183,59 @@ def sync_parse_host(text, expect_n=0, n_threads=1):
         if rc != 0:
             raise NativeError(f"pg_host_sync_parse failed ({rc})")
     return _sync_result(info, counts, pos, off, clen)
+
+
+PILEUP_REASONS = {1: "line of 2^31 bytes or more", 2: "fewer than three tab-separated fields", 3: "position is no number",
+                  4: "reference allele is not one byte below 0x80", 5: "a pool's coverage is no number",
+                  6: "a pool without its read or quality field", 7: "non-digit where an indel length must start",
+                  8: "reads, quality bytes and coverage do not match"}
+
+
+class PileupError(NativeError):
+    """A pileup line at which the reference's pileup2sync panics: `offset` is the byte offset of the first such line of the
+    text, `reason` a pg_pileup_reason."""
+
+    def __init__(self, what, offset, reason):
+        super().__init__(f"{what}: the line at byte {offset} of the text: {PILEUP_REASONS.get(reason, reason)}")
+        self.offset, self.reason = int(offset), int(reason)
+
+
+def _pileup_result(info, n, counts, pos, ref, off, clen):
+    k = info.kept
+    return {"counts": counts[:k * n * 6].reshape(k, n, 6), "pos": pos[:k], "ref": ref[:k], "line_off": off[:k], "chrom_len": clen[:k],
+            "lines": int(info.lines), "n_pools": int(n)}
+
+
+def _pileup_args(pool_sizes, remove_ns, keep_lowercase_reference, max_base_error_rate, min_coverage_depth, min_coverage_breadth,
+                 min_allele_frequency):
+    ps = _host_f64(pool_sizes)
+    return ps, [ps.ctypes.data, len(ps), int(bool(remove_ns)), int(bool(keep_lowercase_reference)), float(max_base_error_rate),
+                int(min_coverage_depth), float(min_coverage_breadth), float(min_allele_frequency)]
+
+
+def pileup_parse_host(text, pool_sizes, remove_ns=True, keep_lowercase_reference=False, max_base_error_rate=0.01, min_coverage_depth=1,
+                      min_coverage_breadth=1.0, min_allele_frequency=0.001, n_threads=1):
+    """Engine.pileup_parse on the host (pg_host_pileup_parse: plain C++, no GPU): the same dictionary, of numpy arrays."""
+    lib = load_library()
+    t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+    ps, rule = _pileup_args(pool_sizes, remove_ns, keep_lowercase_reference, max_base_error_rate, min_coverage_depth, min_coverage_breadth,
+                            min_allele_frequency)
+    info = PgPileupInfo()
+    args = [t.ctypes.data if t.size else None, t.size] + rule
+    rc = lib.pg_host_pileup_parse(*args, None, None, None, None, None, 0, 0, C.byref(info), int(n_threads))
+    if info.err_reason:
+        raise PileupError("pg_host_pileup_parse", info.err_line_off, info.err_reason)
+    k, n = info.kept, len(ps)
+    if rc != 0 and k == 0:
+        raise NativeError(f"pg_host_pileup_parse failed ({rc}): bad arguments")
+    counts = np.empty(k * n * 6, dtype=np.uint32); pos = np.empty(k, dtype=np.uint64); ref = np.empty(k, dtype=np.uint8)
+    off = np.empty(k, dtype=np.int64); clen = np.empty(k, dtype=np.int32)
+    if k:
+        rc = lib.pg_host_pileup_parse(*args, counts.ctypes.data, pos.ctypes.data, ref.ctypes.data, off.ctypes.data, clen.ctypes.data, k,
+                                      counts.size, C.byref(info), int(n_threads))
+        if rc != 0:
+            raise NativeError(f"pg_host_pileup_parse failed ({rc})")
+    return _pileup_result(info, n, counts, pos, ref, off, clen)
 
 
 class Engine:
@@ -622,6 +675,41 @@ class Engine:
             self._check(self._lib.pg_vcf_parse_dev(*args, counts.data_ptr(), pos.data_ptr(), ref.data_ptr(), off.data_ptr(), clen.data_ptr(),
                                                    k, counts.numel(), C.byref(info)), "pg_vcf_parse_dev")
         return _vcf_result(info, counts, pos, ref, off, clen)
+
+    def pileup_parse(self, text, pool_sizes, remove_ns: bool = True, keep_lowercase_reference: bool = False,
+                     max_base_error_rate: float = 0.01, min_coverage_depth: int = 1, min_coverage_breadth: float = 1.0,
+                     min_allele_frequency: float = 0.001):
+        """A slab of samtools mpileup text -- bytes, a NumPy uint8 array or a torch uint8 tensor (on the device it is parsed in
+        place); it starts at a line start, its last line may lack the newline -- to what pileup2sync keeps of it (base/pileup.rs),
+        parsed on the GPU.  A dictionary: counts (kept x n_pools x 6 at the positions pileup_to_sync writes, A:T:C:G:D:N; the
+        uint32 bits as int32, as the loader takes them), pos (the uint64 bits as int64), ref (uint8), line_off (int64), chrom_len
+        (int32) as tensors on the device, and the integers lines, n_pools.  A line at which the reference panics raises
+        PileupError."""
+        dev = torch.device("cuda", self.device)
+        if isinstance(text, torch.Tensor):
+            t = text.to(dev)
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError("pileup_parse: text must be a contiguous uint8 tensor")
+        else:
+            a = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+            t = torch.from_numpy(a.copy()).to(dev)
+        ps, rule = _pileup_args(pool_sizes, remove_ns, keep_lowercase_reference, max_base_error_rate, min_coverage_depth,
+                                min_coverage_breadth, min_allele_frequency)
+        info = PgPileupInfo()
+        args = [self._ctx, t.data_ptr() if t.numel() else None, t.numel()] + rule
+        rc = self._lib.pg_pileup_parse_dev(*args, None, None, None, None, None, 0, 0, C.byref(info))
+        if info.err_reason:
+            raise PileupError("pg_pileup_parse_dev", info.err_line_off, info.err_reason)
+        k, n = info.kept, len(ps)
+        if rc != 0 and k == 0:
+            self._check(rc, "pg_pileup_parse_dev")
+        counts = torch.empty(k * n * 6, dtype=torch.int32, device=dev)
+        pos = torch.empty(k, dtype=torch.int64, device=dev); ref = torch.empty(k, dtype=torch.uint8, device=dev)
+        off = torch.empty(k, dtype=torch.int64, device=dev); clen = torch.empty(k, dtype=torch.int32, device=dev)
+        if k:
+            self._check(self._lib.pg_pileup_parse_dev(*args, counts.data_ptr(), pos.data_ptr(), ref.data_ptr(), off.data_ptr(),
+                                                      clen.data_ptr(), k, counts.numel(), C.byref(info)), "pg_pileup_parse_dev")
+        return _pileup_result(info, n, counts, pos, ref, off, clen)
 
     def sync_parse(self, text, expect_n: int = 0):
         """A slab of sync text -- bytes, a NumPy uint8 array or a torch uint8 tensor (on the device it is parsed in place); it starts
