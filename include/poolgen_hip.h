@@ -67,7 +67,8 @@ int pg_synchronize(pg_ctx *ctx);
 enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, PG_K_OLS_ITER = 3,
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
                     PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_CSV = 13,
-                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_SYNC = 18, PG_K_PILEUP = 19, PG_K_COUNT = 20 };
+                    PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_SYNC = 18, PG_K_PILEUP = 19, PG_K_SYNCFMT = 20,
+                    PG_K_COUNT = 21 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
@@ -641,6 +642,29 @@ int pg_host_pileup_parse(const char *text, int64_t bytes, const double *pool_siz
                          double min_coverage_breadth, double min_allele_frequency, uint32_t *counts, uint64_t *pos, uint8_t *ref,
                          int64_t *line_off, int32_t *chrom_len, int64_t cap_loci, int64_t cap_counts, pg_pileup_info *info,
                          int n_threads);
+
+/* ---------------------------------------------------------------------------------------
+ * The sync writer of pileup2sync and vcf2sync (pileup_to_sync, base/pileup.rs:348-371; vcf_to_sync, base/vcf.rs:212-229): the
+ * rows the three parsers above leave -- counts (rows x n_pools x 6), pos, ref, line_off, chrom_len -- plus the slab of text
+ * their line offsets point into, as the bytes of their sync lines, in row order.  A line is
+ *   slab[line_off .. line_off + chrom_len) '\t' pos '\t' ref, per pool '\t' and its six counts joined by ':', '\n'
+ * with every number in plain decimal (no sign, no leading zeros, "0" for zero).  pg_sync_parse_dev writes no ref array: its
+ * caller supplies one.  n_pools is 1 to 4096, the sync parser's limit; more is PG_ERR_INVALID before anything is launched.
+ * *bytes is always set to the size the text needs; bytes > cap fails with PG_ERR_INVALID and writes nothing (cap = 0 is the
+ * size query, text may then be NULL).  Nothing at or behind text[bytes] is written; text may have any alignment.  A row whose
+ * line_off < 0, chrom_len < 0 or line_off + chrom_len > slab_bytes fails the call with PG_ERR_INVALID and *bytes = 0; so does
+ * a row whose line would be longer than 2^22 bytes (this library's limit; 4096 pools of ten-digit counts are 270 KB).
+ * rows = 0 is PG_OK with *bytes = 0.  Both forms behave alike in all of this.
+ * The device form formats on the GPU (measure, scan, emit on the context's stream out of the context's workspace; it
+ * synchronises once to read the size, and the text is complete once the stream has passed the call); the host form is plain
+ * C++ on n_threads threads, no context, and gives the same bytes.
+ * ------------------------------------------------------------------------------------- */
+int pg_sync_format_rows_dev(pg_ctx *ctx, const char *slab_dev, int64_t slab_bytes, const uint32_t *counts_dev,
+                            const uint64_t *pos_dev, const uint8_t *ref_dev, const int64_t *line_off_dev,
+                            const int32_t *chrom_len_dev, int n_pools, int64_t rows, char *text_dev, int64_t cap, int64_t *bytes);
+int pg_host_sync_format_rows(const char *slab, int64_t slab_bytes, const uint32_t *counts, const uint64_t *pos,
+                             const uint8_t *ref, const int64_t *line_off, const int32_t *chrom_len, int n_pools, int64_t rows,
+                             char *text, int64_t cap, int64_t *bytes, int n_threads);
 
 /* ---------------------------------------------------------------------------------------
  * impute (src/imputation/: filtering_missing.rs, mean_imputation.rs, adaptive_ld_knn_imputation.rs; CLI main.rs:125-142,

@@ -78,6 +78,9 @@ static const char *USAGE =
     "                                      it (the text goes over the link, the counts stay on the device).  The output is the same\n"
     "      --pileup-parser <host|gpu>      who parses a *.pileup / *.mpileup input, pileup2sync's included: the host's --n-threads threads (the\n"
     "                                      default), or the GPU (the text goes over the link, the counts come back).  The output is the same\n"
+    "      --sync-writer <host|gpu>        pileup2sync (with --pileup-parser gpu), vcf2sync: who formats the sync lines: the host's --n-threads\n"
+    "                                      threads (the default), or the GPU that parsed the input (the counts then never leave the device,\n"
+    "                                      only the text comes back).  The output is the same\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
     "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
     "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
@@ -136,6 +139,7 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--imputation-method") a.imputation_method = val();
         else if (k == "--sync-parser") a.sync_parser = val();
         else if (k == "--pileup-parser") a.pileup_parser = val();
+        else if (k == "--sync-writer") a.sync_writer = val();
         else if (k == "--min-depth-set-to-missing") {
             const std::string t = val();
             if (!parse_f64_strict(t, a.min_depth_set_to_missing)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
@@ -204,6 +208,12 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
         throw std::runtime_error("Invalid value `" + a.pileup_parser + "` for --pileup-parser. Please select: 'host' or 'gpu'");
     if (a.pileup_parser == "gpu" && input_kind(a.fname) != InputKind::pileup)
         throw std::runtime_error("--pileup-parser gpu applies to a *.pileup / *.mpileup input; `" + a.fname + "` is read by its own reader");
+    if (a.sync_writer != "host" && a.sync_writer != "gpu")
+        throw std::runtime_error("Invalid value `" + a.sync_writer + "` for --sync-writer. Please select: 'host' or 'gpu'");
+    if (a.sync_writer == "gpu" && analysis != Analysis::pileup2sync && analysis != Analysis::vcf2sync)
+        throw std::runtime_error("--sync-writer gpu applies to pileup2sync and vcf2sync, which write a sync file; `" + a.analysis + "` writes none");
+    if (a.sync_writer == "gpu" && analysis == Analysis::pileup2sync && a.pileup_parser != "gpu")
+        throw std::runtime_error("--sync-writer gpu on pileup2sync needs --pileup-parser gpu: with the host's parser the rows are not on the device");
     gwalpha_fmt = a.phen_format == "gwalpha_fmt";
     if (analysis == Analysis::gwalpha && !gwalpha_fmt)
         throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "

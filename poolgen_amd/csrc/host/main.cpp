@@ -1,5 +1,6 @@
 // main.cpp -- `poolgen`, the command line over libpoolgen_hip.so: run() reads the flags (cli_args.h) and the phenotype file,
-// answers pileup2sync on the host (or, with --pileup-parser gpu, with the GPU's parser) and vcf2sync with the GPU's parser, sets up the ranks and hands over to the analysis' translation unit -- the drivers that take
+// answers pileup2sync on the host (or, with --pileup-parser gpu, with the GPU's parser) and vcf2sync with the GPU's parser (either
+// with the GPU's writer under --sync-writer gpu), sets up the ranks and hands over to the analysis' translation unit -- the drivers that take
 // the input in pieces (cli_streamed.cpp), or the loaded matrix (cli_matrix.cpp) and on it the popgen tools (cli_popgen.cpp), the
 // cross-validation (gp_cv.h) or the kinship GWAS.  Parsing / formatting / ordering follow the reference (base/sync.rs:606-970,
 // :972-1180; gwas/ols.rs:255-275, :372-433); anything else the reference CLI offers is out of scope and reported as such.
@@ -33,7 +34,7 @@ static int run(int argc, char **argv) {
         if (a.pileup_parser == "gpu") {
             probe_output(out); // before any work
             check_n_gpus(a, analysis);
-            kept = pileup_to_sync_file_gpu(a.gpu_ids.empty() ? 0 : a.gpu_ids[0], a.fname, ph.pool_names, pf, out, a.n_threads);
+            kept = pileup_to_sync_file_gpu(a.gpu_ids.empty() ? 0 : a.gpu_ids[0], a.fname, ph.pool_names, pf, out, a.n_threads, a.sync_writer == "gpu");
         } else
             kept = pileup_to_sync_file(a.fname, ph.pool_names, pf, out, a.n_threads);
         lap("pileup2sync");
@@ -45,7 +46,7 @@ static int run(int argc, char **argv) {
         if (out.empty()) out = basename_no_ext(a.fname) + "-" + unix_time_string() + ".sync"; // vcf.rs:317-337
         probe_output(out);                                                                    // :339, before any work
         check_n_gpus(a, analysis);
-        const int64_t kept = vcf_to_sync_file(a.gpu_ids.empty() ? 0 : a.gpu_ids[0], a.fname, pf, out, a.n_threads);
+        const int64_t kept = vcf_to_sync_file(a.gpu_ids.empty() ? 0 : a.gpu_ids[0], a.fname, pf, out, a.n_threads, a.sync_writer == "gpu");
         lap("vcf2sync");
         std::cerr << kept << " loci written\n";
         return done_ok(out);

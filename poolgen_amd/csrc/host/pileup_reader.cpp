@@ -29,13 +29,13 @@ PileupReader::PileupReader(int device, const PileupFilter &f) : device_(device),
 PileupReader::~PileupReader() {
     if (std::getenv("PGH_TIMING") && bytes_ > 0)
         std::fprintf(stderr, "poolgen: pileup reader on GPU %d, %.1f MB of text: copy into pinned memory and H2D of the text %.3f s, parse call %.3f s, "
-                             "D2H of the rows and label bookkeeping %.3f s\n",
-                     device_, bytes_ / 1e6, t_h2d_, t_parse_, t_rows_);
+                             "%s %.3f s\n",
+                     device_, bytes_ / 1e6, t_h2d_, t_parse_, dev_written_ ? "the sync writer (--sync-writer gpu)" : "D2H of the rows and label bookkeeping", t_rows_);
     if (ctx_) pg_destroy(ctx_);
 }
 
 SyncBatch PileupReader::parse(const char *b, const char *e, const SyncAlloc &alloc, const char *origin, const std::string &what, int n_threads,
-                              std::string *sync_text) {
+                              std::string *sync_text, DeviceSyncWriter *dev_writer) {
     hip_ok(hipSetDevice(device_), "hipSetDevice");
     if (n_threads < 1) n_threads = 1;
     SyncBatch sb;
@@ -85,7 +85,12 @@ SyncBatch PileupReader::parse(const char *b, const char *e, const SyncAlloc &all
             rows_dev_.reset(RowLayout(cap_loci_, cap_counts_).bytes, "the rows of a slab of pileup text");
         }
         const int64_t k = info.kept;
-        if (k > 0) {
+        if (k > 0 && dev_writer) { // --sync-writer gpu: the rows stay on the device, their text comes back
+            t_parse_ += clk() - t0; t0 = clk();
+            dev_written_ = true;
+            dev_writer->append_rows(ctx_, text_dev_.get(), bytes, rows_dev_.get(), lay, k, n);
+            t_rows_ += clk() - t0;
+        } else if (k > 0) {
             // the rows come back in one copy: everything the device wrote lies in front of lay.ref + k (the copy waits for the emit pass)
             char *rows = static_cast<char *>(pin_rows_.reserve(lay.bytes));
             if (!rows) throw std::runtime_error("out of pinned memory for the rows of " + what);
@@ -114,9 +119,18 @@ SyncBatch parse_pileup_file_gpu(int device, const std::string &fname, int n_thre
 }
 
 int64_t pileup_to_sync_file_gpu(int device, const std::string &fname, const std::vector<std::string> &pool_names, const PileupFilter &f,
-                                const std::string &out_fname, int n_threads) {
+                                const std::string &out_fname, int n_threads, bool gpu_writer) {
     const MappedFile mf(fname);
     PileupReader reader(device, f);
+    if (gpu_writer) { // the lines are formatted on the device and written slab by slab; an error on the way removes the file (DeviceSyncWriter)
+        std::string header = "#chr\tpos\tref";
+        for (const std::string &nm : pool_names) { header.push_back('\t'); header += nm; }
+        header.push_back('\n');
+        DeviceSyncWriter writer(out_fname);
+        writer.set_header(header);
+        reader.parse(mf.data(), mf.data() + mf.size(), SyncAlloc(), mf.data(), fname, n_threads, nullptr, &writer);
+        return writer.finish(header);
+    }
     std::string text;
     const SyncBatch sb = reader.parse(mf.data(), mf.data() + mf.size(), SyncAlloc(), mf.data(), fname, n_threads, &text);
     const int ofd = ::open(out_fname.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);

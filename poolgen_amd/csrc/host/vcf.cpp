@@ -25,8 +25,23 @@ VcfReader::~VcfReader() {
     if (ctx_) pg_destroy(ctx_);
 }
 
+// "#chr\tpos\tref\t" + the pool names: fields 9.. of a "#CHROM" line (vcf.rs:343-359); false when the line has no such fields
+static bool vcf_sync_header(const std::string &chrom_line, std::string &header) {
+    std::string names;
+    int field = 0;
+    for (size_t i = 0; i < chrom_line.size(); ++i) {
+        if (chrom_line[i] == '\t') {
+            ++field;
+            if (field > 9) names.push_back('\t');
+        } else if (field >= 9)
+            names.push_back(chrom_line[i]);
+    }
+    header = "#chr\tpos\tref\t" + names + "\n";
+    return field >= 9;
+}
+
 SyncBatch VcfReader::parse(const char *b, const char *e, const SyncAlloc &alloc, const std::string &what, int n_threads, std::string *sync_text,
-                           std::string *chrom_line) {
+                           std::string *chrom_line, DeviceSyncWriter *dev_writer) {
     hip_ok(hipSetDevice(device_), "hipSetDevice");
     if (n_threads < 1) n_threads = 1;
     SyncBatch sb;
@@ -78,13 +93,17 @@ SyncBatch VcfReader::parse(const char *b, const char *e, const SyncAlloc &alloc,
             le = le ? le : z;
             if (le > line && le[-1] == '\r' && le < z) --le;
             chrom_line->assign(line, le);
+            std::string header;
+            if (dev_writer && vcf_sync_header(*chrom_line, header)) dev_writer->set_header(header);
         }
         if (info.data_lines > 0) {
             if (n < 0) n = info.n_pools;
             else if (n != info.n_pools) throw std::runtime_error("Input file error, i.e. '" + what + "': the number of samples changes inside the file");
         }
         const int64_t k = info.kept;
-        if (k > 0) {
+        if (k > 0 && dev_writer) // --sync-writer gpu: the rows stay on the device, their text comes back
+            dev_writer->append_rows(ctx_, text_dev_.get(), bytes, rows_dev_.get(), lay, k, n);
+        else if (k > 0) {
             // the rows come back in one copy: everything the device wrote lies in front of lay.ref + k
             char *rows = static_cast<char *>(pin_rows_.reserve(lay.bytes));
             if (!rows) throw std::runtime_error("out of pinned memory for the rows of " + what);
@@ -109,27 +128,24 @@ SyncBatch parse_vcf_file(int device, const std::string &fname, int n_threads, co
     return reader.parse(mf.data(), mf.data() + mf.size(), alloc, fname, n_threads);
 }
 
-int64_t vcf_to_sync_file(int device, const std::string &fname, const PileupFilter &f, const std::string &out_fname, int n_threads) {
+int64_t vcf_to_sync_file(int device, const std::string &fname, const PileupFilter &f, const std::string &out_fname, int n_threads,
+                         bool gpu_writer) {
     const MappedFile mf(fname);
     VcfReader reader(device, f);
-    std::string text, chrom_line;
+    std::string text, chrom_line, header;
+    const char *no_names = "Pool names not found, please check the header line of the vcf file. Make sure `#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT...` header exists.";
+    if (gpu_writer) { // the lines are formatted on the device and written slab by slab; an error on the way removes the file (DeviceSyncWriter)
+        DeviceSyncWriter writer(out_fname);
+        reader.parse(mf.data(), mf.data() + mf.size(), SyncAlloc(), fname, n_threads, nullptr, &chrom_line, &writer);
+        if (!vcf_sync_header(chrom_line, header)) throw std::runtime_error(no_names);
+        return writer.finish(header);
+    }
     const SyncBatch sb = reader.parse(mf.data(), mf.data() + mf.size(), SyncAlloc(), fname, n_threads, &text, &chrom_line);
     // the pool names: fields 9.. of the last #CHROM line (vcf.rs:343-359)
-    std::string names;
-    int field = 0;
-    for (size_t i = 0; i < chrom_line.size(); ++i) {
-        if (chrom_line[i] == '\t') {
-            ++field;
-            if (field > 9) names.push_back('\t');
-        } else if (field >= 9)
-            names.push_back(chrom_line[i]);
-    }
-    if (field < 9)
-        throw std::runtime_error("Pool names not found, please check the header line of the vcf file. Make sure `#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT...` header exists.");
+    if (!vcf_sync_header(chrom_line, header)) throw std::runtime_error(no_names);
     const int ofd = ::open(out_fname.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
     if (ofd < 0) throw std::runtime_error("Unable to create file: " + out_fname + " (it must not exist)");
     FILE *fo = ::fdopen(ofd, "w");
-    const std::string header = "#chr\tpos\tref\t" + names + "\n";
     std::fwrite(header.data(), 1, header.size(), fo);
     std::fwrite(text.data(), 1, text.size(), fo);
     std::fclose(fo);

@@ -238,6 +238,34 @@ def pileup_parse_host(text, pool_sizes, remove_ns=True, keep_lowercase_reference
     return _pileup_result(info, n, counts, pos, ref, off, clen)
 
 
+def sync_format_host(counts, pos, ref, line_off, chrom_len, slab, n_threads=1):
+    """Engine.sync_format on the host (pg_host_sync_format_rows: plain C++, no GPU): the rows of a parser's dictionary as NumPy
+    arrays plus the text they were parsed from, to the bytes of their sync lines.  The checker of the device form and the
+    baseline it is measured against."""
+    lib = load_library()
+    c = np.ascontiguousarray(counts).view(np.uint32) if np.asarray(counts).dtype == np.int32 else np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.ndim != 3 or c.shape[2] != 6:
+        raise ValueError("sync_format_host: counts must be rows x n_pools x 6")
+    k, n = c.shape[0], c.shape[1]
+    po = np.ascontiguousarray(pos).view(np.uint64) if np.asarray(pos).dtype == np.int64 else np.ascontiguousarray(pos, dtype=np.uint64)
+    rf = np.ascontiguousarray(ref, dtype=np.uint8); off = np.ascontiguousarray(line_off, dtype=np.int64)
+    cl = np.ascontiguousarray(chrom_len, dtype=np.int32)
+    if not (len(po) == len(rf) == len(off) == len(cl) == k):
+        raise ValueError("sync_format_host: the row arrays do not match")
+    t = np.frombuffer(slab, dtype=np.uint8) if isinstance(slab, (bytes, bytearray, memoryview)) else np.ascontiguousarray(slab, dtype=np.uint8)
+    args = [t.ctypes.data if t.size else None, t.size, c.ctypes.data, po.ctypes.data, rf.ctypes.data, off.ctypes.data, cl.ctypes.data, n, k]
+    need = C.c_int64()
+    rc = lib.pg_host_sync_format_rows(*args, None, 0, C.byref(need), int(n_threads))
+    if rc != 0 and need.value == 0:
+        raise NativeError(f"pg_host_sync_format_rows failed ({rc}): bad arguments, or a row's chromosome name lies outside the slab")
+    out = np.empty(max(need.value, 1), dtype=np.uint8)
+    if need.value:
+        rc = lib.pg_host_sync_format_rows(*args, out.ctypes.data, need.value, C.byref(need), int(n_threads))
+        if rc != 0:
+            raise NativeError(f"pg_host_sync_format_rows failed ({rc})")
+    return out[:need.value].tobytes()
+
+
 class Engine:
     def __init__(self, device: int | None = None, use_torch_stream: bool = True):
         self._lib = load_library()
@@ -740,6 +768,40 @@ class Engine:
             self._check(self._lib.pg_sync_parse_dev(*args, counts.data_ptr(), pos.data_ptr(), off.data_ptr(), clen.data_ptr(), k, counts.numel(),
                                                     C.byref(info)), "pg_sync_parse_dev")
         return _sync_result(info, counts, pos, off, clen)
+
+    def sync_format(self, counts, pos, ref, line_off, chrom_len, slab, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The rows vcf_parse / pileup_parse / sync_parse return (tensors on the device; sync_parse has no `ref`: supply one) plus
+        the text they were parsed from (`slab`: a uint8 tensor on the device, or bytes / a NumPy array that is copied there) as the
+        bytes of their sync lines (pileup_to_sync, pileup.rs:348-371; vcf_to_sync, vcf.rs:212-229), formatted on the GPU: a
+        torch.uint8 tensor on the device.  With `out` (a uint8 tensor on the device that is large enough) one call formats into
+        it, without the size query, and the filled part of `out` is returned."""
+        dev = torch.device("cuda", self.device)
+        if counts.dim() != 3 or counts.shape[2] != 6:
+            raise ValueError("sync_format: counts must be rows x n_pools x 6")
+        k, n = int(counts.shape[0]), int(counts.shape[1])
+        if not (pos.numel() == ref.numel() == line_off.numel() == chrom_len.numel() == k):
+            raise ValueError("sync_format: the row arrays do not match")
+        if isinstance(slab, torch.Tensor):
+            t = slab.to(dev)
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError("sync_format: slab must be a contiguous uint8 tensor")
+        else:
+            a = np.frombuffer(slab, dtype=np.uint8) if isinstance(slab, (bytes, bytearray, memoryview)) else np.ascontiguousarray(slab, dtype=np.uint8)
+            t = torch.from_numpy(a.copy()).to(dev)
+        args = [self._ctx, t.data_ptr() if t.numel() else None, t.numel(), self._dev(counts, torch.int32), self._dev(pos, torch.int64),
+                self._dev(ref, torch.uint8), self._dev(line_off, torch.int64), self._dev(chrom_len, torch.int32), n, k]
+        need = C.c_int64()
+        if out is not None:
+            self._check(self._lib.pg_sync_format_rows_dev(*args, self._dev(out, torch.uint8), out.numel(), C.byref(need)),
+                        "pg_sync_format_rows_dev")
+            return out[:need.value]
+        rc = self._lib.pg_sync_format_rows_dev(*args, None, 0, C.byref(need))
+        if rc != 0 and need.value == 0:
+            self._check(rc, "pg_sync_format_rows_dev")
+        out = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        if need.value:
+            self._check(self._lib.pg_sync_format_rows_dev(*args, out.data_ptr(), need.value, C.byref(need)), "pg_sync_format_rows_dev")
+        return out
 
     # ---- imputation (src/imputation/) ------------------------------------------------------------
     def _impute_args(self, M, locus_col, n):
