@@ -68,7 +68,7 @@ enum pg_kernel_id { PG_K_KINSHIP = 0, PG_K_KINSHIP_REDUCE = 1, PG_K_SWEEP = 2, P
                     PG_K_PEARSON = 4, PG_K_CHISQ = 5, PG_K_GP_XXT = 6, PG_K_GP_BETA = 7,
                     PG_K_SWEEP_FINISH = 8, PG_K_ALLREDUCE = 9, PG_K_GP_PREDICT = 10, PG_K_FISHER = 11, PG_K_GWALPHA = 12, PG_K_CSV = 13,
                     PG_K_IMPUTE = 14, PG_K_IMPUTE_LINKS = 15, PG_K_IMPUTE_WALK = 16, PG_K_VCF = 17, PG_K_SYNC = 18, PG_K_PILEUP = 19, PG_K_SYNCFMT = 20,
-                    PG_K_COUNT = 21 };
+                    PG_K_RESULTFMT = 21, PG_K_COUNT = 22 };
 int pg_profile_enable(pg_ctx *ctx, int on);
 int pg_profile_reset(pg_ctx *ctx);
 /* Synchronises, then returns total milliseconds and launch count of one kernel id. */
@@ -665,6 +665,69 @@ int pg_sync_format_rows_dev(pg_ctx *ctx, const char *slab_dev, int64_t slab_byte
 int pg_host_sync_format_rows(const char *slab, int64_t slab_bytes, const uint32_t *counts, const uint64_t *pos,
                              const uint8_t *ref, const int64_t *line_off, const int32_t *chrom_len, int n_pools, int64_t rows,
                              char *text, int64_t cap, int64_t *bytes, int n_threads);
+
+/* ---------------------------------------------------------------------------------------
+ * The result writer: the CSV rows of the GWAS analyses, formatted where the statistics are.
+ *
+ * The number text (pg_f64_text.h, one source for host and device).  display(x) is Rust's `{}` of an f64, which is what the
+ * reference prints: "NaN", "inf", "-inf", "0", "-0", otherwise the SHORTEST decimal digit string (1 to 17 digits) that reads
+ * back as the same double -- the closest such string, the even one on a tie -- in fixed notation: no exponent, no trailing
+ * zeros behind the point, "0." and leading zeros below 1, padded with zeros for large exponents.  At most PG_F64_TEXT_MAX = 327
+ * bytes ("-0." + 307 zeros + 17 digits).  roundup_own(x, nd) is parse_f64_roundup_and_own (base/helpers.rs:103-117): display(x)
+ * when that has fewer than nd characters, else display(round_half_away_from_zero(x * 10^nd) / 10^nd), the product and the
+ * quotient rounded separately.
+ * THE HOST WRITER'S DIFFERENCE: the CLI's rust_display is std::to_chars(fixed), which equals display() for every |x| < 2^53
+ * -- every fixture and every realistic statistic -- but prints the exact integer from about 2^54 on, where Rust (and this
+ * formatter) print the shortest digits padded with zeros.  There this formatter is the one that matches the reference.
+ *
+ * Conventions of the three pairs below, those of pg_sync_format_rows_dev: *bytes is always set to the size the text needs;
+ * bytes > cap fails with PG_ERR_INVALID and writes nothing (cap = 0 is the size query, text may then be NULL); nothing at or
+ * behind text[bytes] is written; text may have any alignment; no rows is PG_OK with *bytes = 0; bad arguments, a label out of
+ * range (a chromosome id outside [0, n_chrom), name offsets that decrease, an allele id outside [0, 6)) or a unit above the row
+ * limit fail with PG_ERR_INVALID and *bytes = 0.  The row limit: the text of one unit -- one value, one locus with all its
+ * rows, one kinship row -- is at most 2^22 bytes; at most 2^31 units per call; k is 1 to PG_RESULT_MAX_TRAITS.  Both forms
+ * behave alike in all of this and give the same bytes.  The device form formats on the GPU (measure, 64-bit scan, emit on the
+ * context's stream out of the context's workspace; it synchronises once to read the size, and the text is complete once the
+ * stream has passed the call); the host form is plain C++ on n_threads threads and needs no context.
+ * ------------------------------------------------------------------------------------- */
+#define PG_F64_TEXT_MAX 327
+#define PG_RESULT_MAX_TRAITS 4096
+/* One line per value: display(x) for n_digits < 0, roundup_own(x, n_digits) for 0 <= n_digits <= 22 (more is PG_ERR_INVALID),
+ * then '\n'. */
+int pg_f64_text_dev(pg_ctx *ctx, const double *x_dev, int64_t count, int n_digits, char *text_dev, int64_t cap, int64_t *bytes);
+int pg_host_f64_text(const double *x, int64_t count, int n_digits, char *text, int64_t cap, int64_t *bytes, int n_threads);
+/* The rows of the per-locus operators (format_locus_rows of the CLI; fisher_exact_test.rs:119-129, chisq_test.rs:37-45,
+ * gwalpha.rs:318-326, correlation_test.rs:117-124, ols.rs:263-271) from the slot-major outputs of the pg_*_batch_dev entry
+ * points exactly as they leave them, labels as pg_csv_freq_rows_dev takes them (chromosome id and position per locus, the
+ * names as one byte string with n_chrom + 1 int32 offsets).  Order: locus, then slot, then trait; a locus with n_out <= 0
+ * emits nothing; n_out is clipped at PG_MAX_OUT.  D = display, R(x, n) = roundup_own, a letter indexes "ATCGND":
+ *   PG_RESULT_FISHER   chr,pos,<letters of all slots>,D(stat[l]),D(pval[l])            one row per locus (k is ignored)
+ *   PG_RESULT_CHISQ    chr,pos,<letters of all slots>,R(stat[l],6),D(pval[l])          one row per locus (k is ignored)
+ *   PG_RESULT_GWALPHA  chr,pos,letter,R(freq,6),Pheno_0,R(stat,6),Unknown              per slot (k = 1; pval may be NULL)
+ *   PG_RESULT_PEARSON  chr,pos,letter,D(freq),Pheno_j,R(stat,6),D(pval)                per slot and trait j
+ *   PG_RESULT_OLS_ITER chr,pos,letter,R(freq,8),Pheno_j,R(stat,6),R(pval,12)           per slot and trait j
+ * mean_freq may be NULL for the first two. */
+enum pg_result_op { PG_RESULT_FISHER = 0, PG_RESULT_CHISQ = 1, PG_RESULT_GWALPHA = 2, PG_RESULT_PEARSON = 3, PG_RESULT_OLS_ITER = 4 };
+int pg_result_rows_dev(pg_ctx *ctx, int op, int64_t L, int k, const int32_t *n_out_dev, const int32_t *allele_ids_dev,
+                       const double *mean_freq_dev, const double *stat_dev, const double *pval_dev, const int32_t *locus_chrom_dev,
+                       const uint64_t *locus_pos_dev, const char *chrom_text_dev, const int32_t *chrom_off_dev, int n_chrom,
+                       char *text_dev, int64_t cap, int64_t *bytes);
+int pg_host_result_rows(int op, int64_t L, int k, const int32_t *n_out, const int32_t *allele_ids, const double *mean_freq,
+                        const double *stat, const double *pval, const int32_t *locus_chrom, const uint64_t *locus_pos,
+                        const char *chrom_text, const int32_t *chrom_off, int n_chrom, char *text, int64_t cap, int64_t *bytes,
+                        int n_threads);
+/* Rows [row0, row0 + rows) of the k * p rows of the kinship analyses' CSV (write_kinship_csv of the CLI; ols.rs:409-433),
+ * trait-major: row r = j * p + i is  label_i,Pheno_j,D(beta[i*k+j]),D(pval[i*k+j])  with the reference's label shift kept as
+ * it is (ols.rs:421-425): coefficient 0 is "intercept,0,intercept", coefficient i >= 1 carries chromosome, position and allele
+ * letter of column i - 1 (col_chrom int32, col_pos uint64, col_allele int32, p - 1 entries are read each); the last column's
+ * label is never printed.  row0 < 0, rows < 0 or row0 + rows > k * p is PG_ERR_INVALID. */
+int pg_kinship_rows_dev(pg_ctx *ctx, int64_t p, int k, int64_t row0, int64_t rows, const double *beta_dev, const double *pval_dev,
+                        const int32_t *col_chrom_dev, const uint64_t *col_pos_dev, const int32_t *col_allele_dev,
+                        const char *chrom_text_dev, const int32_t *chrom_off_dev, int n_chrom, char *text_dev, int64_t cap,
+                        int64_t *bytes);
+int pg_host_kinship_rows(int64_t p, int k, int64_t row0, int64_t rows, const double *beta, const double *pval,
+                         const int32_t *col_chrom, const uint64_t *col_pos, const int32_t *col_allele, const char *chrom_text,
+                         const int32_t *chrom_off, int n_chrom, char *text, int64_t cap, int64_t *bytes, int n_threads);
 
 /* ---------------------------------------------------------------------------------------
  * impute (src/imputation/: filtering_missing.rs, mean_imputation.rs, adaptive_ld_knn_imputation.rs; CLI main.rs:125-142,

@@ -126,6 +126,12 @@ SIGNATURES = {
     "pg_host_pileup_parse": (_i, [_vp, _i64, _vp, _i, _i, _i, _d, _u64, _d, _d, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i]),
     "pg_sync_format_rows_dev": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i64, _pi64]),
     "pg_host_sync_format_rows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i64, _pi64, _i]),
+    "pg_f64_text_dev": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _pi64]),
+    "pg_host_f64_text": (_i, [_vp, _i64, _i, _vp, _i64, _pi64, _i]),
+    "pg_result_rows_dev": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64]),
+    "pg_host_result_rows": (_i, [_i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64, _i]),
+    "pg_kinship_rows_dev": (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64]),
+    "pg_host_kinship_rows": (_i, [_i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64, _i]),
     "pg_sync_parse_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "pg_host_sync_parse": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i]),
     "pg_set_missing_by_depth_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _d]),
@@ -146,7 +152,7 @@ SIGNATURES = {
 KERNEL_IDS = {"kinship": 0, "kinship_reduce": 1, "sweep": 2, "ols_iter": 3, "pearson": 4,
               "chisq": 5, "gp_xxt": 6, "gp_beta": 7, "sweep_finish": 8, "allreduce": 9, "gp_predict": 10, "fisher": 11,
               "gwalpha": 12, "csv": 13, "impute": 14, "impute_links": 15, "impute_walk": 16, "vcf": 17, "sync": 18, "pileup": 19,
-              "syncfmt": 20}
+              "syncfmt": 20, "resultfmt": 21}
 
 
 def load_library():

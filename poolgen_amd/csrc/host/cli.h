@@ -4,6 +4,7 @@
 #include "gpu_mem.h"
 #include "host_util.h"
 #include "rank_gate.h"
+#include "result_writer.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -322,7 +323,7 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
 GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt,
                                                      bool keep_p_minus_1, bool remove_missing, bool with_coverages, Lap &lap);
 std::string ols_with_covariate(Ctx &gpu, GenotypesAndPhenotypes &g, double xxt_eigen_variance_explained,
-                               const std::string &fname_input, const std::string &fname_output, int n_threads, Lap &lap, bool mle);
+                               const std::string &fname_input, const std::string &fname_output, int n_threads, Lap &lap, bool mle, bool gpu_writer = false, int64_t slab_rows = 0);
 std::string sync2csv(Ctx &gpu, const SyncBatch &sb, const Phen &ph, const pg_filter &flt, bool keep_p_minus_1, const std::string &out,
                      int64_t slab_rows, Lap &lap);
 void write_freq_csv(Ctx &gpu, const SyncBatch &sb, const std::vector<std::string> &pool_names, const double *G, int64_t ld, int n, int64_t p,

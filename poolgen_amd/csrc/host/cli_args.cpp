@@ -81,6 +81,17 @@ static const char *USAGE =
     "      --sync-writer <host|gpu>        pileup2sync (with --pileup-parser gpu), vcf2sync: who formats the sync lines: the host's --n-threads\n"
     "                                      threads (the default), or the GPU that parsed the input (the counts then never leave the device,\n"
     "                                      only the text comes back).  The output is the same\n"
+    "      --result-writer <host|gpu>      fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship,\n"
+    "                                      mle_iter_with_kinship: who formats the rows of the result CSV: the host's --n-threads threads (the\n"
+    "                                      default), or the GPU that computed them (the statistics then never leave the device, only the\n"
+    "                                      text comes back).  The GPU prints a number as the reference does (the shortest digits that read\n"
+    "                                      back as the same double); the file is the host writer's byte for byte whenever every printed\n"
+    "                                      |value| is below 2^53, and above that it is the one of the two that matches the reference.  The\n"
+    "                                      kinship analyses take it on one GPU, in the whole-file path and in the streamed one (the\n"
+    "                                      coefficients then stay on the device, 16 bytes each per trait, until the last piece)\n"
+    "      --result-slab-rows <N>          --result-writer gpu, kinship analyses: rows formatted, copied and written per turn; default: as\n"
+    "                                      many as hold 256 MB of text at 128 bytes a row.  The file does not depend on it (the per-locus\n"
+    "                                      analyses format the rows of one piece of the input per turn: --stream-chunk-mb)\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
     "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
     "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
@@ -140,6 +151,8 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--sync-parser") a.sync_parser = val();
         else if (k == "--pileup-parser") a.pileup_parser = val();
         else if (k == "--sync-writer") a.sync_writer = val();
+        else if (k == "--result-writer") a.result_writer = val();
+        else if (k == "--result-slab-rows") a.result_slab_rows = flag_int(val(), k, 1);
         else if (k == "--min-depth-set-to-missing") {
             const std::string t = val();
             if (!parse_f64_strict(t, a.min_depth_set_to_missing)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
@@ -214,6 +227,19 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
         throw std::runtime_error("--sync-writer gpu applies to pileup2sync and vcf2sync, which write a sync file; `" + a.analysis + "` writes none");
     if (a.sync_writer == "gpu" && analysis == Analysis::pileup2sync && a.pileup_parser != "gpu")
         throw std::runtime_error("--sync-writer gpu on pileup2sync needs --pileup-parser gpu: with the host's parser the rows are not on the device");
+    if (a.result_writer != "host" && a.result_writer != "gpu")
+        throw std::runtime_error("Invalid value `" + a.result_writer + "` for --result-writer. Please select: 'host' or 'gpu'");
+    const bool kinship_rows = analysis == Analysis::ols_iter_with_kinship || analysis == Analysis::mle_iter_with_kinship;
+    const bool locus_rows = analysis == Analysis::fisher_exact_test || analysis == Analysis::chisq_test || analysis == Analysis::pearson_corr ||
+                            analysis == Analysis::ols_iter || analysis == Analysis::gwalpha;
+    if ((a.result_writer == "gpu" || a.result_slab_rows > 0) && !kinship_rows && !locus_rows)
+        throw std::runtime_error("--result-writer gpu applies to fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship and "
+                                 "mle_iter_with_kinship, which write result rows; `" + a.analysis + "` writes none");
+    if (a.result_slab_rows > 0 && a.result_writer != "gpu")
+        throw std::runtime_error("--result-slab-rows needs --result-writer gpu: the host writer has no slabs");
+    if (a.result_writer == "gpu" && kinship_rows && a.n_gpus > 1)
+        throw std::runtime_error("--result-writer gpu on `" + a.analysis + "` takes one GPU: with --n-gpus " + std::to_string(a.n_gpus) +
+                                 " the rows of one trait would interleave the ranks' coefficients; run it without --n-gpus, or with --result-writer host");
     gwalpha_fmt = a.phen_format == "gwalpha_fmt";
     if (analysis == Analysis::gwalpha && !gwalpha_fmt)
         throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "

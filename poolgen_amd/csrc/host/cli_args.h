@@ -29,6 +29,8 @@ struct Args {
     int64_t csv_slab_rows = 0; // sync2csv, impute: rows formatted per call (0 = as many as CSV_SLAB_BYTES of text hold)
     // impute (main.rs:125-142)
     std::string pileup_parser = "host"; // who parses a *.pileup / *.mpileup input: the host's threads, or the GPU (the counts come back)
+    std::string result_writer = "host"; // who formats the result rows of the GWAS analyses: the host's threads, or the GPU that computed them
+    int64_t result_slab_rows = 0;       // --result-writer gpu, kinship analyses: rows formatted, copied and written per turn (0 = a byte budget's worth)
     std::string sync_writer = "host"; // who formats the sync lines pileup2sync / vcf2sync write: the host's threads, or the GPU that parsed the input
     std::string sync_parser = "host"; // who parses a *.sync input: the host's threads, or the GPU (the counts then stay on the device)
     std::string imputation_method = "aLD-kNNi";

@@ -1,5 +1,7 @@
 // cli_matrix.cpp -- the analyses' common start, the matrix loaded into HBM, and the kinship GWAS on it.
 #include "cli.h"
+#include <cstring>
+#include <map>
 #include <numeric>
 
 // FileSyncPhen::into_genotypes_and_phenotypes (base/sync.rs:1106-1179) = load (:1044-1104: filter + frequencies per locus,
@@ -66,15 +68,15 @@ GenotypesAndPhenotypes into_genotypes_and_phenotypes(Ctx &gpu, const SyncBatch &
 // not reproduced).
 std::string ols_with_covariate(Ctx &gpu, GenotypesAndPhenotypes &g, double xxt_eigen_variance_explained,
                                const std::string &fname_input, const std::string &fname_output, int n_threads, Lap &lap,
-                               bool mle) {
+                               bool mle, bool gpu_writer, int64_t slab_rows) {
     const int64_t p = g.p;
     const int k = g.k;
     if (!fname_output.empty()) probe_output(fname_output); // ols.rs:285
     std::vector<double> beta((size_t)p * k), pval((size_t)p * k);
     int m = 0;
     const size_t cnt = (size_t)p * k;
+    DeviceBuf<double> out_dev(sizeof(double) * 3 * cnt, "device memory for the results");
     {
-        DeviceBuf<double> out_dev(sizeof(double) * 3 * cnt, "device memory for the results");
         const double *G = g.intercept_and_allele_frequencies.get();
         if (mle)
             gpu.ok(pg_mle_kinship_dev(gpu.c, G, p, g.n, g.ld, g.phenotypes.data(), k, xxt_eigen_variance_explained, -1, &m, nullptr, out_dev.get(),
@@ -83,14 +85,48 @@ std::string ols_with_covariate(Ctx &gpu, GenotypesAndPhenotypes &g, double xxt_e
             gpu.ok(pg_ols_kinship_dev(gpu.c, G, p, g.n, g.ld, g.phenotypes.data(), k, xxt_eigen_variance_explained, -1, &m, nullptr, out_dev.get(),
                                       out_dev.get() + cnt, out_dev.get() + 2 * cnt), "ols_iter_with_kinship");
         gpu.ok(pg_synchronize(gpu.c), "ols_iter_with_kinship");
-        hip_ok(hipMemcpy(beta.data(), out_dev.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
-        hip_ok(hipMemcpy(pval.data(), out_dev.get() + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+        if (!gpu_writer) {
+            hip_ok(hipMemcpy(beta.data(), out_dev.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+            hip_ok(hipMemcpy(pval.data(), out_dev.get() + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+        }
     }
-    lap("kinship + fits + D2H");
+    if (!gpu_writer) out_dev.reset();
+    lap(gpu_writer ? "kinship + fits" : "kinship + fits + D2H");
     std::string out = fname_output;
     if (out.empty()) // ols.rs:393-398
         out = basename_no_ext(fname_input) + (mle ? "-mle_iterative_xxt_" : "-ols_iterative_xxt_") + std::to_string(m + 1) + "_eigens-" +
               unix_time_string() + ".csv"; // ols.rs:393-398, mle.rs:423-427
+    if (gpu_writer) { // --result-writer gpu: beta and pval stay on the device; their rows are formatted there, a slab of rows per turn
+        std::vector<std::string> names;
+        std::map<std::string, int32_t> id_of;
+        std::vector<int32_t> col_chrom(p), col_allele(p);
+        std::vector<uint64_t> col_pos(p);
+        for (int64_t c = 0; c < p; ++c) { // column c carries entry c + 1 of the (1+p)-long label vectors; the shift is the formatter's
+            const auto it = id_of.emplace(g.chromosome[c + 1], (int32_t)names.size());
+            if (it.second) names.push_back(g.chromosome[c + 1]);
+            col_chrom[c] = it.first->second;
+            col_pos[c] = g.position[c + 1];
+            const char *at = g.allele[c + 1].size() == 1 ? std::strchr(ALLELES, g.allele[c + 1][0]) : nullptr;
+            if (!at || !*at) throw std::runtime_error("--result-writer gpu: the allele label `" + g.allele[c + 1] + "` is none of " + ALLELES);
+            col_allele[c] = (int32_t)(at - ALLELES);
+        }
+        DeviceResultWriter writer;
+        writer.set_column_labels(col_chrom, col_pos, col_allele, names);
+        FILE *fo = create_new(out);
+        try {
+            fputs("#chr,pos,alleles,phenotype,statistic,pvalue\n", fo); // ols.rs:409
+            const int64_t total = (int64_t)k * p, step = result_slab_rows((int)std::min<int64_t>(slab_rows, INT32_MAX));
+            for (int64_t row0 = 0; row0 < total; row0 += step)
+                writer.kinship_rows(gpu.c, p, k, row0, std::min(step, total - row0), out_dev.get(), out_dev.get() + 2 * cnt, fo);
+            if (fclose(fo) != 0) { fo = nullptr; throw std::runtime_error("write error on " + out); }
+        } catch (...) { // a failure on the way leaves no file
+            if (fo) fclose(fo);
+            ::unlink(out.c_str());
+            throw;
+        }
+        lap("format (gpu) + write CSV");
+        return out;
+    }
     write_kinship_csv(out, p, k, beta, pval, n_threads, [&](int64_t i, std::string &text) {
         // the reference labels coefficient i with entry i of the (1+p)-long label vectors, i.e.
         // shifted by the intercept entry (ols.rs:421-425) -- reproduced as is

@@ -150,7 +150,8 @@ static void kin_load_pieces(KinRank &K, RankGate &gate, const Args &a, const Phe
 // ---- phase B, per rank: all-reduce of the kinship sums, the n x n step (replicated), the rank's sweeps ---------
 // S_host: the ranks' sums added on the host (no communicator); Y: the kept pools' phenotypes; beta, pval: p x k, a rank fills its columns
 static void kin_fit_pieces(KinRank &K, RankGate &gate, const RankSetup &rs, const std::vector<double> &S_host, int64_t p, int n2, int64_t ld,
-                           const std::vector<double> &Y, int k, double xxt, std::vector<double> &beta, std::vector<double> &pval) {
+                           const std::vector<double> &Y, int k, double xxt, std::vector<double> &beta, std::vector<double> &pval,
+                           double *res_dev = nullptr) { // --result-writer gpu (one rank): beta at res_dev, pval p * k further on; nothing copied down
     Ctx &gpu = *K.gpu;
     gate.pass([&] {
         hip_ok(hipSetDevice(K.device), "hipSetDevice");
@@ -164,8 +165,13 @@ static void kin_fit_pieces(KinRank &K, RankGate &gate, const RankSetup &rs, cons
         DeviceBuf<double> out_dev(sizeof(double) * 3 * cnt, "device memory for the results");
         gpu.ok(pg_ols_sweep_dev(gpu.c, K.Gs[c].get(), K.ps[c], n2, ld, out_dev.get(), out_dev.get() + cnt, out_dev.get() + 2 * cnt), "ols_iter_with_kinship");
         gpu.ok(pg_synchronize(gpu.c), "ols_iter_with_kinship");
-        hip_ok(hipMemcpy(beta.data() + (size_t)off * k, out_dev.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
-        hip_ok(hipMemcpy(pval.data() + (size_t)off * k, out_dev.get() + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+        if (res_dev) { // the rank's results stay on the device, 16 bytes per coefficient and trait
+            hip_ok(hipMemcpy(res_dev + (size_t)off * k, out_dev.get(), sizeof(double) * cnt, hipMemcpyDeviceToDevice), "keeping the results");
+            hip_ok(hipMemcpy(res_dev + (size_t)(p + off) * k, out_dev.get() + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToDevice), "keeping the results");
+        } else {
+            hip_ok(hipMemcpy(beta.data() + (size_t)off * k, out_dev.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+            hip_ok(hipMemcpy(pval.data() + (size_t)off * k, out_dev.get() + 2 * cnt, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H results");
+        }
         K.Gs[c].reset(); // a piece leaves HBM right after its sweep
         off += K.ps[c];
     }
@@ -220,15 +226,44 @@ static int kinship_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, 
         for (const KinRank &K : ranks)
             for (size_t i = 0; i < S_host.size(); ++i) S_host[i] += K.S_total[i];
     }
-    std::vector<double> beta((size_t)p * k), pval((size_t)p * k);
-    run_ranks(R, [&](int r) { kin_fit_pieces(ranks[r], gate, rs, S_host, p, n2, ld, Y, k, a.xxt, beta, pval); });
+    const bool gpu_writer = a.result_writer == "gpu"; // one rank: checked with the flags
+    std::vector<double> beta(gpu_writer ? 0 : (size_t)p * k), pval(beta.size());
+    DeviceBuf<double> res_dev;
+    if (gpu_writer) {
+        hip_ok(hipSetDevice(ranks[0].device), "hipSetDevice");
+        res_dev.reset(sizeof(double) * 2 * (size_t)p * k, "device memory for the results");
+    }
+    run_ranks(R, [&](int r) { kin_fit_pieces(ranks[r], gate, rs, S_host, p, n2, ld, Y, k, a.xxt, beta, pval, res_dev.get()); });
     const int m = ranks[0].m;
     for (const KinRank &K : ranks)
         if (K.m != m) throw std::runtime_error("internal error: the ranks disagree on n_eigenvecs");
-    lap("all-reduce + eigen rule + fits + D2H");
+    lap(gpu_writer ? "all-reduce + eigen rule + fits" : "all-reduce + eigen rule + fits + D2H");
     std::string out = a.output;
     if (out.empty()) // ols.rs:393-398
         out = basename_no_ext(a.fname) + "-ols_iterative_xxt_" + std::to_string(m + 1) + "_eigens-" + unix_time_string() + ".csv";
+    if (gpu_writer) { // after the last piece: the rows in their trait-major order, formatted on the device a slab of rows per turn
+        const KinRank &K = ranks[0];
+        std::vector<int32_t> col_allele(K.lab_al.size());
+        for (size_t c = 0; c < K.lab_al.size(); ++c) col_allele[c] = (int32_t)(std::strchr(ALLELES, K.lab_al[c]) - ALLELES);
+        { // (a scope of its own: done_ok below does not return, and the writer reports its timing when it goes)
+        DeviceResultWriter writer;
+        writer.set_column_labels(K.lab_chr, K.lab_pos, col_allele, K.chrom_names);
+        FILE *fo = create_new(out);
+        try {
+            fputs("#chr,pos,alleles,phenotype,statistic,pvalue\n", fo); // ols.rs:409
+            const int64_t total = (int64_t)k * p, step = result_slab_rows((int)std::min<int64_t>(a.result_slab_rows, INT32_MAX));
+            for (int64_t row0 = 0; row0 < total; row0 += step)
+                writer.kinship_rows(K.gpu->c, p, k, row0, std::min(step, total - row0), res_dev.get(), res_dev.get() + (size_t)p * k, fo);
+            if (fclose(fo) != 0) { fo = nullptr; throw std::runtime_error("write error on " + out); }
+        } catch (...) { // a failure on the way leaves no file
+            if (fo) fclose(fo);
+            ::unlink(out.c_str());
+            throw;
+        }
+        }
+        lap("format (gpu) + write CSV");
+        return done_ok(out);
+    }
     // label of global column q: the rank whose range holds it
     std::vector<int64_t> starts;
     for (const KinRank &K : ranks) starts.push_back(K.col0);
@@ -292,6 +327,9 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
     const int n2 = (int)keep.size();
     const bool subset = n2 != n;
     const bool tables = counts_only(op); // chisq_test, fisher_exact_test
+    const bool gpu_writer = a.result_writer == "gpu";
+    const int result_op = op == Analysis::fisher_exact_test ? PG_RESULT_FISHER : op == Analysis::chisq_test ? PG_RESULT_CHISQ
+                          : gwa ? PG_RESULT_GWALPHA : op == Analysis::pearson_corr ? PG_RESULT_PEARSON : PG_RESULT_OLS_ITER;
     const char *header = tables ? "#chr,pos,alleles,statistic,pvalue\n"                    // sync.rs:766
                                    : "#chr,pos,alleles,freq,phenotype,statistic,pvalue\n"; // sync.rs:950
     // One rank = one contiguous range of pieces, one GPU, its own pinned buffers and parser threads, and -- when there are
@@ -322,6 +360,7 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
         std::vector<int32_t> n_out, ids;
         std::vector<double> mfq, stat, pv;
         const size_t per_stat = tables ? 1 : (size_t)PG_MAX_OUT * k;
+        DeviceResultWriter writer; // (its timing line, under PGH_TIMING, comes when the rank is done)
         while (pieces.more()) {
             SyncBatch sb = pieces.next();
             if (sb.L == 0) continue;
@@ -360,6 +399,17 @@ int run_batch_streamed(const Args &a, const Phen &ph, Ctx &gpu0, Lap &lap, Analy
             else
                 gpu.ok(pg_ols_iter_batch_dev(gpu.c, counts, L, n2, ps.data(), &flt, Y.data(), k, n_out_dev.get(), ids_dev.get(), mf_dev.get(),
                                              stat_dev.get(), pv_dev.get()), "ols_iter");
+            if (gpu_writer) { // --result-writer gpu: the piece's results stay on the device, only their text comes back
+                if (!fo) {
+                    fo = create_new(part[r]);
+                    created[r] = 1;
+                    if (R == 1) fputs(header, fo);
+                }
+                writer.set_locus_labels(sb.chrom_id, sb.pos, sb.chrom_names, L);
+                writer.locus_rows(gpu.c, result_op, L, k, n_out_dev.get(), ids_dev.get(), tables ? nullptr : mf_dev.get(), stat_dev.get(),
+                                  gwa ? nullptr : pv_dev.get(), fo);
+                continue;
+            }
             n_out.resize(L); ids.resize((size_t)L * PG_MAX_OUT); mfq.resize((size_t)L * PG_MAX_OUT);
             stat.resize((size_t)L * per_stat); pv.resize((size_t)L * per_stat);
             hip_ok(hipMemcpy(n_out.data(), n_out_dev.get(), sizeof(int32_t) * L, hipMemcpyDeviceToHost), "D2H results");

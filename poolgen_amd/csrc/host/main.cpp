@@ -121,7 +121,8 @@ static int run(int argc, char **argv) {
         lap("cross-validation");
         return done_ok(out);
     }
-    const std::string out = ols_with_covariate(gpu, g, a.xxt, a.fname, a.output, a.n_threads, lap, /*mle=*/analysis == Analysis::mle_iter_with_kinship);
+    const std::string out = ols_with_covariate(gpu, g, a.xxt, a.fname, a.output, a.n_threads, lap, /*mle=*/analysis == Analysis::mle_iter_with_kinship,
+                                               a.result_writer == "gpu", a.result_slab_rows);
     return done_ok(out);
 }
 

@@ -266,6 +266,72 @@ def sync_format_host(counts, pos, ref, line_off, chrom_len, slab, n_threads=1):
     return out[:need.value].tobytes()
 
 
+RESULT_OPS = {"fisher_exact_test": 0, "chisq_test": 1, "gwalpha": 2, "pearson_corr": 3, "ols_iter": 4}   # enum pg_result_op
+
+
+def name_table(names):
+    """Chromosome names -> (one uint8 array of their bytes, int32 offsets: len(names) + 1), the form the row formatters take."""
+    raw = [n if isinstance(n, (bytes, bytearray)) else str(n).encode() for n in names]
+    off = np.zeros(len(raw) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(b) for b in raw], dtype=np.int64)
+    return np.frombuffer(b"".join(raw), dtype=np.uint8).copy(), off
+
+
+def _host_text_call(fn, what, args, n_threads):
+    """size query, then the text: the two-call pattern of the host twins -> bytes"""
+    need = C.c_int64()
+    rc = fn(*args, None, 0, C.byref(need), int(n_threads))
+    if rc != 0 and need.value == 0:
+        raise NativeError(f"{what} failed ({rc}): bad arguments, a label out of range or a row above the row limit")
+    out = np.empty(max(need.value, 1), dtype=np.uint8)
+    if need.value:
+        rc = fn(*args, out.ctypes.data, need.value, C.byref(need), int(n_threads))
+        if rc != 0:
+            raise NativeError(f"{what} failed ({rc})")
+    return out[:need.value].tobytes()
+
+
+def f64_text_host(x, n_digits: int = -1, n_threads: int = 1) -> bytes:
+    """Engine.f64_text on the host (pg_host_f64_text: plain C++, no GPU): one line per value, Rust's `{}` of the double for
+    n_digits < 0, parse_f64_roundup_and_own(x, n_digits) otherwise."""
+    a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    return _host_text_call(load_library().pg_host_f64_text, "pg_host_f64_text", [a.ctypes.data if a.size else None, a.size, int(n_digits)], n_threads)
+
+
+def _u64(a):
+    a = np.asarray(a)
+    return np.ascontiguousarray(a).view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def result_rows_host(op, n_out, allele_ids, mean_freq, stat, pval, locus_chrom, locus_pos, chrom_names, k: int = 1, n_threads: int = 1) -> bytes:
+    """Engine.result_rows on the host (pg_host_result_rows): the slot-major outputs of a per-locus operator as NumPy arrays,
+    chromosome id and position per locus and the list of chromosome names, to the bytes of the analysis' CSV rows."""
+    no = np.ascontiguousarray(n_out, dtype=np.int32); L = no.size
+    ids = np.ascontiguousarray(allele_ids, dtype=np.int32)
+    mf = None if mean_freq is None else np.ascontiguousarray(mean_freq, dtype=np.float64)
+    st = np.ascontiguousarray(stat, dtype=np.float64)
+    pv = None if pval is None else np.ascontiguousarray(pval, dtype=np.float64)
+    ch = np.ascontiguousarray(locus_chrom, dtype=np.int32); po = _u64(locus_pos)
+    text, off = name_table(chrom_names)
+    args = [RESULT_OPS[op] if isinstance(op, str) else int(op), L, int(k), no.ctypes.data, ids.ctypes.data, None if mf is None else mf.ctypes.data,
+            st.ctypes.data, None if pv is None else pv.ctypes.data, ch.ctypes.data, po.ctypes.data, text.ctypes.data if text.size else None,
+            off.ctypes.data, len(off) - 1]
+    return _host_text_call(load_library().pg_host_result_rows, "pg_host_result_rows", args, n_threads)
+
+
+def kinship_rows_host(beta, pval, col_chrom, col_pos, col_allele, chrom_names, row0: int = 0, rows: int | None = None, n_threads: int = 1) -> bytes:
+    """Engine.kinship_rows on the host (pg_host_kinship_rows): beta and pval as p x k arrays, the labels of the matrix'
+    columns, to rows [row0, row0 + rows) of the kinship analyses' CSV (trait-major, the reference's label shift kept)."""
+    b = np.ascontiguousarray(beta, dtype=np.float64); pv = np.ascontiguousarray(pval, dtype=np.float64)
+    b = b.reshape(b.shape[0], -1); p, k = b.shape
+    ch = np.ascontiguousarray(col_chrom, dtype=np.int32); po = _u64(col_pos); al = np.ascontiguousarray(col_allele, dtype=np.int32)
+    text, off = name_table(chrom_names)
+    rows = p * k - row0 if rows is None else rows
+    args = [p, k, int(row0), int(rows), b.ctypes.data, pv.ctypes.data, ch.ctypes.data, po.ctypes.data, al.ctypes.data,
+            text.ctypes.data if text.size else None, off.ctypes.data, len(off) - 1]
+    return _host_text_call(load_library().pg_host_kinship_rows, "pg_host_kinship_rows", args, n_threads)
+
+
 class Engine:
     def __init__(self, device: int | None = None, use_torch_stream: bool = True):
         self._lib = load_library()
@@ -802,6 +868,59 @@ class Engine:
         if need.value:
             self._check(self._lib.pg_sync_format_rows_dev(*args, out.data_ptr(), need.value, C.byref(need)), "pg_sync_format_rows_dev")
         return out
+
+    # ---- the result writer (pg_resultfmt.hip) ----------------------------------------------------
+    def _text_call(self, fn, what, args, out):
+        """size query, then the text (or one call into `out`) -> a uint8 tensor on the device"""
+        need = C.c_int64()
+        if out is not None:
+            self._check(fn(*args, self._dev(out, torch.uint8), out.numel(), C.byref(need)), what)
+            return out[:need.value]
+        rc = fn(*args, None, 0, C.byref(need))
+        if rc != 0 and need.value == 0:
+            self._check(rc, what)
+        out = torch.empty(need.value, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if need.value:
+            self._check(fn(*args, out.data_ptr(), need.value, C.byref(need)), what)
+        return out
+
+    def _names_dev(self, chrom_names):
+        dev = torch.device("cuda", self.device)
+        text, off = name_table(chrom_names)
+        return torch.from_numpy(text).to(dev), torch.from_numpy(off).to(dev)
+
+    def f64_text(self, x: torch.Tensor, n_digits: int = -1, out: torch.Tensor | None = None) -> torch.Tensor:
+        """One line per value of `x` (float64, on the device), formatted on the GPU: Rust's `{}` of the double -- the shortest
+        digits that round-trip, fixed notation -- for n_digits < 0, parse_f64_roundup_and_own(x, n_digits) otherwise.  Returns a
+        uint8 tensor on the device; with `out` one call formats into it."""
+        x = x.reshape(-1)
+        args = [self._ctx, self._dev(x, torch.float64) if x.numel() else None, x.numel(), int(n_digits)]
+        return self._text_call(self._lib.pg_f64_text_dev, "pg_f64_text_dev", args, out)
+
+    def result_rows(self, op, n_out, allele_ids, mean_freq, stat, pval, locus_chrom, locus_pos, chrom_names, k: int = 1,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+        """The CSV rows of a per-locus analysis (`op`: fisher_exact_test, chisq_test, gwalpha, pearson_corr, ols_iter) from the
+        slot-major tensors its batch operator left on the device, formatted on the GPU.  locus_chrom (int32) and locus_pos
+        (int64) are per locus, chrom_names the list of names.  Equal to the host writer's bytes whenever every printed
+        |value| < 2^53; above that it prints what the reference prints (see include/poolgen_hip.h)."""
+        names, off = self._names_dev(chrom_names)
+        args = [self._ctx, RESULT_OPS[op] if isinstance(op, str) else int(op), n_out.numel(), int(k), self._dev(n_out, torch.int32),
+                self._dev(allele_ids, torch.int32), None if mean_freq is None else self._dev(mean_freq, torch.float64),
+                self._dev(stat, torch.float64), None if pval is None else self._dev(pval, torch.float64), self._dev(locus_chrom, torch.int32),
+                self._dev(locus_pos, torch.int64), names.data_ptr() if names.numel() else None, off.data_ptr(), off.numel() - 1]
+        return self._text_call(self._lib.pg_result_rows_dev, "pg_result_rows_dev", args, out)
+
+    def kinship_rows(self, beta, pval, col_chrom, col_pos, col_allele, chrom_names, row0: int = 0, rows: int | None = None,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+        """Rows [row0, row0 + rows) of the CSV of ols_iter_with_kinship / mle_iter_with_kinship from beta and pval (p x k, on the
+        device) and the labels of the matrix' columns, formatted on the GPU: trait-major, the reference's label shift kept."""
+        p = int(beta.shape[0]); k = int(beta.numel() // max(p, 1))
+        names, off = self._names_dev(chrom_names)
+        rows = p * k - row0 if rows is None else rows
+        args = [self._ctx, p, k, int(row0), int(rows), self._dev(beta, torch.float64), self._dev(pval, torch.float64),
+                self._dev(col_chrom, torch.int32), self._dev(col_pos, torch.int64), self._dev(col_allele, torch.int32),
+                names.data_ptr() if names.numel() else None, off.data_ptr(), off.numel() - 1]
+        return self._text_call(self._lib.pg_kinship_rows_dev, "pg_kinship_rows_dev", args, out)
 
     # ---- imputation (src/imputation/) ------------------------------------------------------------
     def _impute_args(self, M, locus_col, n):
