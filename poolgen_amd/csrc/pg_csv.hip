@@ -5,11 +5,11 @@
 // (pg_csv_cell.h: parse_f64_roundup_and_own(x, 6) restricted to frequencies).  Three steps on the context's stream:
 //   measure  k_csv_measure: the byte length of every row (int32), a flag for cells that are no frequency and for labels out
 //            of range;
-//   scan     k_csv_count (exclusive scan of 256 lengths per workgroup, the longest row) + k_csv_scan (64-bit exclusive scan of
-//            the workgroups' sums, 1024 per round): a row's offset is blockoff[r >> 8] + local[r];
+//   scan     PgLengthScan (pg_text_steps.h): k_scan_lengths (exclusive scan of 256 lengths per workgroup, the longest row) +
+//            k_scan_blocks (64-bit exclusive scan of the workgroups' sums, 1024 per round): a row's offset is scan_off(r);
 //   emit     k_csv_emit<CSV_STAGED>: a workgroup takes `rpb` consecutive rows -- one contiguous byte range of the file -- formats them
-//            into an LDS tile laid out like the 16-byte words of the output, then copies the tile out: whole words by 16-byte
-//            stores (a lane a word, consecutive lanes consecutive words), the ragged head and tail by byte stores.  Two
+//            into an LDS tile laid out like the 16-byte words of the output, then copies the tile out (tile_flush): whole words by
+//            16-byte stores (a lane a word, consecutive lanes consecutive words), the ragged head and tail by byte stores.  Two
 //            workgroups meet inside a word only with byte stores; nothing is read back; nothing at or past the total is written.
 //            With fewer rows than waves in a tile (rows above 4 KB) the whole workgroup formats row after row together.
 //            k_csv_emit<CSV_DIRECT>: a row longer than the tile goes from registers to the output by byte stores, a wave per row.
@@ -18,6 +18,7 @@
 // group's running sum of (length + 1), an inclusive scan by lane shuffles.  A cell's text stays in a 64-bit register and
 // leaves by (predicated) byte stores at constant shifts: no array, no scratch.
 #include "pg_common.h"
+#include "pg_text_steps.h"
 #include "pg_csv_cell.h"
 
 namespace {
@@ -26,12 +27,6 @@ constexpr int CSV_THREADS = 256;
 constexpr int CSV_TILE = 16384;       // bytes of text a workgroup stages (plus up to 15 in front of them: the word it starts in)
 constexpr int CSV_MAX_ROW = 1 << 22;  // bytes: 256 rows of this length still sum in an int32
 constexpr int CSV_BAD_CELL = 1, CSV_BAD_LABEL = 2, CSV_BAD_LONG = 4;
-
-struct CsvCtl { // the scan's results, read back by the host
-    int64_t total;
-    int32_t max_row;
-    int32_t bad;
-};
 
 struct CsvRows { // what a row is made of (the pointers of the call, already moved to its first row)
     const double *G;
@@ -45,13 +40,6 @@ struct CsvRows { // what a row is made of (the pointers of the call, already mov
     const int32_t *chrom_off;
     int n_chrom;
 };
-
-// lanes per row: the smallest power of two that holds n, at most a wave
-int csv_lpr_shift(int n) {
-    int s = 0;
-    while (s < 6 && (1 << s) < n) ++s;
-    return s;
-}
 
 struct CsvPrefix {
     int name0, name_len, nd, al;
@@ -75,7 +63,7 @@ __device__ __forceinline__ CsvPrefix csv_prefix(const CsvRows &R, int64_t r) {
 
 // ---- measure -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CSV_THREADS) void k_csv_measure(const CsvRows R, int64_t rows, int lpr_shift, int32_t *__restrict__ rowlen,
-                                                             CsvCtl *__restrict__ ctl) {
+                                                             PgScanCtl *__restrict__ ctl) {
     const int lpr = 1 << lpr_shift;
     const int64_t gid = (int64_t)blockIdx.x * CSV_THREADS + threadIdx.x;
     const int64_t r = gid >> lpr_shift;
@@ -98,58 +86,6 @@ __global__ __launch_bounds__(CSV_THREADS) void k_csv_measure(const CsvRows R, in
         rowlen[r] = (int32_t)len;
     }
     if (bad) atomicOr(&ctl->bad, bad);
-}
-
-// ---- scan: the block-scan pattern of the loader's k_load_count / k_load_scan, in a copy of its own --------------------------
-__global__ __launch_bounds__(256) void k_csv_count(int32_t *__restrict__ local, int64_t rows, int64_t *__restrict__ blocksum,
-                                                   CsvCtl *__restrict__ ctl) {
-    __shared__ int sc[256];
-    __shared__ int smax[256];
-    const int tid = threadIdx.x;
-    const int64_t r = (int64_t)blockIdx.x * 256 + tid;
-    const int c = r < rows ? local[r] : 0; // in: the row's length; out (same element, same thread): its offset inside the block
-    sc[tid] = c;
-    smax[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const int v = tid >= d ? sc[tid - d] : 0;
-        const int m = tid >= d ? smax[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        smax[tid] = max(smax[tid], m);
-        __syncthreads();
-    }
-    if (r < rows) local[r] = sc[tid] - c;
-    if (tid == 255) {
-        blocksum[blockIdx.x] = sc[255];
-        atomicMax(&ctl->max_row, smax[255]);
-    }
-}
-
-__global__ __launch_bounds__(1024) void k_csv_scan(const int64_t *__restrict__ blocksum, int64_t nb, int64_t *__restrict__ blockoff,
-                                                   CsvCtl *__restrict__ ctl) {
-    __shared__ int64_t sc[1024];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += 1024) {
-        const int64_t i = base + tid;
-        const int64_t c = i < nb ? blocksum[i] : 0;
-        sc[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const int64_t v = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += v;
-            __syncthreads();
-        }
-        if (i < nb) blockoff[i] = carry + sc[tid] - c;
-        __syncthreads();
-        if (tid == 1023) carry += sc[1023];
-        __syncthreads();
-    }
-    if (tid == 0) ctl->total = carry;
 }
 
 // ---- emit --------------------------------------------------------------------------------------------------------------
@@ -242,53 +178,41 @@ __device__ __forceinline__ void csv_format_row_wg(const CsvRows &R, int64_t r, i
     }
 }
 
-__device__ __forceinline__ int64_t csv_row_off(const int32_t *__restrict__ local, const int64_t *__restrict__ blockoff, const CsvCtl *ctl,
-                                               int64_t r, int64_t rows) {
-    return r < rows ? blockoff[r >> 8] + local[r] : ctl->total;
-}
-
 enum { CSV_STAGED = 0, CSV_STAGED_WG = 1, CSV_DIRECT = 2 }; // how k_csv_emit takes its rows (the dispatch rules: pg_csv_freq_rows_dev)
 
 template <int MODE>
 __global__ __launch_bounds__(CSV_THREADS) void k_csv_emit(const CsvRows R, int64_t rows, int lpr_shift, int rpb,
                                                           const int32_t *__restrict__ local, const int64_t *__restrict__ blockoff,
-                                                          const CsvCtl *__restrict__ ctl, unsigned char *__restrict__ text) {
+                                                          const PgScanCtl *__restrict__ ctl, unsigned char *__restrict__ text) {
     const int tid = threadIdx.x;
     if (MODE == CSV_DIRECT) { // a wave per row, straight to the output
         const int64_t r = (int64_t)blockIdx.x * (CSV_THREADS / 64) + (tid >> 6);
         const bool active = r < rows;
-        csv_format_row(R, r, active, tid & 63, 64, text + (active ? csv_row_off(local, blockoff, ctl, r, rows) : 0));
+        csv_format_row(R, r, active, tid & 63, 64, text + (active ? scan_off(local, blockoff, ctl, r, rows) : 0));
         return;
     }
     __shared__ __attribute__((aligned(16))) unsigned char tile[CSV_TILE + 16];
     const int lpr = 1 << lpr_shift, ng = CSV_THREADS >> lpr_shift;
     const int g = tid >> lpr_shift, gl = tid & (lpr - 1);
     const int64_t r_lo = (int64_t)blockIdx.x * rpb, r_hi = r_lo + rpb < rows ? r_lo + rpb : rows;
-    const int64_t B = csv_row_off(local, blockoff, ctl, r_lo, rows), E = csv_row_off(local, blockoff, ctl, r_hi, rows);
+    const int64_t B = scan_off(local, blockoff, ctl, r_lo, rows), E = scan_off(local, blockoff, ctl, r_hi, rows);
     const int head = (int)((reinterpret_cast<uintptr_t>(text) + (uint64_t)B) & 15); // tile[head + i] is byte B + i of the output
     if (MODE == CSV_STAGED_WG) { // fewer rows than waves: the workgroup formats row after row together
         __shared__ int wsum[2][CSV_THREADS / 64];
         for (int64_t r = r_lo; r < r_hi; ++r) {
-            csv_format_row_wg(R, r, tid, tile + head + (int)(csv_row_off(local, blockoff, ctl, r, rows) - B), wsum);
+            csv_format_row_wg(R, r, tid, tile + head + (int)(scan_off(local, blockoff, ctl, r, rows) - B), wsum);
             __syncthreads(); // (the next row starts on set 0 of wsum again)
         }
     } else
     for (int64_t r0 = r_lo; r0 < r_hi; r0 += ng) {                                  // uniform trip count
         const int64_t r = r0 + g;
         const bool active = r < r_hi;
-        const int at = active ? (int)(csv_row_off(local, blockoff, ctl, r, rows) - B) : 0;
+        const int at = active ? (int)(scan_off(local, blockoff, ctl, r, rows) - B) : 0;
         csv_format_row(R, r, active, gl, lpr, tile + head + at);
     }
     __syncthreads();
     const int nbytes = (int)(E - B);                                  // <= CSV_TILE: rpb rows of at most the longest row's length
-    const int h = min(nbytes, (16 - head) & 15);                      // bytes in front of the first whole word
-    const int body = (nbytes - h) & ~15;                              // whole 16-byte words
-    unsigned char *out = text + B;
-    if (tid < h) out[tid] = tile[head + tid];
-    for (int i = tid * 16; i < body; i += CSV_THREADS * 16)           // head + h is 0 or 16 whenever body > 0
-        *reinterpret_cast<uint4 *>(out + h + i) = *reinterpret_cast<const uint4 *>(tile + head + h + i);
-    const int tail = nbytes - h - body;                               // < 16
-    if (tid < tail) out[h + body + tid] = tile[head + h + body + tid];
+    tile_flush(tile, head, text + B, nbytes, tid, CSV_THREADS);
 }
 
 } // namespace
@@ -309,33 +233,20 @@ extern "C" int pg_csv_freq_rows_dev(pg_ctx *ctx, const double *G_dev, int64_t ld
     PG_CHECK(ctx, G_dev && col_locus_dev && col_allele_dev && locus_chrom_dev && locus_pos_dev && chrom_text_dev && chrom_off_dev,
              "csv_freq_rows: null pointer");
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t nb = (rows + 255) / 256;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t off = 0;
-    const size_t o_local = off; off = up16(off + sizeof(int32_t) * (size_t)rows);
-    const size_t o_bsum = off; off = up16(off + 8 * (size_t)nb);
-    const size_t o_boff = off; off = up16(off + 8 * (size_t)nb);
-    const size_t o_ctl = off; off = up16(off + sizeof(CsvCtl));
-    const int rc = pg_ws_reserve(ctx, off);
+    PgLengthScan S;
+    int rc = S.prepare(ctx, rows);
     if (rc) return rc;
-    char *ws = static_cast<char *>(ctx->ws.get());
-    int32_t *local = reinterpret_cast<int32_t *>(ws + o_local);
-    int64_t *bsum = reinterpret_cast<int64_t *>(ws + o_bsum), *boff = reinterpret_cast<int64_t *>(ws + o_boff);
-    CsvCtl *ctl = reinterpret_cast<CsvCtl *>(ws + o_ctl);
     const CsvRows R{G_dev + row0 * ld, ld, n, col_locus_dev + row0, col_allele_dev + row0, locus_chrom_dev, locus_pos_dev,
                     reinterpret_cast<const unsigned char *>(chrom_text_dev), chrom_off_dev, n_chrom};
-    const int lpr_shift = csv_lpr_shift(n);
-    PG_HIP(ctx, hipMemsetAsync(ctl, 0, sizeof(CsvCtl), ctx->stream));
+    const int lpr_shift = pg_lpr_shift(n, 0); // so that n = 5 has 8 rows in a wave and n = 200 one row across it
     const int64_t measure_blocks = ((rows << lpr_shift) + CSV_THREADS - 1) / CSV_THREADS;
     pg_prof_begin(ctx, PG_K_CSV);
-    hipLaunchKernelGGL(k_csv_measure, dim3((unsigned)measure_blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, lpr_shift, local, ctl);
-    hipLaunchKernelGGL(k_csv_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, local, rows, bsum, ctl);
-    hipLaunchKernelGGL(k_csv_scan, dim3(1), dim3(1024), 0, ctx->stream, bsum, nb, boff, ctl);
+    hipLaunchKernelGGL(k_csv_measure, dim3((unsigned)measure_blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, lpr_shift, S.local, S.ctl);
+    S.scan(ctx);
     pg_prof_end(ctx);
-    PG_HIP(ctx, hipGetLastError());
-    CsvCtl res{};
-    PG_HIP(ctx, hipMemcpyAsync(&res, ctl, sizeof(CsvCtl), hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PgScanCtl res{};
+    rc = S.read(ctx, &res);
+    if (rc) return rc;
     PG_CHECK(ctx, !(res.bad & CSV_BAD_LABEL), "csv_freq_rows: a row's locus, chromosome id or allele is out of range");
     PG_CHECK(ctx, !(res.bad & CSV_BAD_LONG), "csv_freq_rows: a row of text is longer than %d bytes", CSV_MAX_ROW);
     *bytes = res.total;
@@ -343,18 +254,16 @@ extern "C" int pg_csv_freq_rows_dev(pg_ctx *ctx, const double *G_dev, int64_t ld
     PG_CHECK(ctx, res.total <= cap, "csv_freq_rows: the text needs %lld bytes, the buffer holds %lld", (long long)res.total, (long long)cap);
     unsigned char *text = reinterpret_cast<unsigned char *>(text_dev);
     pg_prof_begin(ctx, PG_K_CSV | PG_PROF_CONT);
-    if (res.max_row > CSV_TILE) { // the direct path: a row does not fit the tile
+    if (res.max > CSV_TILE) { // the direct path: a row does not fit the tile
         const int64_t blocks = (rows + CSV_THREADS / 64 - 1) / (CSV_THREADS / 64);
-        hipLaunchKernelGGL(k_csv_emit<CSV_DIRECT>, dim3((unsigned)blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, 6, 0, local, boff, ctl, text);
+        hipLaunchKernelGGL(k_csv_emit<CSV_DIRECT>, dim3((unsigned)blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, 6, 0, S.local, S.boff, S.ctl, text);
     } else {
-        const int rpb = CSV_TILE / std::max(1, res.max_row); // rows per workgroup: rpb rows of at most the longest row's length fit the tile
+        const int rpb = CSV_TILE / std::max(1, res.max); // rows per workgroup: rpb rows of at most the longest row's length fit the tile
         const int64_t blocks = (rows + rpb - 1) / rpb;
         if (rpb < CSV_THREADS / 64) // fewer rows than waves (rows above 4 KB): a workgroup per row
-            hipLaunchKernelGGL(k_csv_emit<CSV_STAGED_WG>, dim3((unsigned)blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, 6, rpb, local, boff,
-                               ctl, text);
+            hipLaunchKernelGGL(k_csv_emit<CSV_STAGED_WG>, dim3((unsigned)blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, 6, rpb, S.local, S.boff, S.ctl, text);
         else
-            hipLaunchKernelGGL(k_csv_emit<CSV_STAGED>, dim3((unsigned)blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, lpr_shift, rpb, local,
-                               boff, ctl, text);
+            hipLaunchKernelGGL(k_csv_emit<CSV_STAGED>, dim3((unsigned)blocks), dim3(CSV_THREADS), 0, ctx->stream, R, rows, lpr_shift, rpb, S.local, S.boff, S.ctl, text);
     }
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());

@@ -17,6 +17,7 @@
 // the SURVIVING alleles (row sums change) and closes them.  The helpers below up to `Sums` serve that second pass.
 #include "pg_common.h"
 #include "pg_stats_device.h"
+#include "pg_text_steps.h"
 #include <cmath>
 #include <type_traits>
 #include <vector>
@@ -2770,32 +2771,6 @@ __global__ __launch_bounds__(256) void k_load_count(const int32_t *__restrict__ 
     if (tid == 255) blocksum[blockIdx.x] = sc[255];
 }
 
-__global__ __launch_bounds__(1024) void k_load_scan(const int64_t *__restrict__ blocksum, int64_t nb,
-                                                    int64_t *__restrict__ blockoff, int64_t *__restrict__ total) {
-    __shared__ int64_t sc[1024];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += 1024) {
-        const int64_t i = base + tid;
-        const int64_t c = i < nb ? blocksum[i] : 0;
-        sc[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const int64_t v = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += v;
-            __syncthreads();
-        }
-        if (i < nb) blockoff[i] = carry + sc[tid] - c;
-        __syncthreads();
-        if (tid == 1023) carry += sc[1023];
-        __syncthreads();
-    }
-    if (tid == 0) *total = carry;
-}
-
 __global__ __launch_bounds__(256) void k_load_emit(const uint32_t *__restrict__ counts, const int32_t *__restrict__ flags,
                                                    const int64_t *__restrict__ order, const int32_t *__restrict__ local,
                                                    const int64_t *__restrict__ blockoff, int64_t L, int n, int pshift,
@@ -2907,7 +2882,7 @@ int load_plan(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const d
     int64_t *bsum = reinterpret_cast<int64_t *>(tail + t_bsum), *boff = reinterpret_cast<int64_t *>(tail + t_boff);
     int64_t *tot_dev = reinterpret_cast<int64_t *>(tail + t_total);
     hipLaunchKernelGGL(k_load_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, W.flags, order_dev, L, pshift, kpm1, local, bsum);
-    hipLaunchKernelGGL(k_load_scan, dim3(1), dim3(1024), 0, ctx->stream, bsum, nb, boff, tot_dev);
+    pg_scan_blocks(ctx, bsum, nb, boff, tot_dev); // pg_text_steps.h
     PG_HIP(ctx, hipGetLastError());
     int64_t tot = 0;
     PG_HIP(ctx, hipMemcpyAsync(&tot, tot_dev, 8, hipMemcpyDeviceToHost, ctx->stream));

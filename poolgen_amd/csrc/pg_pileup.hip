@@ -1,8 +1,10 @@
 // pg_pileup.hip -- pileup2sync's reader on the device: a slab of samtools mpileup text to the allele counts of the loci that
 // PileupLine::filter keeps (base/pileup.rs; the rules, shared with the host twin, are pg_pileup_line.h).
-// The steps of pg_vcf.hip, in a copy of their own, on the context's stream:
-//   index   k_pl_index<false> (newlines per 4 KB of text: a lane reads one aligned 16-byte word) + k_pl_scan (64-bit exclusive
-//           scan of the workgroups' sums) + k_pl_index<true> (every newline writes the start of the line behind it);
+// The steps of pg_vcf.hip on the context's stream; the index, the scans and the lane-group steps are the shared ones of
+// pg_text_steps.h:
+//   index   PgLineIndex: k_text_index<false> (newlines per 4 KB of text: a lane reads one aligned 16-byte word) + k_scan_blocks
+//           (64-bit exclusive scan of the workgroups' sums) + k_text_index<true> (every newline writes the start of the line
+//           behind it);
 //   parse   k_pl_parse<false>: a line is taken by a GROUP of lanes (8 .. 64, a power of two chosen from the number of pool
 //           sizes).  The group walks its line in chunks of one byte per lane; a ballot on '\t' and a popcount of the lower lanes
 //           give a byte's field index, and the field starts go to LDS.  The first three fields are read by every lane alike;
@@ -11,12 +13,13 @@
 //           through lane shuffles one after the other.  Pools behind the n_sizes-th (the line is dropped, but only when it is
 //           sound) are checked by the group's first lane, one after the other.  One int per line comes out: kept or not; a
 //           line where the reference would panic enters (offset, reason) into one 64-bit atomicMin;
-//   scan    k_pl_keep (exclusive scan of 256 keep flags per workgroup) + k_pl_scan: a kept line's rank;
+//   scan    k_scan_keep (exclusive scan of 256 keep flags per workgroup) + k_scan_blocks: a kept line's rank;
 //   emit    k_pl_parse<true>: the kept lines are split and walked again and write their rows at their rank, adjacent pools
 //           from adjacent lanes.
 // No loop over the text can spin: each advances a cursor towards a field or line end (pg_pileup_line.h).  Every read of the
 // text is a byte of [0, bytes) or an aligned 16-byte word that holds one.
 #include "pg_common.h"
+#include "pg_text_steps.h"
 #include "pg_pileup_line.h"
 
 namespace {
@@ -25,107 +28,10 @@ constexpr int PL_THREADS = 256;
 constexpr size_t PL_LDS_BUDGET = 60 * 1024; // field starts of a workgroup's lines (beside the 512 bytes of tables)
 
 struct PlCtl { // read back by the host
+    PgLineCounts n;
     unsigned long long err; // pg_pileup_err_key of the first bad line, PG_PILEUP_NO_ERR without one
-    long long newlines, lines, kept;
+    int64_t kept;
 };
-
-struct PlText {
-    const unsigned char *text;
-    int64_t bytes;
-    int64_t head;    // text - head is 16-byte aligned
-    int64_t nchunks; // aligned 16-byte words that hold a byte of the text
-};
-
-// lanes per line: the smallest power of two that holds the pools, from 8 lanes to a wave
-int pl_lpr_shift(int n) {
-    int s = 3;
-    while (s < 6 && (1 << s) < n) ++s;
-    return s;
-}
-
-// bit k = byte k of x is '\n'
-__device__ __forceinline__ unsigned pl_nl4(unsigned x) {
-    const unsigned y = x ^ 0x0A0A0A0Au;
-    const unsigned z = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu); // 0x80 in every byte of y that is zero
-    return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u);
-}
-
-// the newlines among the bytes of aligned word c that belong to the text: bit k = position 16 c - head + k
-__device__ __forceinline__ unsigned pl_nl_mask(const PlText &T, int64_t c) {
-    if (c >= T.nchunks) return 0u;
-    const uint4 w = *reinterpret_cast<const uint4 *>(T.text - T.head + 16 * c); // whole inside the aligned words the text touches
-    unsigned m = pl_nl4(w.x) | (pl_nl4(w.y) << 4) | (pl_nl4(w.z) << 8) | (pl_nl4(w.w) << 12);
-    const int64_t p0 = 16 * c - T.head;
-    if (p0 < 0) m &= (0xffffu << (int)(-p0)) & 0xffffu;
-    if (p0 + 16 > T.bytes) m &= (1u << (int)(T.bytes - p0)) - 1u;
-    return m;
-}
-
-// ---- index ---------------------------------------------------------------------------------------------------------------
-template <bool EMIT>
-__global__ __launch_bounds__(PL_THREADS) void k_pl_index(const PlText T, int64_t *__restrict__ blocksum, const int64_t *__restrict__ blockoff,
-                                                         const PlCtl *__restrict__ ctl, int64_t *__restrict__ start) {
-    __shared__ int sc[PL_THREADS];
-    const int tid = threadIdx.x;
-    const int64_t c = (int64_t)blockIdx.x * PL_THREADS + tid;
-    unsigned m = pl_nl_mask(T, c);
-    const int cnt = __popc(m);
-    sc[tid] = cnt;
-    __syncthreads();
-    for (int d = 1; d < PL_THREADS; d <<= 1) {
-        const int v = tid >= d ? sc[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        __syncthreads();
-    }
-    if (!EMIT) {
-        if (tid == PL_THREADS - 1) blocksum[blockIdx.x] = sc[PL_THREADS - 1];
-        return;
-    }
-    int64_t rank = blockoff[blockIdx.x] + (sc[tid] - cnt); // newlines in front of this word
-    const int64_t p0 = 16 * c - T.head;
-    while (m) {
-        const int k = __ffs(m) - 1;
-        m &= m - 1u;
-        start[++rank] = p0 + k + 1; // rank + 1 <= newlines <= lines
-    }
-    if (c == 0) {
-        start[0] = 0;
-        if (ctl->lines > ctl->newlines) start[ctl->lines] = T.bytes + 1; // the last line lacks its newline: as if it stood at `bytes`
-    }
-}
-
-// exclusive 64-bit scan of the workgroups' sums, 1024 per round; the total goes to *total, and with `text` the number of lines
-// to *lines
-__global__ __launch_bounds__(1024) void k_pl_scan(const int64_t *__restrict__ blocksum, int64_t nb, int64_t *__restrict__ blockoff,
-                                                  long long *__restrict__ total, const unsigned char *__restrict__ text, int64_t bytes,
-                                                  long long *__restrict__ lines) {
-    __shared__ int64_t sc[1024];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += 1024) {
-        const int64_t i = base + tid;
-        const int64_t c = i < nb ? blocksum[i] : 0;
-        sc[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const int64_t v = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += v;
-            __syncthreads();
-        }
-        if (i < nb) blockoff[i] = carry + sc[tid] - c;
-        __syncthreads();
-        if (tid == 1023) carry += sc[1023];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        *total = carry;
-        if (text) *lines = carry + (text[bytes - 1] != '\n' ? 1 : 0);
-    }
-}
 
 // ---- parse and emit --------------------------------------------------------------------------------------------------------
 struct PlRule {
@@ -151,7 +57,7 @@ struct PlOut {
 enum { PL_DROP = 1, PL_KEEP = 2 }; // or minus a pg_pileup_reason
 
 template <bool EMIT>
-__global__ __launch_bounds__(PL_THREADS) void k_pl_parse(const PlText T, const int64_t *__restrict__ start, int64_t lines, const PlRule R, int shift,
+__global__ __launch_bounds__(PL_THREADS) void k_pl_parse(const PgText T, const int64_t *__restrict__ start, int64_t lines, const PlRule R, int shift,
                                                          int32_t *__restrict__ keep, PlCtl *__restrict__ ctl, const int32_t *__restrict__ local,
                                                          const int64_t *__restrict__ blockoff, const PlOut O) {
     extern __shared__ int fs_all[];
@@ -159,10 +65,8 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_parse(const PlText T, const i
     const int tid = threadIdx.x;
     for (int i = tid; i < (int)sizeof(PgPileupTables); i += PL_THREADS) tab[i] = R.tables[i];
     const unsigned char *cls = tab, *qcls = tab + 256;
-    const int lpr = 1 << shift;
-    const int g = tid >> shift, gl = tid & (lpr - 1);
-    const int gbase = (tid & 63) & ~(lpr - 1); // the group's first lane in its wave
-    const uint64_t gmask = lpr == 64 ? ~0ULL : ((1ULL << lpr) - 1ULL);
+    const PgLaneGroup G = lane_group(tid, shift);
+    const int lpr = G.lpr, g = G.g, gl = G.gl;
     int *fs = fs_all + (g < R.lpb ? g : 0) * R.F; // (groups without a line write nothing)
     const int64_t line = (int64_t)blockIdx.x * R.lpb + g;
     bool active = g < R.lpb && line < lines; // uniform over the group, as is everything decided from the line alone
@@ -170,27 +74,15 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_parse(const PlText T, const i
     int64_t s = 0;
     int res = PL_DROP, wlen = 0;
     if (active) {
-        s = start[line];
-        const int64_t e = start[line + 1] - 1; // the newline's place, or `bytes` for a last line without one
-        int64_t len = e - s;
-        if (len > 0 && T.text[e - 1] == '\r') --len;
+        int64_t len;
+        line_bounds(T, start, line, true, &s, &len); // a '\r' goes from a last line without its newline too
         if (len == 0) res = -PG_PILEUP_E_FIELDS;
-        else if (len > 0x7fffffffLL) res = -PG_PILEUP_E_LONG;
+        else if (len > PG_LINE_MAX) res = -PG_PILEUP_E_LONG;
         else wlen = (int)len;
     }
     const unsigned char *L = T.text + s;
     // the field starts: fs[f] = where field f begins, for f < F
-    int ntabs = 0;
-    for (int off = 0; off < wlen; off += lpr) { // (one trip count for the group; other groups of the wave may leave earlier)
-        const int idx = off + gl;
-        const bool tabhere = idx < wlen && L[idx] == '\t';
-        const uint64_t gb = ((uint64_t)__ballot(tabhere) >> gbase) & gmask;
-        if (tabhere) {
-            const int f = ntabs + __popcll(gb & ((1ULL << gl) - 1ULL)) + 1;
-            if (f < R.F) fs[f] = idx + 1;
-        }
-        ntabs += __popcll(gb);
-    }
+    const int ntabs = group_split_tabs(L, wlen, G, fs, R.F);
     if (gl == 0 && wlen > 0) fs[0] = 0;
     __syncthreads(); // every thread of the workgroup arrives: no path above returns
     if (wlen > 0) {
@@ -207,7 +99,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_parse(const PlText T, const i
             int covered = 0, phred = 0;
             double q = 0.0;
             int64_t rank = 0;
-            if (EMIT) rank = blockoff[line >> 8] + local[line];
+            if (EMIT) rank = scan_rank(local, blockoff, line);
             for (int j0 = 0; j0 < n; j0 += lpr) { // one trip count for the group
                 const int j = j0 + gl;
                 const bool have = j < n;
@@ -257,28 +149,9 @@ __global__ __launch_bounds__(PL_THREADS) void k_pl_parse(const PlText T, const i
         }
     }
     if (!EMIT && active && gl == 0) {
-        keep[line] = res == PL_KEEP ? 1 : 0;
+        keep[line] = res == PL_KEEP ? PG_LINE_KEEP : 0;
         if (res < 0) atomicMin(&ctl->err, (unsigned long long)pg_pileup_err_key(s, -res));
     }
-}
-
-// ---- scan of the keep flags ----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pl_keep(const int32_t *__restrict__ keep, int64_t lines, int32_t *__restrict__ local,
-                                                 int64_t *__restrict__ blocksum) {
-    __shared__ int sc[256];
-    const int tid = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-    const int c = i < lines ? keep[i] : 0;
-    sc[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const int a = tid >= d ? sc[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += a;
-        __syncthreads();
-    }
-    if (i < lines) local[i] = sc[tid] - c;
-    if (tid == 255) blocksum[blockIdx.x] = sc[255];
 }
 
 const char *pl_reason_text(int r) {
@@ -312,72 +185,35 @@ extern "C" int pg_pileup_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t by
     PG_CHECK(ctx, bytes < ((int64_t)1 << 40), "pileup_parse: a slab of %lld bytes; cut the text at line starts into slabs below 2^40", (long long)bytes);
     if (bytes == 0) return PG_OK;
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    PlText T;
-    T.text = reinterpret_cast<const unsigned char *>(text_dev);
-    T.bytes = bytes;
-    T.head = (int64_t)(reinterpret_cast<uintptr_t>(text_dev) & 15);
-    T.nchunks = (bytes + T.head + 15) / 16;
-    const int64_t nbi = (T.nchunks + PL_THREADS - 1) / PL_THREADS;
-    PG_CHECK(ctx, nbi < ((int64_t)1 << 31), "pileup_parse: a slab of %lld bytes; cut the text into smaller slabs", (long long)bytes);
+    const PgText T = pg_text(text_dev, bytes);
     PgPileupTables tables;
     pg_pileup_tables(keep_lowercase_reference != 0, max_base_error_rate, &tables); // (std::pow on the host, once per call)
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t off = 0;
-    const size_t o_ctl = off; off = up16(off + sizeof(PlCtl));
-    const size_t o_sizes = off; off = up16(off + sizeof(double) * (size_t)n_sizes);
-    const size_t o_tab = off; off = up16(off + sizeof(PgPileupTables));
-    const size_t o_bsi = off; off = up16(off + 8 * (size_t)nbi);
-    const size_t o_boi = off; off = up16(off + 8 * (size_t)nbi);
-    const size_t front = off;
-    int rc = pg_ws_reserve(ctx, front);
-    if (rc) return rc;
+    const size_t o_sizes = pg_up16(sizeof(PlCtl)), o_tab = pg_up16(o_sizes + sizeof(double) * (size_t)n_sizes);
+    const size_t front_bytes = o_tab + sizeof(PgPileupTables); // the front block: PlCtl, the pool sizes, the tables
     PlCtl init{};
     init.err = PG_PILEUP_NO_ERR;
-    auto count_lines = [&]() -> hipError_t { // the control block, the pool sizes, the tables, the newlines of every 4 KB and their scan
-        char *ws = static_cast<char *>(ctx->ws.get());
-        hipError_t e = hipMemcpyAsync(ws + o_ctl, &init, sizeof(PlCtl), hipMemcpyHostToDevice, ctx->stream);
+    auto front = [&](char *ws, auto count_lines) -> hipError_t {
+        hipError_t e = hipMemcpyAsync(ws, &init, sizeof(PlCtl), hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return e;
         e = hipMemcpyAsync(ws + o_sizes, pool_sizes, sizeof(double) * (size_t)n_sizes, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return e;
         e = hipMemcpyAsync(ws + o_tab, &tables, sizeof(PgPileupTables), hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return e;
-        PlCtl *ctl = reinterpret_cast<PlCtl *>(ws + o_ctl);
-        hipLaunchKernelGGL(k_pl_index<false>, dim3((unsigned)nbi), dim3(PL_THREADS), 0, ctx->stream, T, reinterpret_cast<int64_t *>(ws + o_bsi),
-                           (const int64_t *)nullptr, (const PlCtl *)nullptr, (int64_t *)nullptr);
-        hipLaunchKernelGGL(k_pl_scan, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const int64_t *>(ws + o_bsi), nbi,
-                           reinterpret_cast<int64_t *>(ws + o_boi), &ctl->newlines, T.text, bytes, &ctl->lines);
+        count_lines(PgNoHook());
         return hipGetLastError();
     };
     PlCtl res{};
-    pg_prof_begin(ctx, PG_K_PILEUP);
-    PG_HIP(ctx, count_lines());
-    pg_prof_end(ctx);
-    PG_HIP(ctx, hipMemcpyAsync(&res, static_cast<char *>(ctx->ws.get()) + o_ctl, sizeof(PlCtl), hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the host copies of init, tables and the sizes have been read by now)
-    const int64_t lines = res.lines;
-    PG_CHECK(ctx, lines >= 1 && lines <= bytes && res.newlines <= lines, "pileup_parse: internal error, %lld lines in %lld bytes", (long long)lines, (long long)bytes);
-    info->lines = lines;
-    const int64_t nbk = (lines + 255) / 256;
-    const size_t o_start = off; off = up16(off + 8 * (size_t)(lines + 2));
-    const size_t o_keep = off; off = up16(off + 4 * (size_t)lines);
-    const size_t o_local = off; off = up16(off + 4 * (size_t)lines);
-    const size_t o_bsk = off; off = up16(off + 8 * (size_t)nbk);
-    const size_t o_bok = off; off = up16(off + 8 * (size_t)nbk);
-    const size_t before = ctx->ws.bytes();
-    rc = pg_ws_reserve(ctx, off);
+    PgLineIndex X;
+    int rc = X.build(ctx, PG_K_PILEUP, "pileup_parse", T, front_bytes, front, &res);
+    const int64_t lines = X.lines;
+    info->lines = lines; // (0 until they are counted; reported even where the line tables could not be reserved)
     if (rc) return rc;
-    pg_prof_begin(ctx, PG_K_PILEUP | PG_PROF_CONT);
-    if (ctx->ws.bytes() != before) PG_HIP(ctx, count_lines()); // the workspace was replaced by a larger block: its front part again (the same numbers)
-    char *ws = static_cast<char *>(ctx->ws.get());
-    PlCtl *ctl = reinterpret_cast<PlCtl *>(ws + o_ctl);
-    int64_t *start = reinterpret_cast<int64_t *>(ws + o_start), *bsk = reinterpret_cast<int64_t *>(ws + o_bsk), *bok = reinterpret_cast<int64_t *>(ws + o_bok);
-    int32_t *keep = reinterpret_cast<int32_t *>(ws + o_keep), *local = reinterpret_cast<int32_t *>(ws + o_local);
-    hipLaunchKernelGGL(k_pl_index<true>, dim3((unsigned)nbi), dim3(PL_THREADS), 0, ctx->stream, T, (int64_t *)nullptr,
-                       reinterpret_cast<const int64_t *>(ws + o_boi), (const PlCtl *)ctl, start);
-    const int shift = pl_lpr_shift(n_sizes);
+    PlCtl *ctl = reinterpret_cast<PlCtl *>(X.ws);
+    int32_t *keep = X.info; // PG_LINE_KEEP or 0
+    const int shift = pg_lpr_shift(n_sizes, 3);
     PlRule R;
-    R.sizes = reinterpret_cast<const double *>(ws + o_sizes);
-    R.tables = reinterpret_cast<const unsigned char *>(ws + o_tab);
+    R.sizes = reinterpret_cast<const double *>(X.ws + o_sizes);
+    R.tables = reinterpret_cast<const unsigned char *>(X.ws + o_tab);
     R.n_sizes = n_sizes;
     R.F = 3 * n_sizes + 4;
     R.lpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)(PL_THREADS >> shift), PL_LDS_BUDGET / (sizeof(int) * (size_t)R.F)));
@@ -386,15 +222,17 @@ extern "C" int pg_pileup_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t by
     R.depth = min_coverage_depth;
     R.breadth = pg_pileup_breadth_threshold(min_coverage_breadth, n_sizes);
     R.maf = min_allele_frequency;
-    const int64_t nbp = (lines + R.lpb - 1) / R.lpb;
-    PG_CHECK(ctx, nbp < ((int64_t)1 << 31), "pileup_parse: %lld lines in one slab; cut the text into smaller slabs", (long long)lines);
+    int64_t nbp;
+    rc = X.parse_blocks(ctx, "pileup_parse", R.lpb, &nbp);
+    if (rc) return rc;
     const size_t lds = sizeof(int) * (size_t)R.lpb * (size_t)R.F; // at most 60 KB, or one line of 4096 pools: 49 168 bytes
     const PlOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(k_pl_parse<false>, dim3((unsigned)nbp), dim3(PL_THREADS), lds, ctx->stream, T, (const int64_t *)start, lines, R, shift, keep, ctl,
+    pg_prof_begin(ctx, PG_K_PILEUP | PG_PROF_CONT);
+    hipLaunchKernelGGL(k_pl_parse<false>, dim3((unsigned)nbp), dim3(PL_THREADS), lds, ctx->stream, T, (const int64_t *)X.start, lines, R, shift, keep, ctl,
                        (const int32_t *)nullptr, (const int64_t *)nullptr, none);
-    hipLaunchKernelGGL(k_pl_keep, dim3((unsigned)nbk), dim3(256), 0, ctx->stream, (const int32_t *)keep, lines, local, bsk);
-    hipLaunchKernelGGL(k_pl_scan, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)bsk, nbk, bok, &ctl->kept, (const unsigned char *)nullptr,
-                       (int64_t)0, (long long *)nullptr);
+    hipLaunchKernelGGL(k_scan_keep, dim3((unsigned)X.nbk), dim3(PG_COUNT_ROWS), 0, ctx->stream, (const int32_t *)keep, lines, X.local, X.bsk,
+                       (int64_t *)nullptr);
+    X.scan_kept(ctx, &ctl->kept);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
     PG_HIP(ctx, hipMemcpyAsync(&res, ctl, sizeof(PlCtl), hipMemcpyDeviceToHost, ctx->stream));
@@ -413,8 +251,8 @@ extern "C" int pg_pileup_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t by
     PG_CHECK(ctx, counts_dev && pos_dev && ref_dev && line_off_dev && chrom_len_dev, "pileup_parse: null output buffer");
     const PlOut O{counts_dev, pos_dev, ref_dev, line_off_dev, chrom_len_dev};
     pg_prof_begin(ctx, PG_K_PILEUP | PG_PROF_CONT);
-    hipLaunchKernelGGL(k_pl_parse<true>, dim3((unsigned)nbp), dim3(PL_THREADS), lds, ctx->stream, T, (const int64_t *)start, lines, R, shift, keep, ctl,
-                       (const int32_t *)local, (const int64_t *)bok, O);
+    hipLaunchKernelGGL(k_pl_parse<true>, dim3((unsigned)nbp), dim3(PL_THREADS), lds, ctx->stream, T, (const int64_t *)X.start, lines, R, shift, keep, ctl,
+                       (const int32_t *)X.local, (const int64_t *)X.bok, O);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
     return PG_OK;

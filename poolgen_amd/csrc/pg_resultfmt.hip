@@ -5,11 +5,12 @@
 // structure is pg_syncfmt.hip's, three steps on the context's stream:
 //   measure  k_rf_measure<Units>: the byte length of every unit (int32), a flag for a label out of range and for a unit that is
 //            too long;
-//   scan     k_rf_count (exclusive scan of RF_COUNT_ROWS = 256 lengths per workgroup, the longest unit) + k_rf_scan (64-bit
-//            exclusive scan of the workgroups' sums, RF_SCAN_WIDTH = 1024 per round): a unit's offset is blockoff[u >> 8] + local[u];
+//   scan     PgLengthScan (pg_text_steps.h): k_scan_lengths (exclusive scan of PG_COUNT_ROWS = 256 lengths per workgroup, the longest
+//            unit) + k_scan_blocks (64-bit exclusive scan of the workgroups' sums, PG_SCAN_WIDTH = 1024 per round): a unit's offset is
+//            scan_off(u);
 //   emit     k_rf_emit<Units, RF_STAGED>: a workgroup takes `upb` consecutive units -- one contiguous byte range of the output --
-//            formats them into an LDS tile laid out like the 16-byte words of the output, then copies the tile out: whole words by
-//            16-byte stores (a lane a word, consecutive lanes consecutive words), the ragged head and tail by byte stores.  Two
+//            formats them into an LDS tile laid out like the 16-byte words of the output, then copies the tile out (tile_flush): whole
+//            words by 16-byte stores (a lane a word, consecutive lanes consecutive words), the ragged head and tail by byte stores.  Two
 //            workgroups meet inside a word only with byte stores; nothing is read back; nothing at or past the total is written.
 //            k_rf_emit<Units, RF_DIRECT>: a unit longer than the tile goes to the output by byte stores.
 // ONE LANE FORMATS ONE UNIT.  The work differs from the other formatters': a unit has two to four number cells, not hundreds, and
@@ -23,6 +24,7 @@
 // A conversion keeps its state in registers (pg_f64_parts_t: digits, exponent, count); digits go straight to their bytes: no
 // array, no scratch.  The 128-bit powers of ten (pg_f64_pow10.h, 9872 bytes) are read-only device data.
 #include "pg_common.h"
+#include "pg_text_steps.h"
 #include "pg_result_rows.h"
 #include <algorithm>
 
@@ -34,20 +36,12 @@ namespace {
 
 constexpr int RF_THREADS = 256;
 constexpr int RF_TILE = 16384; // bytes of text a workgroup stages (plus up to 15 in front of them: the word it starts in)
-constexpr int RF_COUNT_SHIFT = 8, RF_COUNT_ROWS = 1 << RF_COUNT_SHIFT; // units per workgroup of the scan's first level
-constexpr int RF_SCAN_WIDTH = 1024;                                    // workgroup sums per round of its second level
 constexpr int RF_BAD_LABEL = 1, RF_BAD_LONG = 2;
-
-struct RfCtl { // the scan's results, read back by the host
-    int64_t total;
-    int32_t max_unit;
-    int32_t bad;
-};
 
 // ---- measure -----------------------------------------------------------------------------------------------------------
 template <class Units>
 __global__ __launch_bounds__(RF_THREADS) void k_rf_measure(const Units U, int64_t u0, int64_t count, int32_t *__restrict__ unitlen,
-                                                           RfCtl *__restrict__ ctl) {
+                                                           PgScanCtl *__restrict__ ctl) {
     const int64_t u = (int64_t)blockIdx.x * RF_THREADS + threadIdx.x;
     if (u >= count) return;
     int bad = 0;
@@ -63,128 +57,51 @@ __global__ __launch_bounds__(RF_THREADS) void k_rf_measure(const Units U, int64_
     if (bad) atomicOr(&ctl->bad, bad);
 }
 
-// ---- scan: the block-scan pattern of pg_csv.hip's k_csv_count / k_csv_scan, in a copy of its own ------------------------------
-__global__ __launch_bounds__(RF_COUNT_ROWS) void k_rf_count(int32_t *__restrict__ local, int64_t count, int64_t *__restrict__ blocksum,
-                                                            RfCtl *__restrict__ ctl) {
-    __shared__ int sc[RF_COUNT_ROWS];
-    __shared__ int smax[RF_COUNT_ROWS];
-    const int tid = threadIdx.x;
-    const int64_t u = (int64_t)blockIdx.x * RF_COUNT_ROWS + tid;
-    const int c = u < count ? local[u] : 0; // in: the unit's length; out (same element, same thread): its offset inside the block
-    sc[tid] = c;
-    smax[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < RF_COUNT_ROWS; d <<= 1) {
-        const int v = tid >= d ? sc[tid - d] : 0;
-        const int m = tid >= d ? smax[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        smax[tid] = max(smax[tid], m);
-        __syncthreads();
-    }
-    if (u < count) local[u] = sc[tid] - c;
-    if (tid == RF_COUNT_ROWS - 1) {
-        blocksum[blockIdx.x] = sc[RF_COUNT_ROWS - 1];
-        atomicMax(&ctl->max_unit, smax[RF_COUNT_ROWS - 1]);
-    }
-}
-
-__global__ __launch_bounds__(RF_SCAN_WIDTH) void k_rf_scan(const int64_t *__restrict__ blocksum, int64_t nb, int64_t *__restrict__ blockoff,
-                                                           RfCtl *__restrict__ ctl) {
-    __shared__ int64_t sc[RF_SCAN_WIDTH];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += RF_SCAN_WIDTH) {
-        const int64_t i = base + tid;
-        const int64_t c = i < nb ? blocksum[i] : 0;
-        sc[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < RF_SCAN_WIDTH; d <<= 1) {
-            const int64_t v = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += v;
-            __syncthreads();
-        }
-        if (i < nb) blockoff[i] = carry + sc[tid] - c;
-        __syncthreads();
-        if (tid == RF_SCAN_WIDTH - 1) carry += sc[RF_SCAN_WIDTH - 1];
-        __syncthreads();
-    }
-    if (tid == 0) ctl->total = carry;
-}
-
 // ---- emit --------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t rf_unit_off(const int32_t *__restrict__ local, const int64_t *__restrict__ blockoff, const RfCtl *ctl,
-                                               int64_t u, int64_t count) {
-    return u < count ? blockoff[u >> RF_COUNT_SHIFT] + local[u] : ctl->total;
-}
-
 enum { RF_STAGED = 0, RF_DIRECT = 1 }; // how k_rf_emit takes its units (the dispatch rule: rf_run)
 
 // Launched with blockDim.x = a multiple of 64, at most RF_THREADS: as many lanes as a workgroup has units (RF_STAGED).
 template <class Units, int MODE>
 __global__ __launch_bounds__(RF_THREADS) void k_rf_emit(const Units U, int64_t u0, int64_t count, int upb, const int32_t *__restrict__ local,
-                                                        const int64_t *__restrict__ blockoff, const RfCtl *__restrict__ ctl,
+                                                        const int64_t *__restrict__ blockoff, const PgScanCtl *__restrict__ ctl,
                                                         unsigned char *__restrict__ text) {
     const int tid = threadIdx.x, nthreads = blockDim.x;
     if (MODE == RF_DIRECT) { // a lane per unit, straight to the output
         const int64_t u = (int64_t)blockIdx.x * nthreads + tid;
         if (u < count) {
-            PgPutSink s{text + rf_unit_off(local, blockoff, ctl, u, count)};
+            PgPutSink s{text + scan_off(local, blockoff, ctl, u, count)};
             U.write(u0 + u, s);
         }
         return;
     }
     __shared__ __attribute__((aligned(16))) unsigned char tile[RF_TILE + 16];
     const int64_t u_lo = (int64_t)blockIdx.x * upb, u_hi = u_lo + upb < count ? u_lo + upb : count;
-    const int64_t B = rf_unit_off(local, blockoff, ctl, u_lo, count), E = rf_unit_off(local, blockoff, ctl, u_hi, count);
+    const int64_t B = scan_off(local, blockoff, ctl, u_lo, count), E = scan_off(local, blockoff, ctl, u_hi, count);
     const int head = (int)((reinterpret_cast<uintptr_t>(text) + (uint64_t)B) & 15); // tile[head + i] is byte B + i of the output
     for (int64_t u = u_lo + tid; u < u_hi; u += nthreads) {
-        PgPutSink s{tile + head + (int)(rf_unit_off(local, blockoff, ctl, u, count) - B)};
+        PgPutSink s{tile + head + (int)(scan_off(local, blockoff, ctl, u, count) - B)};
         U.write(u0 + u, s);
     }
     __syncthreads();
     const int nbytes = (int)(E - B);                                  // <= RF_TILE: upb units of at most the longest unit's length
-    const int h = min(nbytes, (16 - head) & 15);                      // bytes in front of the first whole word
-    const int body = (nbytes - h) & ~15;                              // whole 16-byte words
-    unsigned char *out = text + B;
-    if (tid < h) out[tid] = tile[head + tid];
-    for (int i = tid * 16; i < body; i += nthreads * 16)              // head + h is 0 or 16 whenever body > 0
-        *reinterpret_cast<uint4 *>(out + h + i) = *reinterpret_cast<const uint4 *>(tile + head + h + i);
-    const int tail = nbytes - h - body;                               // < 16
-    if (tid < tail) out[h + body + tid] = tile[head + h + body + tid];
+    tile_flush(tile, head, text + B, nbytes, tid, nthreads);
 }
 
 // units [u0, u0 + count) of U into text_dev; count >= 1 and the arguments checked
 template <class Units>
 int rf_run(pg_ctx *ctx, const char *who, const Units &U, int64_t u0, int64_t count, char *text_dev, int64_t cap, int64_t *bytes) {
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t nb = (count + RF_COUNT_ROWS - 1) / RF_COUNT_ROWS;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t off = 0;
-    const size_t o_local = off; off = up16(off + sizeof(int32_t) * (size_t)count);
-    const size_t o_bsum = off; off = up16(off + 8 * (size_t)nb);
-    const size_t o_boff = off; off = up16(off + 8 * (size_t)nb);
-    const size_t o_ctl = off; off = up16(off + sizeof(RfCtl));
-    const int rc = pg_ws_reserve(ctx, off);
+    PgLengthScan S;
+    int rc = S.prepare(ctx, count);
     if (rc) return rc;
-    char *ws = static_cast<char *>(ctx->ws.get());
-    int32_t *local = reinterpret_cast<int32_t *>(ws + o_local);
-    int64_t *bsum = reinterpret_cast<int64_t *>(ws + o_bsum), *boff = reinterpret_cast<int64_t *>(ws + o_boff);
-    RfCtl *ctl = reinterpret_cast<RfCtl *>(ws + o_ctl);
-    PG_HIP(ctx, hipMemsetAsync(ctl, 0, sizeof(RfCtl), ctx->stream));
     const int64_t measure_blocks = (count + RF_THREADS - 1) / RF_THREADS;
     pg_prof_begin(ctx, PG_K_RESULTFMT);
-    hipLaunchKernelGGL(k_rf_measure<Units>, dim3((unsigned)measure_blocks), dim3(RF_THREADS), 0, ctx->stream, U, u0, count, local, ctl);
-    hipLaunchKernelGGL(k_rf_count, dim3((unsigned)nb), dim3(RF_COUNT_ROWS), 0, ctx->stream, local, count, bsum, ctl);
-    hipLaunchKernelGGL(k_rf_scan, dim3(1), dim3(RF_SCAN_WIDTH), 0, ctx->stream, bsum, nb, boff, ctl);
+    hipLaunchKernelGGL(k_rf_measure<Units>, dim3((unsigned)measure_blocks), dim3(RF_THREADS), 0, ctx->stream, U, u0, count, S.local, S.ctl);
+    S.scan(ctx);
     pg_prof_end(ctx);
-    PG_HIP(ctx, hipGetLastError());
-    RfCtl res{};
-    PG_HIP(ctx, hipMemcpyAsync(&res, ctl, sizeof(RfCtl), hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PgScanCtl res{};
+    rc = S.read(ctx, &res);
+    if (rc) return rc;
     PG_CHECK(ctx, !(res.bad & RF_BAD_LABEL), "%s: a label is out of range (chromosome id, name offsets or allele id)", who);
     PG_CHECK(ctx, !(res.bad & RF_BAD_LONG), "%s: the text of one unit is longer than %d bytes", who, PG_RESULT_UNIT_MAX);
     *bytes = res.total;
@@ -192,16 +109,14 @@ int rf_run(pg_ctx *ctx, const char *who, const Units &U, int64_t u0, int64_t cou
     if (res.total == 0) return PG_OK; // (every locus dropped)
     unsigned char *text = reinterpret_cast<unsigned char *>(text_dev);
     pg_prof_begin(ctx, PG_K_RESULTFMT | PG_PROF_CONT);
-    if (res.max_unit > RF_TILE) { // the direct path: a unit does not fit the tile
+    if (res.max > RF_TILE) { // the direct path: a unit does not fit the tile
         const int64_t blocks = (count + RF_THREADS - 1) / RF_THREADS;
-        hipLaunchKernelGGL((k_rf_emit<Units, RF_DIRECT>), dim3((unsigned)blocks), dim3(RF_THREADS), 0, ctx->stream, U, u0, count, 0, local, boff, ctl,
-                           text);
+        hipLaunchKernelGGL((k_rf_emit<Units, RF_DIRECT>), dim3((unsigned)blocks), dim3(RF_THREADS), 0, ctx->stream, U, u0, count, 0, S.local, S.boff, S.ctl, text);
     } else {
-        const int upb = RF_TILE / std::max(1, res.max_unit); // units per workgroup: upb units of at most the longest unit's length fit the tile
+        const int upb = RF_TILE / std::max(1, res.max); // units per workgroup: upb units of at most the longest unit's length fit the tile
         const int threads = std::min(RF_THREADS, (upb + 63) & ~63);
         const int64_t blocks = (count + upb - 1) / upb;
-        hipLaunchKernelGGL((k_rf_emit<Units, RF_STAGED>), dim3((unsigned)blocks), dim3(threads), 0, ctx->stream, U, u0, count, upb, local, boff, ctl,
-                           text);
+        hipLaunchKernelGGL((k_rf_emit<Units, RF_STAGED>), dim3((unsigned)blocks), dim3(threads), 0, ctx->stream, U, u0, count, upb, S.local, S.boff, S.ctl, text);
     }
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());

@@ -1,85 +1,44 @@
 // pg_sync.hip -- the sync reader on the device: a slab of sync text to the counts of its loci (the rules, shared with the host
-// twin, are pg_sync_line.h).  The index / scan pattern is pg_vcf.hip's, in a copy of its own.  Steps on
-// the context's stream:
-//   index   k_sync_index<false> (newlines per 4 KB of text: a lane reads one aligned 16-byte word; it also offers every line
-//           start whose first byte is not '#' to a minimum, the first data line) + k_sync_scan (64-bit exclusive scan of the
-//           workgroups' sums, 1024 per round) + k_sync_first (the tabs of that first line: the pool count, from which the host
-//           sizes the lane groups) + k_sync_index<true> (the same read again, a block scan, and every newline writes the start
-//           of the line behind it): start[0 .. lines], no host work per line;
+// twin, are pg_sync_line.h).  The index, the scans and the lane-group steps are the shared ones of
+// pg_text_steps.h.  Steps on the context's stream:
+//   index   PgLineIndex: k_text_index<false> (newlines per 4 KB of text: a lane reads one aligned 16-byte word; through
+//           SyncFirstHook it also offers every line start whose first byte is not '#' to a minimum, the first data line) +
+//           k_scan_blocks (64-bit exclusive scan of the workgroups' sums, 1024 per round) + k_sync_first (the tabs of that first
+//           line: the pool count, from which the host sizes the lane groups) + k_text_index<true> (the same read again, a block
+//           scan, and every newline writes the start of the line behind it): start[0 .. lines], no host work per line;
 //   parse   k_sync_parse<false>: a line is taken by a GROUP of lanes (8 .. 64, a power of two chosen from the pool count, so that
 //           5 pools have 8 lines in a wave and 200 pools one line across it).  The group walks its line in chunks of one byte per
 //           lane; a ballot on '\t' and a popcount of the lower lanes give a byte's field index, and the field starts go to LDS.
 //           The position is read by every lane alike; then lane j takes pools j, j + lanes, ..  One int per line comes out
 //           (kept, data line); a line where the host parser would throw enters (offset, reason) into one 64-bit atomicMin;
-//   scan    k_sync_keep (exclusive scan of 256 keep flags per workgroup, data lines counted) + k_sync_scan: a kept line's rank
-//           is blockoff[line >> 8] + local[line];
+//   scan    k_scan_keep (exclusive scan of 256 keep flags per workgroup, data lines counted) + k_scan_blocks: a kept line's rank
+//           is scan_rank(local, blockoff, line);
 //   emit    k_sync_parse<true>: the kept lines are split and read again and write their rows at their rank; adjacent lanes
 //           write adjacent pools, so a wave's stores are one contiguous run.
 // No array is indexed at run time in a thread: a pool's numbers are the named members of PgSyncPool.  Every read of the text
 // is a byte inside [0, bytes) or a whole aligned 16-byte word that holds such a byte.
 #include "pg_common.h"
+#include "pg_text_steps.h"
 #include "pg_sync_line.h"
 
 namespace {
 
 constexpr int SYNC_THREADS = 256;
-constexpr int SYNC_INFO_KEEP = 1, SYNC_INFO_DATA = 2;
+constexpr int SYNC_INFO_KEEP = PG_LINE_KEEP, SYNC_INFO_DATA = PG_LINE_DATA;
 
 struct SyncCtl { // read back by the host
+    PgLineCounts n;
     unsigned long long err;   // pg_sync_err_key of the first bad line, PG_SYNC_NO_ERR without one
     unsigned long long first; // the offset of the first line that does not start with '#', ~0 without one
     long long first_tabs;     // the tabs of that line
-    long long newlines, lines, kept, data_lines;
+    int64_t kept, data_lines;
 };
 
-struct SyncText {
-    const unsigned char *text;
-    int64_t bytes;
-    int64_t head;    // text - head is 16-byte aligned
-    int64_t nchunks; // aligned 16-byte words that hold a byte of the text
-};
-
-// lanes per line: the smallest power of two that holds the pools, from 8 lanes to a wave
-int sync_lpr_shift(int n) {
-    int s = 3;
-    while (s < 6 && (1 << s) < n) ++s;
-    return s;
-}
-
-// bit k = byte k of x equals the byte repeated in c4
-__device__ __forceinline__ unsigned sync_eq4(unsigned x, unsigned c4) {
-    const unsigned y = x ^ c4;
-    const unsigned z = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu); // 0x80 in every byte of y that is zero
-    return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u);
-}
-
-// of the bytes of aligned word c that belong to the text: *nl bit k = position 16 c - head + k is '\n', *hash the same for '#'
-__device__ __forceinline__ void sync_masks(const SyncText &T, int64_t c, unsigned *nl, unsigned *hash) {
-    *nl = 0u;
-    *hash = 0u;
-    if (c >= T.nchunks) return;
-    const uint4 w = *reinterpret_cast<const uint4 *>(T.text - T.head + 16 * c); // whole inside the aligned words the text touches
-    unsigned m = sync_eq4(w.x, 0x0A0A0A0Au) | (sync_eq4(w.y, 0x0A0A0A0Au) << 4) | (sync_eq4(w.z, 0x0A0A0A0Au) << 8) | (sync_eq4(w.w, 0x0A0A0A0Au) << 12);
-    unsigned h = sync_eq4(w.x, 0x23232323u) | (sync_eq4(w.y, 0x23232323u) << 4) | (sync_eq4(w.z, 0x23232323u) << 8) | (sync_eq4(w.w, 0x23232323u) << 12);
-    const int64_t p0 = 16 * c - T.head;
-    unsigned valid = 0xffffu;
-    if (p0 < 0) valid &= (0xffffu << (int)(-p0)) & 0xffffu;
-    if (p0 + 16 > T.bytes) valid &= (1u << (int)(T.bytes - p0)) - 1u;
-    *nl = m & valid;
-    *hash = h & valid;
-}
-
-// ---- index ---------------------------------------------------------------------------------------------------------------
-template <bool EMIT>
-__global__ __launch_bounds__(SYNC_THREADS) void k_sync_index(const SyncText T, int64_t *__restrict__ blocksum, const int64_t *__restrict__ blockoff,
-                                                             SyncCtl *__restrict__ ctl, int64_t *__restrict__ start) {
-    __shared__ int sc[SYNC_THREADS];
-    const int tid = threadIdx.x;
-    const int64_t c = (int64_t)blockIdx.x * SYNC_THREADS + tid;
-    unsigned m, hash;
-    sync_masks(T, c, &m, &hash);
-    const int64_t p0 = 16 * c - T.head;
-    if (!EMIT && c < T.nchunks) {
+// The index's hook: every line start whose first byte is not '#' is offered to a minimum, the first data line.
+struct SyncFirstHook {
+    unsigned long long *first; // SyncCtl::first
+    __device__ void operator()(const PgText &T, int64_t c, int64_t p0, unsigned m) const {
+        const unsigned hash = text_eq_mask(T, c, '#');
         // the line starts among this word's bytes: behind a newline of this word, behind one that ends the word before, at 0
         unsigned ls = (m << 1) & 0xffffu;
         if (p0 <= 0) ls |= 1u << (int)(-p0);
@@ -88,68 +47,13 @@ __global__ __launch_bounds__(SYNC_THREADS) void k_sync_index(const SyncText T, i
         ls &= ~hash;
         if (ls) {
             const unsigned long long cand = (unsigned long long)(p0 + (__ffs(ls) - 1));
-            if (cand < *reinterpret_cast<volatile unsigned long long *>(&ctl->first)) atomicMin(&ctl->first, cand); // (the value only falls)
+            if (cand < *reinterpret_cast<volatile unsigned long long *>(first)) atomicMin(first, cand); // (the value only falls)
         }
     }
-    const int cnt = __popc(m);
-    sc[tid] = cnt;
-    __syncthreads();
-    for (int d = 1; d < SYNC_THREADS; d <<= 1) {
-        const int v = tid >= d ? sc[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        __syncthreads();
-    }
-    if (!EMIT) {
-        if (tid == SYNC_THREADS - 1) blocksum[blockIdx.x] = sc[SYNC_THREADS - 1];
-        return;
-    }
-    int64_t rank = blockoff[blockIdx.x] + (sc[tid] - cnt); // newlines in front of this word
-    while (m) {
-        const int k = __ffs(m) - 1;
-        m &= m - 1u;
-        start[++rank] = p0 + k + 1; // rank + 1 <= newlines <= lines
-    }
-    if (c == 0) {
-        start[0] = 0;
-        if (ctl->lines > ctl->newlines) start[ctl->lines] = T.bytes + 1; // the last line lacks its newline: as if it stood at `bytes`
-    }
-}
-
-// exclusive 64-bit scan of the workgroups' sums (the pattern of k_vcf_scan / k_csv_scan, in a copy of its own); the total goes
-// to *total, and with `text` the number of lines to *lines
-__global__ __launch_bounds__(1024) void k_sync_scan(const int64_t *__restrict__ blocksum, int64_t nb, int64_t *__restrict__ blockoff,
-                                                    long long *__restrict__ total, const unsigned char *__restrict__ text, int64_t bytes,
-                                                    long long *__restrict__ lines) {
-    __shared__ int64_t sc[1024];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += 1024) {
-        const int64_t i = base + tid;
-        const int64_t c = i < nb ? blocksum[i] : 0;
-        sc[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const int64_t v = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += v;
-            __syncthreads();
-        }
-        if (i < nb) blockoff[i] = carry + sc[tid] - c;
-        __syncthreads();
-        if (tid == 1023) carry += sc[1023];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        *total = carry;
-        if (text) *lines = carry + (text[bytes - 1] != '\n' ? 1 : 0);
-    }
-}
+};
 
 // the tabs of the first line that does not start with '#' (one workgroup; 256 bytes a round, up to the line's newline)
-__global__ __launch_bounds__(SYNC_THREADS) void k_sync_first(const SyncText T, SyncCtl *__restrict__ ctl) {
+__global__ __launch_bounds__(SYNC_THREADS) void k_sync_first(const PgText T, SyncCtl *__restrict__ ctl) {
     __shared__ int tabs[SYNC_THREADS];
     __shared__ int stop;
     const int tid = threadIdx.x;
@@ -186,15 +90,13 @@ struct SyncOut {
 };
 
 template <bool EMIT>
-__global__ __launch_bounds__(SYNC_THREADS) void k_sync_parse(const SyncText T, const int64_t *__restrict__ start, int64_t lines, int n_ref, int F,
+__global__ __launch_bounds__(SYNC_THREADS) void k_sync_parse(const PgText T, const int64_t *__restrict__ start, int64_t lines, int n_ref, int F,
                                                              int shift, int32_t *__restrict__ info, SyncCtl *__restrict__ ctl,
                                                              const int32_t *__restrict__ local, const int64_t *__restrict__ blockoff, const SyncOut O) {
     extern __shared__ int fs_all[];
     const int tid = threadIdx.x;
-    const int lpr = 1 << shift;
-    const int g = tid >> shift, gl = tid & (lpr - 1);
-    const int gbase = (tid & 63) & ~(lpr - 1); // the group's first lane in its wave
-    const uint64_t gmask = lpr == 64 ? ~0ULL : ((1ULL << lpr) - 1ULL);
+    const PgLaneGroup G = lane_group(tid, shift);
+    const int lpr = G.lpr, g = G.g, gl = G.gl;
     int *fs = fs_all + g * F;
     const int64_t line = (int64_t)blockIdx.x * (blockDim.x >> shift) + g;
     bool active = line < lines; // uniform over the group, as is everything decided from the line alone
@@ -203,30 +105,18 @@ __global__ __launch_bounds__(SYNC_THREADS) void k_sync_parse(const SyncText T, c
     int res = 0, wlen = 0; // res: 0 skipped, 1 kept, or minus a pg_sync_reason
     bool data = false;
     if (active) {
-        s = start[line];
-        const int64_t e = start[line + 1] - 1; // the newline's place, or `bytes` for a last line without one
-        int64_t len = e - s;
-        if (len > 0 && T.text[e - 1] == '\r') --len;
+        int64_t len;
+        line_bounds(T, start, line, true, &s, &len); // a '\r' goes from a last line without its newline too
         if (len == 0) res = -PG_SYNC_E_EMPTY;
         else if (T.text[s] != '#') {
             data = true;
-            if (len > 0x7fffffffLL) res = -PG_SYNC_E_LONG;
+            if (len > PG_LINE_MAX) res = -PG_SYNC_E_LONG;
             else wlen = (int)len;
         }
     }
     const unsigned char *L = T.text + s;
     // the field starts: fs[f] = where field f begins, for 1 <= f < F
-    int ntabs = 0;
-    for (int off = 0; off < wlen; off += lpr) { // (one trip count for the group; other groups of the wave may leave earlier)
-        const int idx = off + gl;
-        const bool tab = idx < wlen && L[idx] == '\t';
-        const uint64_t gb = ((uint64_t)__ballot(tab) >> gbase) & gmask;
-        if (tab) {
-            const int f = ntabs + __popcll(gb & ((1ULL << gl) - 1ULL)) + 1;
-            if (f < F) fs[f] = idx + 1;
-        }
-        ntabs += __popcll(gb);
-    }
+    const int ntabs = group_split_tabs(L, wlen, G, fs, F);
     __syncthreads(); // every thread of the workgroup arrives: no path above returns
     if (wlen > 0) {
         uint64_t pos = 0;
@@ -238,7 +128,7 @@ __global__ __launch_bounds__(SYNC_THREADS) void k_sync_parse(const SyncText T, c
             const int mm = min(m, n_ref);       // those that are looked at; field 3 + j < F - 1 for j < mm
             int err = m != n_ref ? PG_SYNC_E_POOLS : 0;
             int64_t rank = 0;
-            if (EMIT) rank = blockoff[line >> 8] + local[line];
+            if (EMIT) rank = scan_rank(local, blockoff, line);
             for (int j0 = 0; j0 < mm; j0 += lpr) { // one trip count for the group
                 const int j = j0 + gl;
                 if (j < mm) {
@@ -271,33 +161,6 @@ __global__ __launch_bounds__(SYNC_THREADS) void k_sync_parse(const SyncText T, c
     }
 }
 
-// ---- scan of the keep flags (k_vcf_keep's pattern) -------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sync_keep(const int32_t *__restrict__ info, int64_t lines, int32_t *__restrict__ local,
-                                                   int64_t *__restrict__ blocksum, SyncCtl *__restrict__ ctl) {
-    __shared__ int sc[256];
-    __shared__ int sd[256];
-    const int tid = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-    const int v = i < lines ? info[i] : 0;
-    const int c = v & SYNC_INFO_KEEP;
-    sc[tid] = c;
-    sd[tid] = (v & SYNC_INFO_DATA) ? 1 : 0;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const int a = tid >= d ? sc[tid - d] : 0;
-        const int b = tid >= d ? sd[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += a;
-        sd[tid] += b;
-        __syncthreads();
-    }
-    if (i < lines) local[i] = sc[tid] - c;
-    if (tid == 255) {
-        blocksum[blockIdx.x] = sc[255];
-        if (sd[255]) atomicAdd(reinterpret_cast<unsigned long long *>(&ctl->data_lines), (unsigned long long)sd[255]);
-    }
-}
-
 const char *sync_reason_text(int r) {
     switch (r) {
     case PG_SYNC_E_EMPTY: return "an empty line";
@@ -324,43 +187,24 @@ extern "C" int pg_sync_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t byte
     PG_CHECK(ctx, bytes < ((int64_t)1 << 40), "sync_parse: a slab of %lld bytes; cut the text at line starts into slabs below 2^40", (long long)bytes);
     if (bytes == 0) return PG_OK;
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    SyncText T;
-    T.text = reinterpret_cast<const unsigned char *>(text_dev);
-    T.bytes = bytes;
-    T.head = (int64_t)(reinterpret_cast<uintptr_t>(text_dev) & 15);
-    T.nchunks = (bytes + T.head + 15) / 16;
-    const int64_t nbi = (T.nchunks + SYNC_THREADS - 1) / SYNC_THREADS;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t off = 0;
-    const size_t o_ctl = off; off = up16(off + sizeof(SyncCtl));
-    const size_t o_bsi = off; off = up16(off + 8 * (size_t)nbi);
-    const size_t o_boi = off; off = up16(off + 8 * (size_t)nbi);
-    const size_t front = off;
-    int rc = pg_ws_reserve(ctx, front);
-    if (rc) return rc;
+    const PgText T = pg_text(text_dev, bytes);
     SyncCtl init{};
     init.err = PG_SYNC_NO_ERR;
     init.first = ~0ULL;
-    auto count_lines = [&]() -> hipError_t { // the control block, the newlines of every 4 KB, their scan, the first data line
-        char *ws = static_cast<char *>(ctx->ws.get());
-        hipError_t e = hipMemcpyAsync(ws + o_ctl, &init, sizeof(SyncCtl), hipMemcpyHostToDevice, ctx->stream);
+    auto front = [&](char *ws, auto count_lines) -> hipError_t { // the front block is SyncCtl alone; behind the index, the first data line's tabs
+        SyncCtl *ctl = reinterpret_cast<SyncCtl *>(ws);
+        const hipError_t e = hipMemcpyAsync(ctl, &init, sizeof(SyncCtl), hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return e;
-        SyncCtl *ctl = reinterpret_cast<SyncCtl *>(ws + o_ctl);
-        hipLaunchKernelGGL(k_sync_index<false>, dim3((unsigned)nbi), dim3(SYNC_THREADS), 0, ctx->stream, T, reinterpret_cast<int64_t *>(ws + o_bsi),
-                           (const int64_t *)nullptr, ctl, (int64_t *)nullptr);
-        hipLaunchKernelGGL(k_sync_scan, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const int64_t *>(ws + o_bsi), nbi,
-                           reinterpret_cast<int64_t *>(ws + o_boi), &ctl->newlines, T.text, bytes, &ctl->lines);
+        count_lines(SyncFirstHook{&ctl->first});
         hipLaunchKernelGGL(k_sync_first, dim3(1), dim3(SYNC_THREADS), 0, ctx->stream, T, ctl);
         return hipGetLastError();
     };
     SyncCtl res{};
-    pg_prof_begin(ctx, PG_K_SYNC);
-    PG_HIP(ctx, count_lines());
-    pg_prof_end(ctx);
-    PG_HIP(ctx, hipMemcpyAsync(&res, static_cast<char *>(ctx->ws.get()) + o_ctl, sizeof(SyncCtl), hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t lines = res.lines;
-    PG_CHECK(ctx, lines >= 1 && lines <= bytes && res.newlines <= lines, "sync_parse: internal error, %lld lines in %lld bytes", (long long)lines, (long long)bytes);
+    PgLineIndex X;
+    int rc = X.build(ctx, PG_K_SYNC, "sync_parse", T, sizeof(SyncCtl), front, &res);
+    if (rc) return rc;
+    const int64_t lines = X.lines;
+    SyncCtl *ctl = reinterpret_cast<SyncCtl *>(X.ws);
     // the first line that does not start with '#' fixes the pool count
     uint64_t first_err = PG_SYNC_NO_ERR;
     int n_first = 0;
@@ -369,36 +213,21 @@ extern "C" int pg_sync_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t byte
         if (code) first_err = pg_sync_err_key((int64_t)res.first, code);
     }
     const int n_ref = expect_n > 0 ? expect_n : std::max(1, std::min(n_first, PG_SYNC_MAX_POOLS)); // what the lines are compared with
-    const int64_t nbk = (lines + 255) / 256;
-    const size_t o_start = off; off = up16(off + 8 * (size_t)(lines + 2));
-    const size_t o_info = off; off = up16(off + 4 * (size_t)lines);
-    const size_t o_local = off; off = up16(off + 4 * (size_t)lines);
-    const size_t o_bsk = off; off = up16(off + 8 * (size_t)nbk);
-    const size_t o_bok = off; off = up16(off + 8 * (size_t)nbk);
-    const size_t before = ctx->ws.bytes();
-    rc = pg_ws_reserve(ctx, off);
-    if (rc) return rc;
-    pg_prof_begin(ctx, PG_K_SYNC | PG_PROF_CONT);
-    if (ctx->ws.bytes() != before) PG_HIP(ctx, count_lines()); // the workspace was replaced by a larger block (wherever that one lies): its front part again (the same numbers)
-    char *ws = static_cast<char *>(ctx->ws.get());
-    SyncCtl *ctl = reinterpret_cast<SyncCtl *>(ws + o_ctl);
-    int64_t *start = reinterpret_cast<int64_t *>(ws + o_start), *bsk = reinterpret_cast<int64_t *>(ws + o_bsk), *bok = reinterpret_cast<int64_t *>(ws + o_bok);
-    int32_t *linfo = reinterpret_cast<int32_t *>(ws + o_info), *local = reinterpret_cast<int32_t *>(ws + o_local);
-    hipLaunchKernelGGL(k_sync_index<true>, dim3((unsigned)nbi), dim3(SYNC_THREADS), 0, ctx->stream, T, (int64_t *)nullptr,
-                       reinterpret_cast<const int64_t *>(ws + o_boi), ctl, start);
     const int F = n_ref + 4; // field starts a group keeps: 1 .. n_ref + 3
-    const int shift = sync_lpr_shift(n_ref);
+    const int shift = pg_lpr_shift(n_ref, 3); // so that 5 pools have 8 lines in a wave and 200 pools one line across it
     const int threads = n_ref > 1024 ? 64 : SYNC_THREADS; // one line per workgroup where a line's field starts take 4 KB or more
     const int lines_per_block = threads >> shift;
-    const int64_t nbp = (lines + lines_per_block - 1) / lines_per_block;
-    PG_CHECK(ctx, nbp < ((int64_t)1 << 31), "sync_parse: %lld lines in one slab; cut the text into smaller slabs", (long long)lines);
+    int64_t nbp;
+    rc = X.parse_blocks(ctx, "sync_parse", lines_per_block, &nbp);
+    if (rc) return rc;
     const size_t lds = sizeof(int) * (size_t)lines_per_block * (size_t)F; // at most 32 x 12, 4 x 1028 or 1 x 4100 ints
     const SyncOut none{nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(k_sync_parse<false>, dim3((unsigned)nbp), dim3(threads), lds, ctx->stream, T, (const int64_t *)start, lines, n_ref, F, shift, linfo,
+    pg_prof_begin(ctx, PG_K_SYNC | PG_PROF_CONT);
+    hipLaunchKernelGGL(k_sync_parse<false>, dim3((unsigned)nbp), dim3(threads), lds, ctx->stream, T, (const int64_t *)X.start, lines, n_ref, F, shift, X.info,
                        ctl, (const int32_t *)nullptr, (const int64_t *)nullptr, none);
-    hipLaunchKernelGGL(k_sync_keep, dim3((unsigned)nbk), dim3(256), 0, ctx->stream, (const int32_t *)linfo, lines, local, bsk, ctl);
-    hipLaunchKernelGGL(k_sync_scan, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)bsk, nbk, bok, &ctl->kept, (const unsigned char *)nullptr,
-                       (int64_t)0, (long long *)nullptr);
+    hipLaunchKernelGGL(k_scan_keep, dim3((unsigned)X.nbk), dim3(PG_COUNT_ROWS), 0, ctx->stream, (const int32_t *)X.info, lines, X.local, X.bsk,
+                       &ctl->data_lines);
+    X.scan_kept(ctx, &ctl->kept);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
     PG_HIP(ctx, hipMemcpyAsync(&res, ctl, sizeof(SyncCtl), hipMemcpyDeviceToHost, ctx->stream));
@@ -420,8 +249,8 @@ extern "C" int pg_sync_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t byte
     PG_CHECK(ctx, pos_dev && line_off_dev && chrom_len_dev && counts_dev, "sync_parse: null output buffer");
     const SyncOut O{counts_dev, pos_dev, line_off_dev, chrom_len_dev};
     pg_prof_begin(ctx, PG_K_SYNC | PG_PROF_CONT);
-    hipLaunchKernelGGL(k_sync_parse<true>, dim3((unsigned)nbp), dim3(threads), lds, ctx->stream, T, (const int64_t *)start, lines, n_ref, F, shift, linfo, ctl,
-                       (const int32_t *)local, (const int64_t *)bok, O);
+    hipLaunchKernelGGL(k_sync_parse<true>, dim3((unsigned)nbp), dim3(threads), lds, ctx->stream, T, (const int64_t *)X.start, lines, n_ref, F, shift, X.info, ctl,
+                       (const int32_t *)X.local, (const int64_t *)X.bok, O);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
     return PG_OK;

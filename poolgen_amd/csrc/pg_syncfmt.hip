@@ -7,32 +7,30 @@
 // context's stream:
 //   measure  k_syncfmt_measure: the byte length of every row (int32), a flag for a name outside the slab and for a row that is
 //            too long;
-//   scan     k_syncfmt_count (exclusive scan of SF_COUNT_ROWS = 256 lengths per workgroup, the longest row) + k_syncfmt_scan (64-bit exclusive
-//            scan of the workgroups' sums, SF_SCAN_WIDTH = 1024 per round): a row's offset is blockoff[r >> 8] + local[r];
+//   scan     PgLengthScan (pg_text_steps.h): k_scan_lengths (exclusive scan of PG_COUNT_ROWS = 256 lengths per workgroup, the longest
+//            row) + k_scan_blocks (64-bit exclusive scan of the workgroups' sums, PG_SCAN_WIDTH = 1024 per round): a row's offset is
+//            scan_off(r);
 //   emit     k_syncfmt_emit<SF_STAGED>: a workgroup takes `rpb` consecutive rows -- one contiguous byte range of the output --
-//            formats them into an LDS tile laid out like the 16-byte words of the output, then copies the tile out: whole words by
-//            16-byte stores (a lane a word, consecutive lanes consecutive words), the ragged head and tail by byte stores.  Two
+//            formats them into an LDS tile laid out like the 16-byte words of the output, then copies the tile out (tile_flush): whole
+//            words by 16-byte stores (a lane a word, consecutive lanes consecutive words), the ragged head and tail by byte stores.  Two
 //            workgroups meet inside a word only with byte stores; nothing is read back; nothing at or past the total is written.
 //            k_syncfmt_emit<SF_DIRECT>: a row longer than the tile goes to the output by byte stores, a wave per row.
 // A row is formatted by a GROUP of lpr lanes (1 .. 64, a power of two: the smallest that holds n_pools): lane j of the group takes
 // pools j, j + lpr, ..; a pool's place in the row is the group's running sum of the pools' text lengths, an inclusive scan by lane
 // shuffles.  A pool's six counts stay in registers and every digit goes straight to its byte: no array, no scratch.
 #include "pg_common.h"
+#include "pg_text_steps.h"
 #include "pg_sync_fmt.h"
 
 namespace {
 
 constexpr int SF_THREADS = 256;
 constexpr int SF_TILE = 16384; // bytes of text a workgroup stages (plus up to 15 in front of them: the word it starts in)
-constexpr int SF_COUNT_SHIFT = 8, SF_COUNT_ROWS = 1 << SF_COUNT_SHIFT; // rows per workgroup of the scan's first level
-constexpr int SF_SCAN_WIDTH = 1024;                                    // workgroup sums per round of its second level
 constexpr int SF_BAD_NAME = 1, SF_BAD_LONG = 2;
-
-struct SfCtl { // the scan's results, read back by the host
-    int64_t total;
-    int32_t max_row;
-    int32_t bad;
-};
+// The two widths of the shared scan (pg_text_steps.h) under this file's names: tests/test_gpu_syncfmt.py reads them from this
+// source to place its row counts on both sides of a scan level.  They cannot drift from what the kernels are built with.
+constexpr int SF_COUNT_ROWS = 256, SF_SCAN_WIDTH = 1024;
+static_assert(SF_COUNT_ROWS == PG_COUNT_ROWS && SF_SCAN_WIDTH == PG_SCAN_WIDTH, "the scan widths of pg_text_steps.h");
 
 struct SfRows { // what a row is made of
     const unsigned char *slab;
@@ -45,13 +43,6 @@ struct SfRows { // what a row is made of
     int n;
 };
 
-// lanes per row: the smallest power of two that holds n, at most a wave
-int sf_lpr_shift(int n) {
-    int s = 0;
-    while (s < 6 && (1 << s) < n) ++s;
-    return s;
-}
-
 __device__ __forceinline__ void sf_load_pool(const uint32_t *__restrict__ p, uint32_t (&c)[6]) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) c[i] = p[i];
@@ -59,7 +50,7 @@ __device__ __forceinline__ void sf_load_pool(const uint32_t *__restrict__ p, uin
 
 // ---- measure -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SF_THREADS) void k_syncfmt_measure(const SfRows R, int64_t rows, int lpr_shift, int32_t *__restrict__ rowlen,
-                                                                SfCtl *__restrict__ ctl) {
+                                                                PgScanCtl *__restrict__ ctl) {
     const int lpr = 1 << lpr_shift;
     const int64_t gid = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x;
     const int64_t r = gid >> lpr_shift;
@@ -87,58 +78,6 @@ __global__ __launch_bounds__(SF_THREADS) void k_syncfmt_measure(const SfRows R, 
         rowlen[r] = (int32_t)len;
         if (bad) atomicOr(&ctl->bad, bad);
     }
-}
-
-// ---- scan: the block-scan pattern of pg_csv.hip's k_csv_count / k_csv_scan, in a copy of its own ------------------------------
-__global__ __launch_bounds__(SF_COUNT_ROWS) void k_syncfmt_count(int32_t *__restrict__ local, int64_t rows, int64_t *__restrict__ blocksum,
-                                                       SfCtl *__restrict__ ctl) {
-    __shared__ int sc[SF_COUNT_ROWS];
-    __shared__ int smax[SF_COUNT_ROWS];
-    const int tid = threadIdx.x;
-    const int64_t r = (int64_t)blockIdx.x * SF_COUNT_ROWS + tid;
-    const int c = r < rows ? local[r] : 0; // in: the row's length; out (same element, same thread): its offset inside the block
-    sc[tid] = c;
-    smax[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < SF_COUNT_ROWS; d <<= 1) {
-        const int v = tid >= d ? sc[tid - d] : 0;
-        const int m = tid >= d ? smax[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        smax[tid] = max(smax[tid], m);
-        __syncthreads();
-    }
-    if (r < rows) local[r] = sc[tid] - c;
-    if (tid == SF_COUNT_ROWS - 1) {
-        blocksum[blockIdx.x] = sc[SF_COUNT_ROWS - 1];
-        atomicMax(&ctl->max_row, smax[SF_COUNT_ROWS - 1]);
-    }
-}
-
-__global__ __launch_bounds__(SF_SCAN_WIDTH) void k_syncfmt_scan(const int64_t *__restrict__ blocksum, int64_t nb, int64_t *__restrict__ blockoff,
-                                                       SfCtl *__restrict__ ctl) {
-    __shared__ int64_t sc[SF_SCAN_WIDTH];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += SF_SCAN_WIDTH) {
-        const int64_t i = base + tid;
-        const int64_t c = i < nb ? blocksum[i] : 0;
-        sc[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < SF_SCAN_WIDTH; d <<= 1) {
-            const int64_t v = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += v;
-            __syncthreads();
-        }
-        if (i < nb) blockoff[i] = carry + sc[tid] - c;
-        __syncthreads();
-        if (tid == SF_SCAN_WIDTH - 1) carry += sc[SF_SCAN_WIDTH - 1];
-        __syncthreads();
-    }
-    if (tid == 0) ctl->total = carry;
 }
 
 // ---- emit --------------------------------------------------------------------------------------------------------------
@@ -175,46 +114,34 @@ __device__ __forceinline__ void sf_format_row(const SfRows &R, int64_t r, bool a
     }
 }
 
-__device__ __forceinline__ int64_t sf_row_off(const int32_t *__restrict__ local, const int64_t *__restrict__ blockoff, const SfCtl *ctl,
-                                              int64_t r, int64_t rows) {
-    return r < rows ? blockoff[r >> SF_COUNT_SHIFT] + local[r] : ctl->total;
-}
-
 enum { SF_STAGED = 0, SF_DIRECT = 1 }; // how k_syncfmt_emit takes its rows (the dispatch rule: pg_sync_format_rows_dev)
 
 template <int MODE>
 __global__ __launch_bounds__(SF_THREADS) void k_syncfmt_emit(const SfRows R, int64_t rows, int lpr_shift, int rpb,
                                                              const int32_t *__restrict__ local, const int64_t *__restrict__ blockoff,
-                                                             const SfCtl *__restrict__ ctl, unsigned char *__restrict__ text) {
+                                                             const PgScanCtl *__restrict__ ctl, unsigned char *__restrict__ text) {
     const int tid = threadIdx.x;
     if (MODE == SF_DIRECT) { // a wave per row, straight to the output
         const int64_t r = (int64_t)blockIdx.x * (SF_THREADS / 64) + (tid >> 6);
         const bool active = r < rows;
-        sf_format_row(R, r, active, tid & 63, 64, text + (active ? sf_row_off(local, blockoff, ctl, r, rows) : 0));
+        sf_format_row(R, r, active, tid & 63, 64, text + (active ? scan_off(local, blockoff, ctl, r, rows) : 0));
         return;
     }
     __shared__ __attribute__((aligned(16))) unsigned char tile[SF_TILE + 16];
     const int lpr = 1 << lpr_shift, ng = SF_THREADS >> lpr_shift;
     const int g = tid >> lpr_shift, gl = tid & (lpr - 1);
     const int64_t r_lo = (int64_t)blockIdx.x * rpb, r_hi = r_lo + rpb < rows ? r_lo + rpb : rows;
-    const int64_t B = sf_row_off(local, blockoff, ctl, r_lo, rows), E = sf_row_off(local, blockoff, ctl, r_hi, rows);
+    const int64_t B = scan_off(local, blockoff, ctl, r_lo, rows), E = scan_off(local, blockoff, ctl, r_hi, rows);
     const int head = (int)((reinterpret_cast<uintptr_t>(text) + (uint64_t)B) & 15); // tile[head + i] is byte B + i of the output
     for (int64_t r0 = r_lo; r0 < r_hi; r0 += ng) {                                  // uniform trip count
         const int64_t r = r0 + g;
         const bool active = r < r_hi;
-        const int at = active ? (int)(sf_row_off(local, blockoff, ctl, r, rows) - B) : 0;
+        const int at = active ? (int)(scan_off(local, blockoff, ctl, r, rows) - B) : 0;
         sf_format_row(R, r, active, gl, lpr, tile + head + at);
     }
     __syncthreads();
     const int nbytes = (int)(E - B);                                  // <= SF_TILE: rpb rows of at most the longest row's length
-    const int h = min(nbytes, (16 - head) & 15);                      // bytes in front of the first whole word
-    const int body = (nbytes - h) & ~15;                              // whole 16-byte words
-    unsigned char *out = text + B;
-    if (tid < h) out[tid] = tile[head + tid];
-    for (int i = tid * 16; i < body; i += SF_THREADS * 16)            // head + h is 0 or 16 whenever body > 0
-        *reinterpret_cast<uint4 *>(out + h + i) = *reinterpret_cast<const uint4 *>(tile + head + h + i);
-    const int tail = nbytes - h - body;                               // < 16
-    if (tid < tail) out[h + body + tid] = tile[head + h + body + tid];
+    tile_flush(tile, head, text + B, nbytes, tid, SF_THREADS);
 }
 
 } // namespace
@@ -235,46 +162,32 @@ extern "C" int pg_sync_format_rows_dev(pg_ctx *ctx, const char *slab_dev, int64_
     PG_CHECK(ctx, (slab_dev || slab_bytes == 0) && counts_dev && pos_dev && ref_dev && line_off_dev && chrom_len_dev,
              "sync_format_rows: null pointer");
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t nb = (rows + SF_COUNT_ROWS - 1) / SF_COUNT_ROWS;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t off = 0;
-    const size_t o_local = off; off = up16(off + sizeof(int32_t) * (size_t)rows);
-    const size_t o_bsum = off; off = up16(off + 8 * (size_t)nb);
-    const size_t o_boff = off; off = up16(off + 8 * (size_t)nb);
-    const size_t o_ctl = off; off = up16(off + sizeof(SfCtl));
-    const int rc = pg_ws_reserve(ctx, off);
+    PgLengthScan S;
+    int rc = S.prepare(ctx, rows);
     if (rc) return rc;
-    char *ws = static_cast<char *>(ctx->ws.get());
-    int32_t *local = reinterpret_cast<int32_t *>(ws + o_local);
-    int64_t *bsum = reinterpret_cast<int64_t *>(ws + o_bsum), *boff = reinterpret_cast<int64_t *>(ws + o_boff);
-    SfCtl *ctl = reinterpret_cast<SfCtl *>(ws + o_ctl);
     const SfRows R{reinterpret_cast<const unsigned char *>(slab_dev), slab_bytes, counts_dev, pos_dev, ref_dev, line_off_dev, chrom_len_dev, n_pools};
-    const int lpr_shift = sf_lpr_shift(n_pools);
-    PG_HIP(ctx, hipMemsetAsync(ctl, 0, sizeof(SfCtl), ctx->stream));
+    const int lpr_shift = pg_lpr_shift(n_pools, 0);
     const int64_t measure_blocks = ((rows << lpr_shift) + SF_THREADS - 1) / SF_THREADS;
     pg_prof_begin(ctx, PG_K_SYNCFMT);
-    hipLaunchKernelGGL(k_syncfmt_measure, dim3((unsigned)measure_blocks), dim3(SF_THREADS), 0, ctx->stream, R, rows, lpr_shift, local, ctl);
-    hipLaunchKernelGGL(k_syncfmt_count, dim3((unsigned)nb), dim3(SF_COUNT_ROWS), 0, ctx->stream, local, rows, bsum, ctl);
-    hipLaunchKernelGGL(k_syncfmt_scan, dim3(1), dim3(SF_SCAN_WIDTH), 0, ctx->stream, bsum, nb, boff, ctl);
+    hipLaunchKernelGGL(k_syncfmt_measure, dim3((unsigned)measure_blocks), dim3(SF_THREADS), 0, ctx->stream, R, rows, lpr_shift, S.local, S.ctl);
+    S.scan(ctx);
     pg_prof_end(ctx);
-    PG_HIP(ctx, hipGetLastError());
-    SfCtl res{};
-    PG_HIP(ctx, hipMemcpyAsync(&res, ctl, sizeof(SfCtl), hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PgScanCtl res{};
+    rc = S.read(ctx, &res);
+    if (rc) return rc;
     PG_CHECK(ctx, !(res.bad & SF_BAD_NAME), "sync_format_rows: a row's chromosome name (line_off, chrom_len) lies outside the slab");
     PG_CHECK(ctx, !(res.bad & SF_BAD_LONG), "sync_format_rows: a line of text is longer than %d bytes", PG_SYNCFMT_MAX_ROW);
     *bytes = res.total;
     PG_CHECK(ctx, res.total <= cap, "sync_format_rows: the text needs %lld bytes, the buffer holds %lld", (long long)res.total, (long long)cap);
     unsigned char *text = reinterpret_cast<unsigned char *>(text_dev);
     pg_prof_begin(ctx, PG_K_SYNCFMT | PG_PROF_CONT);
-    if (res.max_row > SF_TILE) { // the direct path: a row does not fit the tile
+    if (res.max > SF_TILE) { // the direct path: a row does not fit the tile
         const int64_t blocks = (rows + SF_THREADS / 64 - 1) / (SF_THREADS / 64);
-        hipLaunchKernelGGL(k_syncfmt_emit<SF_DIRECT>, dim3((unsigned)blocks), dim3(SF_THREADS), 0, ctx->stream, R, rows, 6, 0, local, boff, ctl, text);
+        hipLaunchKernelGGL(k_syncfmt_emit<SF_DIRECT>, dim3((unsigned)blocks), dim3(SF_THREADS), 0, ctx->stream, R, rows, 6, 0, S.local, S.boff, S.ctl, text);
     } else {
-        const int rpb = SF_TILE / std::max(1, res.max_row); // rows per workgroup: rpb rows of at most the longest row's length fit the tile
+        const int rpb = SF_TILE / std::max(1, res.max); // rows per workgroup: rpb rows of at most the longest row's length fit the tile
         const int64_t blocks = (rows + rpb - 1) / rpb;
-        hipLaunchKernelGGL(k_syncfmt_emit<SF_STAGED>, dim3((unsigned)blocks), dim3(SF_THREADS), 0, ctx->stream, R, rows, lpr_shift, rpb, local, boff,
-                           ctl, text);
+        hipLaunchKernelGGL(k_syncfmt_emit<SF_STAGED>, dim3((unsigned)blocks), dim3(SF_THREADS), 0, ctx->stream, R, rows, lpr_shift, rpb, S.local, S.boff, S.ctl, text);
     }
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());

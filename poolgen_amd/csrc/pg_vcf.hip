@@ -1,8 +1,9 @@
 // pg_vcf.hip -- vcf2sync's reader on the device: a slab of VCF text to the allele counts of the loci that VcfLine::filter keeps
-// (base/vcf.rs; the rules, shared with the host twin, are pg_vcf_line.h).  Four steps on the context's stream:
-//   index   k_vcf_index<false> (newlines per 4 KB of text: a lane reads one aligned 16-byte word) + k_vcf_scan (64-bit exclusive
-//           scan of the workgroups' sums, 1024 per round) + k_vcf_index<true> (the same read again, a block scan, and every
-//           newline writes the start of the line behind it): start[0 .. lines], no host work per line;
+// (base/vcf.rs; the rules, shared with the host twin, are pg_vcf_line.h).  Four steps on the context's stream;
+// the index, the scans and the lane-group steps are the shared ones of pg_text_steps.h:
+//   index   PgLineIndex: k_text_index<false> (newlines per 4 KB of text: a lane reads one aligned 16-byte word) + k_scan_blocks
+//           (64-bit exclusive scan of the workgroups' sums, 1024 per round) + k_text_index<true> (the same read again, a block scan,
+//           and every newline writes the start of the line behind it): start[0 .. lines], no host work per line;
 //   parse   k_vcf_parse<false>: a line is taken by a GROUP of lanes (8 .. 64, a power of two chosen from the number of pool sizes,
 //           so that 5 pools have 8 lines in a wave and 200 pools one line across it).  The group walks its line in chunks of one
 //           byte per lane; a ballot on '\t' and a popcount of the lower lanes give a byte's field index, and the field starts go
@@ -12,124 +13,28 @@
 //           formed in pool order, the terms passing through lane shuffles one after the other (a tree would be faster and not
 //           bit-equal).  One int per line comes out: kept, data line, number of samples; a line where the reference would
 //           panic enters (offset, reason) into one 64-bit atomicMin;
-//   scan    k_vcf_keep (exclusive scan of 256 keep flags per workgroup, data lines counted, sample numbers compared with the first
-//           data line's) + k_vcf_scan: a kept line's rank is blockoff[line >> 8] + local[line];
+//   scan    k_vcf_keep (scan_keep_flags: exclusive scan of 256 keep flags per workgroup, data lines counted; then, VCF's own, the
+//           sample numbers compared with the first data line's) + k_scan_blocks: a kept line's rank is scan_rank(local, blockoff, line);
 //   emit    k_vcf_parse<true>: the kept lines are split and read again (the text is in cache or cheap to fetch beside what a
 //           staging copy of every line's counts would cost) and write their rows at their rank.
 // No array is indexed at run time in a thread: a sample's numbers are the named members of PgVcfSample.
 #include "pg_common.h"
+#include "pg_text_steps.h"
 #include "pg_vcf_line.h"
 
 namespace {
 
 constexpr int VCF_THREADS = 256;
-constexpr int VCF_INFO_KEEP = 1, VCF_INFO_DATA = 2, VCF_INFO_HAS_N = 4, VCF_INFO_N_SHIFT = 3;
+constexpr int VCF_INFO_KEEP = PG_LINE_KEEP, VCF_INFO_DATA = PG_LINE_DATA, VCF_INFO_HAS_N = 4, VCF_INFO_N_SHIFT = 3;
 constexpr int VCF_N_BITS = 12; // the first data line's (offset << 12 | samples): samples <= PG_VCF_MAX_POOLS + 1 < 4096
 
 struct VcfCtl { // read back by the host
+    PgLineCounts n;
     unsigned long long err;     // pg_vcf_err_key of the first bad line, PG_VCF_NO_ERR without one
     unsigned long long first_n; // (offset << VCF_N_BITS | samples) of the first line with sample fields, ~0 without one
     unsigned long long chrom_key; // 1 + the offset of the last line that begins with #CHROM, 0 without one
-    long long newlines, lines, kept, data_lines;
+    int64_t kept, data_lines;
 };
-
-struct VcfText {
-    const unsigned char *text;
-    int64_t bytes;
-    int64_t head;    // text - head is 16-byte aligned
-    int64_t nchunks; // aligned 16-byte words that hold a byte of the text
-};
-
-// lanes per line: the smallest power of two that holds the pools, from 8 lanes to a wave
-int vcf_lpr_shift(int n) {
-    int s = 3;
-    while (s < 6 && (1 << s) < n) ++s;
-    return s;
-}
-
-// bit k = byte k of x is '\n'
-__device__ __forceinline__ unsigned vcf_nl4(unsigned x) {
-    const unsigned y = x ^ 0x0A0A0A0Au;
-    const unsigned z = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu); // 0x80 in every byte of y that is zero
-    return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u);
-}
-
-// the newlines among the bytes of aligned word c that belong to the text: bit k = position 16 c - head + k
-__device__ __forceinline__ unsigned vcf_nl_mask(const VcfText &T, int64_t c) {
-    if (c >= T.nchunks) return 0u;
-    const uint4 w = *reinterpret_cast<const uint4 *>(T.text - T.head + 16 * c); // whole inside the aligned words the text touches
-    unsigned m = vcf_nl4(w.x) | (vcf_nl4(w.y) << 4) | (vcf_nl4(w.z) << 8) | (vcf_nl4(w.w) << 12);
-    const int64_t p0 = 16 * c - T.head;
-    if (p0 < 0) m &= (0xffffu << (int)(-p0)) & 0xffffu;
-    if (p0 + 16 > T.bytes) m &= (1u << (int)(T.bytes - p0)) - 1u;
-    return m;
-}
-
-// ---- index ---------------------------------------------------------------------------------------------------------------
-template <bool EMIT>
-__global__ __launch_bounds__(VCF_THREADS) void k_vcf_index(const VcfText T, int64_t *__restrict__ blocksum, const int64_t *__restrict__ blockoff,
-                                                           const VcfCtl *__restrict__ ctl, int64_t *__restrict__ start) {
-    __shared__ int sc[VCF_THREADS];
-    const int tid = threadIdx.x;
-    const int64_t c = (int64_t)blockIdx.x * VCF_THREADS + tid;
-    unsigned m = vcf_nl_mask(T, c);
-    const int cnt = __popc(m);
-    sc[tid] = cnt;
-    __syncthreads();
-    for (int d = 1; d < VCF_THREADS; d <<= 1) {
-        const int v = tid >= d ? sc[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        __syncthreads();
-    }
-    if (!EMIT) {
-        if (tid == VCF_THREADS - 1) blocksum[blockIdx.x] = sc[VCF_THREADS - 1];
-        return;
-    }
-    int64_t rank = blockoff[blockIdx.x] + (sc[tid] - cnt); // newlines in front of this word
-    const int64_t p0 = 16 * c - T.head;
-    while (m) {
-        const int k = __ffs(m) - 1;
-        m &= m - 1u;
-        start[++rank] = p0 + k + 1; // rank + 1 <= newlines <= lines
-    }
-    if (c == 0) {
-        start[0] = 0;
-        if (ctl->lines > ctl->newlines) start[ctl->lines] = T.bytes + 1; // the last line lacks its newline: as if it stood at `bytes`
-    }
-}
-
-// exclusive 64-bit scan of the workgroups' sums (the pattern of k_csv_scan / k_load_scan, in a copy of its own); the total goes to
-// *total, and with `text` the number of lines to *lines
-__global__ __launch_bounds__(1024) void k_vcf_scan(const int64_t *__restrict__ blocksum, int64_t nb, int64_t *__restrict__ blockoff,
-                                                   long long *__restrict__ total, const unsigned char *__restrict__ text, int64_t bytes,
-                                                   long long *__restrict__ lines) {
-    __shared__ int64_t sc[1024];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += 1024) {
-        const int64_t i = base + tid;
-        const int64_t c = i < nb ? blocksum[i] : 0;
-        sc[tid] = c;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const int64_t v = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += v;
-            __syncthreads();
-        }
-        if (i < nb) blockoff[i] = carry + sc[tid] - c;
-        __syncthreads();
-        if (tid == 1023) carry += sc[1023];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        *total = carry;
-        if (text) *lines = carry + (text[bytes - 1] != '\n' ? 1 : 0);
-    }
-}
 
 // ---- parse and emit --------------------------------------------------------------------------------------------------------
 struct VcfRule {
@@ -153,16 +58,14 @@ struct VcfOut {
 enum { VCF_SKIP = 0, VCF_DROP = 1, VCF_KEEP = 2 }; // or minus a pg_vcf_reason
 
 template <bool EMIT>
-__global__ __launch_bounds__(VCF_THREADS) void k_vcf_parse(const VcfText T, const int64_t *__restrict__ start, int64_t lines, const VcfRule R,
+__global__ __launch_bounds__(VCF_THREADS) void k_vcf_parse(const PgText T, const int64_t *__restrict__ start, int64_t lines, const VcfRule R,
                                                            int shift, int32_t *__restrict__ info, VcfCtl *__restrict__ ctl,
                                                            const int32_t *__restrict__ local, const int64_t *__restrict__ blockoff,
                                                            const VcfOut O) {
     extern __shared__ int fs_all[];
     const int tid = threadIdx.x;
-    const int lpr = 1 << shift;
-    const int g = tid >> shift, gl = tid & (lpr - 1);
-    const int gbase = (tid & 63) & ~(lpr - 1); // the group's first lane in its wave
-    const uint64_t gmask = lpr == 64 ? ~0ULL : ((1ULL << lpr) - 1ULL);
+    const PgLaneGroup G = lane_group(tid, shift);
+    const int lpr = G.lpr, g = G.g, gl = G.gl;
     int *fs = fs_all + g * R.F;
     const int64_t line = (int64_t)blockIdx.x * (VCF_THREADS >> shift) + g;
     bool active = line < lines; // uniform over the group, as is everything decided from the line alone
@@ -171,10 +74,8 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_parse(const VcfText T, cons
     int res = VCF_SKIP, wlen = 0;
     bool data = false;
     if (active) {
-        s = start[line];
-        const int64_t e = start[line + 1] - 1; // the newline's place, or `bytes` for a last line without one
-        int64_t len = e - s;
-        if (e < T.bytes && len > 0 && T.text[e - 1] == '\r') --len;
+        int64_t len;
+        line_bounds(T, start, line, false, &s, &len); // a '\r' goes only with its newline (pg_hostvcf.cpp does the same)
         if (len == 0) res = -PG_VCF_E_EMPTY;
         else if (T.text[s] == '#') {
             if (!EMIT && gl == 0 && len >= 6 && T.text[s + 1] == 'C' && T.text[s + 2] == 'H' && T.text[s + 3] == 'R' && T.text[s + 4] == 'O' &&
@@ -183,23 +84,13 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_parse(const VcfText T, cons
         } else {
             data = true;
             if (len < PG_VCF_MIN_LINE) res = -PG_VCF_E_SHORT;
-            else if (len > 0x7fffffffLL) res = -PG_VCF_E_LONG;
+            else if (len > PG_LINE_MAX) res = -PG_VCF_E_LONG;
             else wlen = (int)len;
         }
     }
     const unsigned char *L = T.text + s;
     // the field starts: fs[f] = where field f begins, for f < F
-    int ntabs = 0;
-    for (int off = 0; off < wlen; off += lpr) { // (one trip count for the group; other groups of the wave may leave earlier)
-        const int idx = off + gl;
-        const bool tab = idx < wlen && L[idx] == '\t';
-        const uint64_t gb = ((uint64_t)__ballot(tab) >> gbase) & gmask;
-        if (tab) {
-            const int f = ntabs + __popcll(gb & ((1ULL << gl) - 1ULL)) + 1;
-            if (f < R.F) fs[f] = idx + 1;
-        }
-        ntabs += __popcll(gb);
-    }
+    const int ntabs = group_split_tabs(L, wlen, G, fs, R.F);
     if (gl == 0 && wlen > 0) fs[0] = 0;
     __syncthreads(); // every thread of the workgroup arrives: no path above returns
     int n = -1;
@@ -219,7 +110,7 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_parse(const VcfText T, cons
                 int covered = 0, ragged = 0, cov0 = 0;
                 double q = 0.0;
                 int64_t rank = 0;
-                if (EMIT) rank = blockoff[line >> 8] + local[line];
+                if (EMIT) rank = scan_rank(local, blockoff, line);
                 for (int j0 = 0; j0 < n; j0 += lpr) { // one trip count for the group
                     const int j = j0 + gl;
                     const bool have = j < n;
@@ -274,31 +165,11 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_parse(const VcfText T, cons
     }
 }
 
-// ---- scan of the keep flags (k_csv_count's pattern) -----------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_vcf_keep(const int32_t *__restrict__ info, int64_t lines, const int64_t *__restrict__ start,
-                                                  int32_t *__restrict__ local, int64_t *__restrict__ blocksum, VcfCtl *__restrict__ ctl) {
-    __shared__ int sc[256];
-    __shared__ int sd[256];
-    const int tid = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-    const int v = i < lines ? info[i] : 0;
-    const int c = v & VCF_INFO_KEEP;
-    sc[tid] = c;
-    sd[tid] = (v & VCF_INFO_DATA) ? 1 : 0;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const int a = tid >= d ? sc[tid - d] : 0;
-        const int b = tid >= d ? sd[tid - d] : 0;
-        __syncthreads();
-        sc[tid] += a;
-        sd[tid] += b;
-        __syncthreads();
-    }
-    if (i < lines) local[i] = sc[tid] - c;
-    if (tid == 255) {
-        blocksum[blockIdx.x] = sc[255];
-        if (sd[255]) atomicAdd(reinterpret_cast<unsigned long long *>(&ctl->data_lines), (unsigned long long)sd[255]);
-    }
+// ---- scan of the keep flags, and VCF's own tail: every line has the first data line's number of samples ---------------------
+__global__ __launch_bounds__(PG_COUNT_ROWS) void k_vcf_keep(const int32_t *__restrict__ info, int64_t lines, const int64_t *__restrict__ start,
+                                                            int32_t *__restrict__ local, int64_t *__restrict__ blocksum, VcfCtl *__restrict__ ctl) {
+    const int64_t i = (int64_t)blockIdx.x * PG_COUNT_ROWS + threadIdx.x;
+    const int v = scan_keep_flags(info, lines, local, blocksum, &ctl->data_lines);
     if ((v & VCF_INFO_HAS_N) && (v >> VCF_INFO_N_SHIFT) != (int)(ctl->first_n & ((1u << VCF_N_BITS) - 1u))) // (first_n is complete: the parse kernel is over)
         atomicMin(&ctl->err, (unsigned long long)pg_vcf_err_key(start[i], PG_VCF_E_POOLS));
 }
@@ -339,64 +210,27 @@ extern "C" int pg_vcf_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t bytes
     PG_CHECK(ctx, bytes < ((int64_t)1 << 40), "vcf_parse: a slab of %lld bytes; cut the text at line starts into slabs below 2^40", (long long)bytes);
     if (bytes == 0) return PG_OK;
     PG_HIP(ctx, hipSetDevice(ctx->device));
-    VcfText T;
-    T.text = reinterpret_cast<const unsigned char *>(text_dev);
-    T.bytes = bytes;
-    T.head = (int64_t)(reinterpret_cast<uintptr_t>(text_dev) & 15);
-    T.nchunks = (bytes + T.head + 15) / 16;
-    const int64_t nbi = (T.nchunks + VCF_THREADS - 1) / VCF_THREADS;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t off = 0;
-    const size_t o_ctl = off; off = up16(off + sizeof(VcfCtl));
-    const size_t o_sizes = off; off = up16(off + sizeof(double) * (size_t)n_sizes);
-    const size_t o_bsi = off; off = up16(off + 8 * (size_t)nbi);
-    const size_t o_boi = off; off = up16(off + 8 * (size_t)nbi);
-    const size_t front = off;
-    int rc = pg_ws_reserve(ctx, front);
-    if (rc) return rc;
+    const PgText T = pg_text(text_dev, bytes);
+    const size_t o_sizes = pg_up16(sizeof(VcfCtl)), front_bytes = o_sizes + sizeof(double) * (size_t)n_sizes; // the front block: VcfCtl, the pool sizes
     VcfCtl init{};
     init.err = PG_VCF_NO_ERR;
     init.first_n = ~0ULL;
-    auto count_lines = [&]() -> hipError_t { // the control block, the pool sizes, the newlines of every 4 KB and their scan
-        char *ws = static_cast<char *>(ctx->ws.get());
-        hipError_t e = hipMemcpyAsync(ws + o_ctl, &init, sizeof(VcfCtl), hipMemcpyHostToDevice, ctx->stream);
+    auto front = [&](char *ws, auto count_lines) -> hipError_t {
+        hipError_t e = hipMemcpyAsync(ws, &init, sizeof(VcfCtl), hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return e;
         e = hipMemcpyAsync(ws + o_sizes, pool_sizes, sizeof(double) * (size_t)n_sizes, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return e;
-        VcfCtl *ctl = reinterpret_cast<VcfCtl *>(ws + o_ctl);
-        hipLaunchKernelGGL(k_vcf_index<false>, dim3((unsigned)nbi), dim3(VCF_THREADS), 0, ctx->stream, T, reinterpret_cast<int64_t *>(ws + o_bsi),
-                           (const int64_t *)nullptr, (const VcfCtl *)nullptr, (int64_t *)nullptr);
-        hipLaunchKernelGGL(k_vcf_scan, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const int64_t *>(ws + o_bsi), nbi,
-                           reinterpret_cast<int64_t *>(ws + o_boi), &ctl->newlines, T.text, bytes, &ctl->lines);
+        count_lines(PgNoHook());
         return hipGetLastError();
     };
     VcfCtl res{};
-    pg_prof_begin(ctx, PG_K_VCF);
-    PG_HIP(ctx, count_lines());
-    pg_prof_end(ctx);
-    PG_HIP(ctx, hipMemcpyAsync(&res, static_cast<char *>(ctx->ws.get()) + o_ctl, sizeof(VcfCtl), hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t lines = res.lines;
-    PG_CHECK(ctx, lines >= 1 && lines <= bytes && res.newlines <= lines, "vcf_parse: internal error, %lld lines in %lld bytes", (long long)lines, (long long)bytes);
-    const int64_t nbk = (lines + 255) / 256;
-    const size_t o_start = off; off = up16(off + 8 * (size_t)(lines + 2));
-    const size_t o_info = off; off = up16(off + 4 * (size_t)lines);
-    const size_t o_local = off; off = up16(off + 4 * (size_t)lines);
-    const size_t o_bsk = off; off = up16(off + 8 * (size_t)nbk);
-    const size_t o_bok = off; off = up16(off + 8 * (size_t)nbk);
-    const size_t before = ctx->ws.bytes();
-    rc = pg_ws_reserve(ctx, off);
+    PgLineIndex X;
+    int rc = X.build(ctx, PG_K_VCF, "vcf_parse", T, front_bytes, front, &res);
     if (rc) return rc;
-    pg_prof_begin(ctx, PG_K_VCF | PG_PROF_CONT);
-    if (ctx->ws.bytes() != before) PG_HIP(ctx, count_lines()); // the workspace was replaced by a larger block (wherever that one lies): its front part again (the same numbers)
-    char *ws = static_cast<char *>(ctx->ws.get());
-    VcfCtl *ctl = reinterpret_cast<VcfCtl *>(ws + o_ctl);
-    int64_t *start = reinterpret_cast<int64_t *>(ws + o_start), *bsk = reinterpret_cast<int64_t *>(ws + o_bsk), *bok = reinterpret_cast<int64_t *>(ws + o_bok);
-    int32_t *linfo = reinterpret_cast<int32_t *>(ws + o_info), *local = reinterpret_cast<int32_t *>(ws + o_local);
-    hipLaunchKernelGGL(k_vcf_index<true>, dim3((unsigned)nbi), dim3(VCF_THREADS), 0, ctx->stream, T, (int64_t *)nullptr,
-                       reinterpret_cast<const int64_t *>(ws + o_boi), (const VcfCtl *)ctl, start);
+    const int64_t lines = X.lines;
+    VcfCtl *ctl = reinterpret_cast<VcfCtl *>(X.ws);
     VcfRule R;
-    R.sizes = reinterpret_cast<const double *>(ws + o_sizes);
+    R.sizes = reinterpret_cast<const double *>(X.ws + o_sizes);
     R.n_sizes = n_sizes;
     R.F = n_sizes + PG_VCF_FIXED_FIELDS + 1;
     R.depth = min_coverage_depth;
@@ -404,17 +238,19 @@ extern "C" int pg_vcf_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t bytes
     R.maf = min_allele_frequency;
     R.sizes_sum = 0.0;
     for (int i = 0; i < n_sizes; ++i) R.sizes_sum += pool_sizes[i];
-    const int shift = vcf_lpr_shift(n_sizes);
+    const int shift = pg_lpr_shift(n_sizes, 3); // so that 5 pools have 8 lines in a wave and 200 pools one line across it
     const int lines_per_block = VCF_THREADS >> shift;
-    const int64_t nbp = (lines + lines_per_block - 1) / lines_per_block;
-    PG_CHECK(ctx, nbp < ((int64_t)1 << 31), "vcf_parse: %lld lines in one slab; cut the text into smaller slabs", (long long)lines);
+    int64_t nbp;
+    rc = X.parse_blocks(ctx, "vcf_parse", lines_per_block, &nbp);
+    if (rc) return rc;
     const size_t lds = sizeof(int) * (size_t)lines_per_block * (size_t)R.F; // at most 32 x 18 or 4 x 2058 ints
     const VcfOut none{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    hipLaunchKernelGGL(k_vcf_parse<false>, dim3((unsigned)nbp), dim3(VCF_THREADS), lds, ctx->stream, T, (const int64_t *)start, lines, R, shift, linfo,
+    pg_prof_begin(ctx, PG_K_VCF | PG_PROF_CONT);
+    hipLaunchKernelGGL(k_vcf_parse<false>, dim3((unsigned)nbp), dim3(VCF_THREADS), lds, ctx->stream, T, (const int64_t *)X.start, lines, R, shift, X.info,
                        ctl, (const int32_t *)nullptr, (const int64_t *)nullptr, none);
-    hipLaunchKernelGGL(k_vcf_keep, dim3((unsigned)nbk), dim3(256), 0, ctx->stream, (const int32_t *)linfo, lines, (const int64_t *)start, local, bsk, ctl);
-    hipLaunchKernelGGL(k_vcf_scan, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)bsk, nbk, bok, &ctl->kept, (const unsigned char *)nullptr,
-                       (int64_t)0, (long long *)nullptr);
+    hipLaunchKernelGGL(k_vcf_keep, dim3((unsigned)X.nbk), dim3(PG_COUNT_ROWS), 0, ctx->stream, (const int32_t *)X.info, lines, (const int64_t *)X.start,
+                       X.local, X.bsk, ctl);
+    X.scan_kept(ctx, &ctl->kept);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
     PG_HIP(ctx, hipMemcpyAsync(&res, ctl, sizeof(VcfCtl), hipMemcpyDeviceToHost, ctx->stream));
@@ -436,8 +272,8 @@ extern "C" int pg_vcf_parse_dev(pg_ctx *ctx, const char *text_dev, int64_t bytes
     PG_CHECK(ctx, pos_dev && ref_dev && line_off_dev && chrom_len_dev && (need_counts == 0 || counts_dev), "vcf_parse: null output buffer");
     const VcfOut O{counts_dev, pos_dev, ref_dev, line_off_dev, chrom_len_dev, (int)info->n_pools};
     pg_prof_begin(ctx, PG_K_VCF | PG_PROF_CONT);
-    hipLaunchKernelGGL(k_vcf_parse<true>, dim3((unsigned)nbp), dim3(VCF_THREADS), lds, ctx->stream, T, (const int64_t *)start, lines, R, shift, linfo, ctl,
-                       (const int32_t *)local, (const int64_t *)bok, O);
+    hipLaunchKernelGGL(k_vcf_parse<true>, dim3((unsigned)nbp), dim3(VCF_THREADS), lds, ctx->stream, T, (const int64_t *)X.start, lines, R, shift, X.info, ctl,
+                       (const int32_t *)X.local, (const int64_t *)X.bok, O);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());
     return PG_OK;

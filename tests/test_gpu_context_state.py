@@ -17,6 +17,7 @@ on history by design and has its own test, test_gpu_locus_ops.py::test_kernel_ch
 import contextlib
 import ctypes as C
 import gc
+import random
 import time
 
 import numpy as np
@@ -24,6 +25,7 @@ import pytest
 import torch
 
 import dispatch_rules as R
+import pileup_corpus
 import sync_corpus
 import vcf_corpus
 from test_gpu_kinship_path import cmp_fit, make
@@ -406,6 +408,13 @@ def vcf_text(n, lines, seed):
     return (vcf_corpus.HEADER + vcf_corpus.chrom_line(n) + block * max(1, lines // BLOCK)).encode("latin-1")
 
 
+def pileup_text(n, lines, seed):
+    rng = random.Random(seed)
+    block = b"".join(pileup_corpus.good_line(rng, n) + b"\n" for _ in range(min(lines, BLOCK)))   # short read strings: 1 to 12 reads a pool
+    assert lines <= BLOCK or lines % BLOCK == 0
+    return block * max(1, lines // BLOCK)
+
+
 def sync_op(n, lines, seed):
     text = cached(("sync", n, lines, seed), lambda: sync_text(n, lines, seed))
 
@@ -431,6 +440,21 @@ def vcf_op(n, lines, seed):
         same(got, want, f"vcf {lines} lines")
         assert got["data_lines"] == lines and 0 < len(want["pos"]) < lines, (got["data_lines"], len(want["pos"]))
     return Op(f"vcf_parse n={n} lines={lines}", lambda e: e.vcf_parse(text, sizes, 30, 0.75, 0.1), check)
+
+
+def pileup_op(n, lines, seed):
+    text = cached(("pileup", n, lines, seed), lambda: pileup_text(n, lines, seed))
+    sizes = [1.0 / n] * n
+    rule = dict(pileup_corpus.BASE)
+
+    def check(res):
+        from poolgen_amd import pileup_parse_host
+        from test_gpu_pileup_parse import same
+        got = dict(res); got["counts"] = got["counts"].view(np.uint32); got["pos"] = got["pos"].view(np.uint64)
+        want = pileup_parse_host(text, sizes, **rule, n_threads=16)
+        same(got, want, f"pileup {lines} lines")
+        assert got["lines"] == lines and 0 < len(want["pos"]) <= lines, (got["lines"], len(want["pos"]))
+    return Op(f"pileup_parse n={n} lines={lines}", lambda e: e.pileup_parse(text, sizes, **rule), check)
 
 
 def ridge_op(n, p, seed, n_folds=3, G=None, Y=None, tag=""):
@@ -835,12 +859,12 @@ def test_large_then_small_popgen_and_csv(engine, name):
     large_then_small(small, large)
 
 
-@pytest.mark.parametrize("parser", ["sync_parse", "vcf_parse"])
+@pytest.mark.parametrize("parser", ["sync_parse", "vcf_parse", "pileup_parse"])
 def test_large_then_small_parsers(parser):
     """a text of a few hundred lines against one of 20 000: the second reservation of the large call replaces the workspace the
-    first one filled (pg_sync.hip / pg_vcf.hip rebuild the front part whenever that happened), and the small call after it parses
+    first one filled (PgLineIndex of pg_text_steps.h rebuilds the front part whenever that happened), and the small call after it parses
     inside a workspace full of the large one's line tables"""
-    mk = sync_op if parser == "sync_parse" else vcf_op
+    mk = {"sync_parse": sync_op, "vcf_parse": vcf_op, "pileup_parse": pileup_op}[parser]
     small, large = mk(5, 300, 21), mk(5, 20000, 22)
     reference(large)
     large_then_small(small, large)

@@ -65,6 +65,24 @@ def test_pool_counts_at_the_lane_group_steps(engine, n):
     same(as_numpy(engine.vcf_parse(text, sizes, 30, 0.75, 0.1)), want, n)
 
 
+def test_every_alignment_of_the_text(engine):
+    """slices of one device tensor that start at each of 16 consecutive bytes, the last line with and without its newline"""
+    from poolgen_amd import vcf_parse_host
+    rng = np.random.default_rng(5)
+    sizes = [10.0, 20.0, 30.0, 40.0, 50.0]
+    body = (vcf_corpus.chrom_line(5) + "".join(vcf_corpus.data_line(rng, 5, short_ad=i % 4 == 3) for i in range(11))).encode("latin-1")
+    for text in (body, body[:-1]):
+        dev = torch.frombuffer(bytearray(b"#" * 31 + b"\n" + text), dtype=torch.uint8).cuda()
+        seen = set()
+        for a in range(16):
+            t = dev[a:]                                         # a comment line of 32 - a bytes in front
+            seen.add(t.data_ptr() % 16)
+            want = vcf_parse_host(b"#" * (31 - a) + b"\n" + text, sizes, 1, 0.5, 0.0, n_threads=1)
+            assert 0 < len(want["pos"]) < 11
+            same(as_numpy(engine.vcf_parse(t, sizes, 1, 0.5, 0.0)), want, (a, len(text)))
+        assert len(seen) == 16
+
+
 def one_pool_text(lines):
     """`lines` data lines of one pool whose answer is known by construction: AD = i % 7, i % 5"""
     i = np.arange(lines)
