@@ -11,7 +11,7 @@
 // loci and a pair (bi <= bj) of pool blocks (a block = up to `Tb` 16-pool tiles).  For
 // n <= 208 pools there is a single block: the workgroup holds the WHOLE upper triangle of S
 // (<= 91 tiles, <= 6 per wave, 4 fp64 accumulators per lane per tile) in registers while it
-// streams its loci once from HBM through a double-buffered LDS stage (16 loci per stage).
+// streams its loci once from HBM through a double-buffered LDS stage (16 loci per stage; 32 in the 13-tile kernels).
 // The contraction is MFMA-bound (intensity n/4 flop per byte); HBM traffic is the single read
 // of G.  Each workgroup finally writes its partial tiles to a slab; a second tiny kernel sums
 // the slabs in a fixed order (deterministic, no atomics) and mirrors the lower triangle.
@@ -36,7 +36,12 @@ constexpr int KIN_TPW = 96 / KIN_WAVES;  // max tiles per wave (>= ceil(91 / wav
 #define KIN_KC_DEF 16
 #endif
 constexpr int KIN_KC = KIN_KC_DEF;  // loci per LDS stage (4 loci = one MFMA k-step)
-constexpr int KIN_PPT = (KIN_KC * 128 + KIN_THREADS - 1) / KIN_THREADS;  // 16-byte staging pieces per thread per stage
+constexpr int KIN_PPT = (KIN_KC * 128 + KIN_THREADS - 1) / KIN_THREADS;  // 16-byte staging pieces per thread per stage (13-tile kernels: per staging half)
+// The 13-tile kernels (193..208 pools, 16 waves) run stages of 32 loci: one barrier and one hand-over per 32 loci, and two loci
+// per wave for the fused sums.  They are STAGED in halves of KIN_KC loci (same registers, same pieces per thread), and the
+// launcher's slab rule stays in units of KIN_KC, so a slab may end in a half stage, which the kernel peels.
+constexpr int KC13 = 32;
+constexpr bool KIN_HAS13 = (KIN_WAVES == 16); // (the 8-wave build never runs the 13-tile shape and does not build its kernels)
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int uint4_t __attribute__((ext_vector_type(4)));
@@ -288,8 +293,8 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
 
     const int64_t l_begin = (int64_t)bx * loci_per_wg;
     const int64_t l_end = min(P.p, l_begin + loci_per_wg);
-    const int nstages = (l_end > l_begin) ? (int)((l_end - l_begin + KIN_KC - 1) / KIN_KC) : 0;
-    const int bufsz = KIN_KC * ldsld;
+    const int nstages = (l_end > l_begin) ? (int)((l_end - l_begin + KIN_KC - 1) / KIN_KC) : 0; // (SPEC13: half stages)
+    const int bufsz = (SPEC13 ? KC13 : KIN_KC) * ldsld;
 
     // zero both buffers once: the padding columns must stay zero for the edge tiles
     for (int i = tid; i < 2 * bufsz; i += KIN_THREADS) lds[i] = 0.0;
@@ -331,6 +336,19 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
     if (nstages > 0) {
         stage_load(0);
         stage_store(0);
+    }
+    if constexpr (SPEC13) { // the second half of the first 32-locus stage: rows KIN_KC .. of buffer 0
+        if (nstages > 1) {
+            stage_load(1);
+#pragma unroll
+            for (int r = 0; r < KIN_PPT; ++r) {
+                if (st_on[r]) {
+                    uint4_t v = stage_reg[r];
+                    if (!st_two[r]) { v.z = 0u; v.w = 0u; }
+                    *reinterpret_cast<uint4_t *>(&lds[(KIN_KC + st_loc[r]) * ldsld + st_lcol[r]]) = v;
+                }
+            }
+        }
     }
     __syncthreads();
 
@@ -424,46 +442,62 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
             // feeds its <= 6 tiles from them.  The stage barrier sits in front of the LAST k-step's MFMAs: their
             // operands are already in registers, and the first reads of the next stage hide behind them.
             constexpr int NC = kin13_ncols(W), NT = kin13_ntiles(W);
-            static_assert(NC <= KIN13_MAXC && KS % 2 == 0, "fragment sets alternate with the k-step parity");
-            // Both stage buffers, every k-step and every tile column are COMPILE-TIME offsets from a per-lane base that is set once:
-            // the stage loop runs two stages per trip (buffer 0, then buffer 1), so a fragment, strip, rotated-diagonal, staging-store
-            // or fused-sum row address is "base register + immediate" (2 x 16 x 208 x 8 = 53 248 bytes: inside the 16-bit offset
-            // field of the LDS instructions) and no address is rebuilt per stage.
-            constexpr int LD13 = 208, BUF13 = KIN_KC * LD13; // row pitch and doubles per stage buffer of the 13-tile shape
+            static_assert(KIN_WAVES == 16 && KC13 == 2 * KIN_KC && KC13 == 2 * KIN_WAVES, "a 32-locus stage: two staging halves, two loci per wave");
+            static_assert(NC <= KIN13_MAXC, "fragment registers");
+            // A stage is KC13 = 32 loci (8 k-steps, one barrier).  Within ONE stage buffer every k-step, tile column, staging row and
+            // fused-sum row is a COMPILE-TIME offset from a per-lane base, so a fragment, strip, rotated-diagonal, staging-store or
+            // fused-sum row address is "base register + immediate" (32 x 208 x 8 = 53 248 bytes per buffer: inside the 16-bit offset
+            // field of the LDS instructions).  The two buffers together (106 496 bytes) are not, so every base is FLIPPED to the other
+            // buffer once per stage with one v_add_u32 (at the barrier; the loop runs two stages per trip, so the sign of the flip is
+            // compile-time: + in the stage that computes from buffer 0, - in the other).  The flipped value goes through an empty asm
+            // statement: without it the compiler sees that "base + BUF - BUF" is loop-invariant and keeps BOTH values of every base
+            // in registers, which the fused kernel does not have.
+            constexpr int LD13 = 208, HALF13 = KIN_KC * LD13, BUF13 = KC13 * LD13; // row pitch, doubles per staging half and per stage buffer
+            constexpr int KSW = KC13 / 4, KSH = KIN_KC / 4;                        // k-steps of a whole stage and of a half stage
+            static_assert(KSW % 2 == 0 && KSH % 2 == 0, "fragment sets alternate with the k-step parity");
+            static_assert(BUF13 * 8 < 65536, "a stage buffer must lie inside the 16-bit offset field of the LDS instructions");
+            typedef __attribute__((address_space(3))) double lds_f64;
+            typedef __attribute__((address_space(3))) uint4_t lds_u128;
             // One ds_read_b64 per operand, its whole offset in the instruction: left to itself the compiler pairs the reads into
             // ds_read2_b64, whose two 8-bit offsets reach 2 040 bytes -- a k-step is 6 656 bytes from the next -- and pays for every
-            // pair with a v_add_u32 that builds its base (or, the bases being loop-invariant now, with a register each: 297 spills).
-            auto ldv = [](const double *q) __attribute__((always_inline)) { return *(const volatile __attribute__((address_space(3))) double *)q; };
+            // pair with a v_add_u32 that builds its base.  `base` is a byte address in LDS, `d` an offset in doubles.
+            auto ldv = [](uint32_t base, int d) __attribute__((always_inline)) { return *(const volatile lds_f64 *)(base + (uint32_t)(d * 8)); };
+            auto flip = [](uint32_t &base, auto up) __attribute__((always_inline)) {
+                if constexpr (decltype(up)::value) base += (uint32_t)(BUF13 * 8);
+                else base -= (uint32_t)(BUF13 * 8);
+                asm("" : "+v"(base));
+            };
+            const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_f64 *)lds;
             double fr[2][KIN13_MAXC];
-            const double *lb = lds + kq * LD13 + fi;
+            uint32_t lb = lds0 + (uint32_t)((kq * LD13 + fi) * 8);
             // which of this wave's tiles are strip tiles (r, 12), r < 12
             constexpr bool has_strip = [] { bool h = false; for (int u = 0; u < 6; ++u) h = h || (KIN13_T[W][u][0] >= 0 && KIN13_T[W][u][0] < 12 && KIN13_T[W][u][1] == 12); return h; }();
             double bs[2][2];                          // strip B operands: pools 192 + 4 c + (lane & 3), c = 0, 1
-            const double *lbs = lds + kq * LD13 + 192 + (lane & 3);
+            uint32_t lbs = lds0 + (uint32_t)((kq * LD13 + 192 + (lane & 3)) * 8);
             // diagonal tiles: the B operands of the block diagonals d = 1, 2 = the tile's fragment rotated by 4 d lanes inside its
             // 16-lane row.  Read from LDS at the rotated address (a DPP rotation is VALU work on the port the MFMAs issue from:
             // measured, it ate the saving)
             constexpr int ND = (SMALL & 1) ? kin13_ndiag(W) : 0;
             double bd[2][ND > 0 ? ND : 1][2];
-            const double *lbr1 = lds + kq * LD13 + ((fi + 4) & 15), *lbr2 = lds + kq * LD13 + ((fi + 8) & 15);
-            auto load_set = [&](auto bc, auto sc, auto pc) __attribute__((always_inline)) {
+            uint32_t lbr1 = lds0 + (uint32_t)((kq * LD13 + ((fi + 4) & 15)) * 8), lbr2 = lds0 + (uint32_t)((kq * LD13 + ((fi + 8) & 15)) * 8);
+            auto load_set = [&](auto sc, auto pc) __attribute__((always_inline)) { // k-step sc of the buffer the bases point at
                 constexpr int s2 = decltype(sc)::value, par = decltype(pc)::value;
-                constexpr int o = decltype(bc)::value * BUF13 + 4 * s2 * LD13; // buffer and k-step
+                constexpr int o = 4 * s2 * LD13;
                 static_for<NC>([&](auto cc) __attribute__((always_inline)) {
                     constexpr int ci = decltype(cc)::value;
-                    fr[par][ci] = ldv(lb + (o + 16 * kin13_col(W, ci)));
+                    fr[par][ci] = ldv(lb, o + 16 * kin13_col(W, ci));
                 });
                 if constexpr ((SMALL & 2) != 0 && has_strip) {
-                    bs[par][0] = ldv(lbs + o);
-                    bs[par][1] = ldv(lbs + (o + 4));
+                    bs[par][0] = ldv(lbs, o);
+                    bs[par][1] = ldv(lbs, o + 4);
                 }
                 if constexpr (ND > 0) {
                     static_for<NT>([&](auto uc) __attribute__((always_inline)) {
                         constexpr int u = decltype(uc)::value;
                         if constexpr (KIN13_T[W][u][0] == KIN13_T[W][u][1]) {
                             constexpr int di = kin13_diag_index(W, u);
-                            bd[par][di][0] = ldv(lbr1 + (o + 16 * KIN13_T[W][u][0]));
-                            bd[par][di][1] = ldv(lbr2 + (o + 16 * KIN13_T[W][u][0]));
+                            bd[par][di][0] = ldv(lbr1, o + 16 * KIN13_T[W][u][0]);
+                            bd[par][di][1] = ldv(lbr2, o + 16 * KIN13_T[W][u][0]);
                         }
                     });
                 }
@@ -487,21 +521,22 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                     }
                 });
             };
-            // ---- staging of this wave's pieces.  193..208 pools are 97..104 pieces per locus row, 1552..1664 per stage, so with the
+            // ---- staging of this wave's pieces.  193..208 pools are 97..104 pieces per locus row, 1552..1664 per staging half (KIN_KC loci), so with the
             // wave known at compile time piece r of its lanes is on in every lane (kind 2: no predicate at all), in no lane (kind 0: the
             // piece does not exist for this wave -- no load, no store, no registers) or decided per lane (kind 1: under the exec mask).
-            // The byte offset of a piece is a kept register that advances by one stage per load.
+            // The byte offset of a piece is a kept register that advances by one staging half (KIN_KC loci) per load: a stage is
+            // staged as two halves one after the other through the SAME registers, pieces and kinds.
             constexpr auto st_kind = [](int r) { const int t0 = W * 64 + r * KIN_THREADS; return t0 + 63 < KIN_KC * 97 ? 2 : (t0 >= KIN_KC * 104 ? 0 : 1); };
             uint4_t sreg[KIN_PPT];
             uint32_t voff[KIN_PPT];
-            uint4_t *sdst[KIN_PPT];
+            uint32_t sdst[KIN_PPT]; // byte address of the piece in the buffer that is NOT computed from (flipped with the other bases)
 #pragma unroll
             for (int r = 0; r < KIN_PPT; ++r) {
                 sreg[r] = (uint4_t){0u, 0u, 0u, 0u};
-                voff[r] = st_voff[r];
-                sdst[r] = reinterpret_cast<uint4_t *>(&lds[st_loc[r] * LD13 + st_lcol[r]]); // 16-byte aligned: even column, pitch 208
+                voff[r] = st_voff[r] + stage_stride; // (both halves of the first stage were staged by the prologue)
+                sdst[r] = lds0 + (uint32_t)((BUF13 + st_loc[r] * LD13 + st_lcol[r]) * 8); // 16-byte aligned: even column, pitch 208
             }
-            auto st_load = [&]() __attribute__((always_inline)) { // the pieces of the NEXT stage
+            auto st_load = [&]() __attribute__((always_inline)) { // the pieces of the next half of the NEXT stage
                 static_for<KIN_PPT>([&](auto rc) __attribute__((always_inline)) {
                     constexpr int r = decltype(rc)::value;
                     if constexpr (st_kind(r) == 2) {
@@ -515,8 +550,8 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                     }
                 });
             };
-            auto st_store = [&](auto bc) __attribute__((always_inline)) {
-                constexpr int B = decltype(bc)::value;
+            auto st_store = [&](auto hc) __attribute__((always_inline)) { // into half hc of the other buffer
+                constexpr int H = decltype(hc)::value;
                 static_for<KIN_PPT>([&](auto rc) __attribute__((always_inline)) {
                     constexpr int r = decltype(rc)::value;
                     if constexpr (st_kind(r) != 0) {
@@ -524,7 +559,7 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                         if constexpr (ODDN) { // the last piece of a row of an odd pool count carries one pool
                             if (!st_two[r]) { v.z = 0u; v.w = 0u; }
                         }
-                        if (st_kind(r) == 2 || st_on[r]) sdst[r][B * (BUF13 / 2)] = v;
+                        if (st_kind(r) == 2 || st_on[r]) *(lds_u128 *)(sdst[r] + (uint32_t)(H * HALF13 * 8)) = v;
                     }
                 });
             };
@@ -532,75 +567,147 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
             // pool pointer.  A lane of the fourth 64-pool group that lies past the last pool reads column 0, the shift itself: its
             // d is +0.0 as in spec_pass, without a clamp or a select.  The sums leave through a buffer descriptor that ends with this
             // workgroup's loci (a locus past the end is out of range and dropped by the hardware), offset and lane predicate kept.
-            const double *srow = lds + lane, *srow3 = lds + (lane + 192 < P.n ? lane + 192 : 0);
+            uint32_t srow = lds0 + (uint32_t)(lane * 8), srow3 = lds0 + (uint32_t)((lane + 192 < P.n ? lane + 192 : 0) * 8);
             const bool sp_on = (lane & 15) == 15 && (lane >> 4) < NV;
             uint32_t sp_voff = (uint32_t)((W * NV + (lane >> 4)) * 8);
-            const uint32_t sp_stride = (uint32_t)(KIN_KC * NV * 8);
             const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
                 FUSE ? P.spec + l_begin * NV : nullptr, 0, FUSE ? (int)(uint32_t)((uint64_t)(l_end > l_begin ? l_end - l_begin : 0) * NV * 8) : 0, 0x00020000);
             const double *sc13 = scratch + (lane >> 4) * 64 + (lane & 15);
-            auto spec13 = [&](auto bc) __attribute__((always_inline)) {
-                static_for<KIN_KC / KIN_WAVES>([&](auto jc) __attribute__((always_inline)) {
-                    constexpr int jl = decltype(jc)::value;
-                    constexpr int ro = decltype(bc)::value * BUF13 + (W + KIN_WAVES * jl) * LD13;
-                    const double shift = ldv(lds + ro); // same address in every lane: an LDS broadcast
-                    double s1 = 0.0, s2 = 0.0, sy[KIN_FUSE_MAXK], d[4];
+            // The sums of NL loci of the stage -- W and W + 16 in a whole stage, W alone in a half stage -- as NL INDEPENDENT chains
+            // issued together: all row reads first, the f64 sums interleaved, the two transposes through the wave's scratch back to
+            // back (the second locus's partials are written behind the first's reads without waiting for their data: a wave's LDS
+            // operations execute in order), the DPP adds interleaved, then the stores.  Per locus the f64 operations and their
+            // order are those of spec_pass, so the sums are the same bits whatever the stage length.
+            auto spec13 = [&](auto nlc) __attribute__((always_inline)) {
+                constexpr int NL = decltype(nlc)::value;
+                double shift[NL], g[NL][4], s1[NL], s2[NL], sy[NL][KIN_FUSE_MAXK], d[NL][4], part[NL][4], tot[NL];
+                static_for<NL>([&](auto jc) __attribute__((always_inline)) {
+                    constexpr int jl = decltype(jc)::value, ro = (W + KIN_WAVES * jl) * LD13;
 #pragma unroll
-                    for (int t = 0; t < KIN_FUSE_MAXK; ++t) sy[t] = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        d[j] = (j < 3 ? ldv(srow + (ro + 64 * j)) : ldv(srow3 + ro)) - shift;
-                        s1 += d[j];
-                        s2 = fma(d[j], d[j], s2);
-                        sy[0] = fma(d[j], yreg[0][j], sy[0]);
-                    }
-                    const bool two = P.k > 1; // wave-uniform
-                    if (two) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) sy[1] = fma(d[j], yreg[1][j], sy[1]);
-                    }
-                    scratch[lane] = s1;
-                    scratch[64 + lane] = s2;
-                    scratch[2 * 64 + lane] = sy[0];
-                    if (two) scratch[3 * 64 + lane] = sy[1];
-                    __builtin_amdgcn_wave_barrier();
-                    double tot = (sc13[0] + sc13[16]) + (sc13[32] + sc13[48]);
-                    tot = dpp_add<0x111, 0xf>(tot); // row_shr:1
-                    tot = dpp_add<0x112, 0xf>(tot); // row_shr:2
-                    tot = dpp_add<0x114, 0xf>(tot); // row_shr:4
-                    tot = dpp_add<0x118, 0xf>(tot); // row_shr:8 -> lane 15 of row v holds value v
-                    if (sp_on)
-                        __builtin_amdgcn_raw_buffer_store_b64((uint2_t){(uint32_t)__double2loint(tot), (uint32_t)__double2hiint(tot)}, srsrc,
-                                                              sp_voff + (uint32_t)(KIN_WAVES * jl * 8) * (uint32_t)NV, 0, 0);
-                    __builtin_amdgcn_wave_barrier();
+                    for (int j = 0; j < 4; ++j) g[jl][j] = j < 3 ? ldv(srow, ro + 64 * j) : ldv(srow3, ro);
                 });
-                sp_voff += sp_stride;
+                // the shift is pool 0 of the row, which lane 0 has just read: taken from there into scalar registers (the same value as
+                // spec_pass's broadcast read, without a read, a base register and two vector registers of its own)
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl)
+                    shift[jl] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(g[jl][0])), __builtin_amdgcn_readfirstlane(__double2loint(g[jl][0])));
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl) {
+                    s1[jl] = 0.0; s2[jl] = 0.0;
+#pragma unroll
+                    for (int t = 0; t < KIN_FUSE_MAXK; ++t) sy[jl][t] = 0.0;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int jl = 0; jl < NL; ++jl) {
+                        d[jl][j] = g[jl][j] - shift[jl];
+                        s1[jl] += d[jl][j];
+                        s2[jl] = fma(d[jl][j], d[jl][j], s2[jl]);
+                        sy[jl][0] = fma(d[jl][j], yreg[0][j], sy[jl][0]);
+                    }
+                const bool two = P.k > 1; // wave-uniform
+                if (two) { // (the second trait's phenotypes are read here, not kept: the one-trait loop has no registers for them)
+                    double y1[4];
+                    // (behind the two stage buffers, i.e. ylds[256 + ...]; spelled off `lds` because capturing `ylds` in this lambda
+                    //  changes the code the compiler emits for the kernels of the OTHER shapes, which must stay as they are)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) y1[j] = lds[2 * BUF13 + 256 + lane + 64 * j];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int jl = 0; jl < NL; ++jl) sy[jl][1] = fma(d[jl][j], y1[j], sy[jl][1]);
+                }
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl) {
+                    scratch[lane] = s1[jl];
+                    scratch[64 + lane] = s2[jl];
+                    scratch[2 * 64 + lane] = sy[jl][0];
+                    if (two) scratch[3 * 64 + lane] = sy[jl][1];
+                    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) part[jl][q] = sc13[16 * q];
+                    __builtin_amdgcn_wave_barrier();
+                }
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl) tot[jl] = (part[jl][0] + part[jl][1]) + (part[jl][2] + part[jl][3]);
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x111, 0xf>(tot[jl]); // row_shr:1
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x112, 0xf>(tot[jl]); // row_shr:2
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x114, 0xf>(tot[jl]); // row_shr:4
+#pragma unroll
+                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x118, 0xf>(tot[jl]); // row_shr:8 -> lane 15 of row v holds value v
+                if (sp_on) {
+#pragma unroll
+                    for (int jl = 0; jl < NL; ++jl)
+                        __builtin_amdgcn_raw_buffer_store_b64((uint2_t){(uint32_t)__double2loint(tot[jl]), (uint32_t)__double2hiint(tot[jl])}, srsrc,
+                                                              sp_voff + (uint32_t)(KIN_WAVES * jl * 8) * (uint32_t)NV, 0, 0);
+                }
+                sp_voff += (uint32_t)(NL * KIN_WAVES * 8) * (uint32_t)NV;
             };
-            constexpr int spec_step = (W / 4) % KS; // FUSE: the four waves of a SIMD do their per-locus sums in different k-steps
+            // FUSE: the four waves of a SIMD (W, W + 4, W + 8, W + 12) do their per-locus sums in different k-steps: 1, 2, 4, 5 of the 8.
+            // None in the barrier's (the last) or the one in front of it, and none in the first, where every wave's first reads of
+            // the new stage are in the LDS queue (measured, fused kernel at 200 pools x 10 M loci, one box, three runs each:
+            // steps 1, 2, 4, 5: 6.70-6.71 ms; 0, 2, 4, 5: 6.73-6.75; 0, 2, 4, 6: 6.74-6.79; the 16-locus loop: 6.96-6.98)
+            constexpr int spec_step = (W / 4) == 0 ? 1 : (W / 4) == 1 ? 2 : (W / 4) == 2 ? 4 : 5, spec_step_half = (W / 4) % KSH;
+            // One whole stage, computed from the buffer the read bases point at (buffer B).  Staging of the next stage into the
+            // OTHER buffer: its first half is requested at the top and written in the middle, its second half is requested there
+            // and written in front of the barrier.  Both writes are safe without a further barrier: the other buffer was last read
+            // in the previous stage, whose fragment reads (the last set is requested in front of that stage's barrier) and fused-sum
+            // reads (spec_step < KSW - 1) all precede that stage's barrier in program order and have returned there (__syncthreads
+            // waits for the wave's LDS operations), so no wave still reads it once any wave is past that barrier; and its next
+            // reader starts behind THIS stage's barrier, which both writes precede.  `more`: a stage or a half stage follows (if
+            // only a half follows, the second half's pieces lie past the slab's end: the descriptor returns zeros, which nobody
+            // reads; the launcher's cap on a slab leaves the room of one half for these offsets).
             auto stage = [&](auto bc, const auto more) __attribute__((always_inline)) {
-                constexpr int B = decltype(bc)::value;
+                constexpr bool up = decltype(bc)::value == 0;
                 if (more) st_load();
-                static_for<KS>([&](auto sc) __attribute__((always_inline)) {
+                static_for<KSW>([&](auto sc) __attribute__((always_inline)) {
                     constexpr int s2 = decltype(sc)::value;
-                    if constexpr (FUSE && s2 == spec_step) spec13(bc);
-                    if constexpr (s2 + 1 < KS) {
-                        load_set(bc, std::integral_constant<int, s2 + 1>{}, std::integral_constant<int, (s2 + 1) & 1>{});
+                    if constexpr (FUSE && s2 == spec_step) spec13(std::integral_constant<int, 2>{});
+                    if constexpr (s2 == KSW / 2 - 1) {
+                        if (more) { st_store(std::integral_constant<int, 0>{}); st_load(); }
+                    }
+                    if constexpr (s2 + 1 < KSW) {
+                        load_set(std::integral_constant<int, s2 + 1>{}, std::integral_constant<int, (s2 + 1) & 1>{});
                     } else {
-                        if (more) st_store(std::integral_constant<int, B ^ 1>{});
+                        if (more) st_store(std::integral_constant<int, 1>{});
                         __syncthreads();
-                        if (more) load_set(std::integral_constant<int, B ^ 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+                        flip(lb, std::bool_constant<up>{});
+                        if constexpr ((SMALL & 2) != 0 && has_strip) flip(lbs, std::bool_constant<up>{});
+                        if constexpr (ND > 0) { flip(lbr1, std::bool_constant<up>{}); flip(lbr2, std::bool_constant<up>{}); }
+                        if constexpr (FUSE) { flip(srow, std::bool_constant<up>{}); flip(srow3, std::bool_constant<up>{}); }
+                        static_for<KIN_PPT>([&](auto rc) __attribute__((always_inline)) {
+                            if constexpr (st_kind(decltype(rc)::value) != 0) flip(sdst[decltype(rc)::value], std::bool_constant<!up>{});
+                        });
+                        if (more) load_set(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
                     }
                     mfma_set(std::integral_constant<int, s2 & 1>{});
                 });
             };
-            if (nstages > 0) load_set(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-            // two stages per trip (inside the loop the first always has a successor); an odd stage count ends with a peeled stage
+            // the half stage a slab may end in: the first KIN_KC rows of the buffer the bases point at, one locus per wave, nothing follows
+            auto half_stage = [&]() __attribute__((always_inline)) {
+                static_for<KSH>([&](auto sc) __attribute__((always_inline)) {
+                    constexpr int s2 = decltype(sc)::value;
+                    if constexpr (FUSE && s2 == spec_step_half) spec13(std::integral_constant<int, 1>{});
+                    if constexpr (s2 + 1 < KSH) load_set(std::integral_constant<int, s2 + 1>{}, std::integral_constant<int, (s2 + 1) & 1>{});
+                    mfma_set(std::integral_constant<int, s2 & 1>{});
+                });
+            };
+            const int nwhole = nstages >> 1;
+            const bool half = (nstages & 1) != 0;
+            if (nstages > 0) load_set(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            // two stages per trip (inside the loop the first always has a successor); an odd count of whole stages ends with a peeled
+            // stage, and a slab of an odd number of halves with the half stage
             int c = 0;
-            for (; c + 1 < nstages; c += 2) {
+            for (; c + 1 < nwhole; c += 2) {
                 stage(std::integral_constant<int, 0>{}, std::true_type{});
-                stage(std::integral_constant<int, 1>{}, c + 2 < nstages);
+                stage(std::integral_constant<int, 1>{}, c + 2 < nwhole || half);
             }
-            if (c < nstages) stage(std::integral_constant<int, 0>{}, std::false_type{});
+            if (c < nwhole) stage(std::integral_constant<int, 0>{}, half);
+            if (half) half_stage();
             double *slab = P.slabs + (size_t)bx * P.npad * P.npad;
             static_for<NT>([&](auto uc) __attribute__((always_inline)) {
                 constexpr int u = decltype(uc)::value;
@@ -890,8 +997,15 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     int ldsld = (P.nb == 1) ? P.Tb * 16 : 2 * P.Tb * 16;
     if ((ldsld & 31) != 16) ldsld += 16;
     // fused speculative intercept-only sums: only in the single-block path and with phenotypes announced
-    const size_t fuse_lds = (size_t)2 * KIN_KC * ldsld * 8 + ((size_t)KIN_FUSE_MAXK * 256 + (size_t)KIN_WAVES * 4 * 64) * 8;
-    const bool fuse = allow_fuse && ctx->ph_armed && fuse_lds <= 160 * 1024 && P.nb == 1 && ctx->ph_n == n && ctx->ph_k >= 1 && ctx->ph_k <= KIN_FUSE_MAXK &&
+    const bool spec13 = KIN_HAS13 && P.nb == 1 && P.T == 13;
+    // LDS of a launch, in ONE place for the guard and the launch: two stage buffers of the kernel family's stage length (13-tile
+    // kernels: KC13 loci; the rest: KIN_KC), and for the fused sums the phenotypes and the waves' scratch ([4][64] doubles each).
+    // 13-tile, fused: 2 x 32 x 208 x 8 + 4 096 + 32 768 = 143 360 bytes for one trait and for two (the scratch is reused).
+    auto lds_bytes = [&](bool fused) -> size_t {
+        return (size_t)2 * (spec13 ? KC13 : KIN_KC) * ldsld * sizeof(double) +
+               (fused ? ((size_t)KIN_FUSE_MAXK * 256 + (size_t)KIN_WAVES * 4 * 64) * sizeof(double) : 0);
+    };
+    const bool fuse = allow_fuse && ctx->ph_armed && lds_bytes(true) <= 160 * 1024 && P.nb == 1 && ctx->ph_n == n && ctx->ph_k >= 1 && ctx->ph_k <= KIN_FUSE_MAXK &&
                       ctx->ph_ytil_dev != nullptr;
     P.ytil = nullptr; P.spec = nullptr; P.k = 0;
     ctx->spec_valid = false;
@@ -901,10 +1015,9 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
         if (rrc) return rrc;
         P.ytil = ctx->ph_ytil_dev; P.spec = ctx->spec_dev; P.k = ctx->ph_k;
     }
-    const size_t shmem = (size_t)2 * KIN_KC * ldsld * sizeof(double) + (fuse ? ((size_t)KIN_FUSE_MAXK * 256 + (size_t)KIN_WAVES * 4 * 64) * sizeof(double) : 0);
+    const size_t shmem = lds_bytes(fuse);
     const int max_cols = (P.nb == 1) ? P.Tb * 16 : 2 * P.Tb * 16; // staged pools per locus row
     PG_CHECK(ctx, KIN_KC * (max_cols / 2) <= KIN_PPT * KIN_THREADS, "kinship: staging overflow");
-    const bool spec13 = (P.nb == 1 && P.T == 13);
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
@@ -926,9 +1039,12 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     auto pick = [&](auto fz) -> hipError_t {
         constexpr bool FZ = decltype(fz)::value;
         if (!spec13) return P.skip_dead ? launch(k_kinship_syrk<FZ, false, 0, true>) : launch(k_kinship_syrk<FZ, false, 0, false>);
-        // (an even pool count, the headline among them, runs the instance without the odd-tail zeroing in its stage loop)
-        if (n & 1) return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3>) : launch(k_kinship_syrk<FZ, true, 1>);
-        return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3, false, false>) : launch(k_kinship_syrk<FZ, true, 1, false, false>);
+        if constexpr (KIN_HAS13) {
+            // (an even pool count, the headline among them, runs the instance without the odd-tail zeroing in its stage loop)
+            if (n & 1) return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3>) : launch(k_kinship_syrk<FZ, true, 1>);
+            return n <= 200 ? launch(k_kinship_syrk<FZ, true, 3, false, false>) : launch(k_kinship_syrk<FZ, true, 1, false, false>);
+        }
+        return hipErrorInvalidDeviceFunction; // (not reached: spec13 implies KIN_HAS13)
     };
     le = fuse ? pick(std::true_type{}) : pick(std::false_type{});
     PG_HIP(ctx, le);
