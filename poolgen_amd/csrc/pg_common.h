@@ -98,7 +98,7 @@ struct pg_ctx {
     const uint32_t *load_counts = nullptr;
     const int64_t *load_order = nullptr;
     int64_t load_L = 0, load_total = 0, load_nunits = 0;
-    int load_n = 0, load_kpm1 = 0, load_pshift = 0;
+    int load_n = 0, load_kpm1 = 0;
     size_t load_off_flags = 0, load_off_local = 0, load_off_blockoff = 0, load_off_poolmap = 0;
     int64_t lo_last_L = 0, lo_last_listed = 0; // pg_locus_op_stats
     bool rows_call[2] = {true, true};   // ... and what the current call's launch groups run

@@ -54,7 +54,6 @@ struct LocusParams {
     int n, k;        // k = traits handled by this launch (<= MAXK)
     int k_total, t0; // output layout: trait t0 + tt of k_total
     int remove_ns;
-    int pshift;      // unit_slot's interleave (0 since round 3: records and flags are indexed by the locus itself)
     int sort_desc;   // OP_LOAD: order the surviving alleles by decreasing column sum (--keep-p-minus-1)
     double min_cov, maf, max_miss;
     int tdf, ntcoef;     // t-test degrees of freedom (OLS: n-1, Pearson: n-2)
@@ -172,32 +171,104 @@ __device__ __forceinline__ double div_by(double a, double b, double r) {
     return fma(fma(-b, q0, a), r, q0);
 }
 
-template <typename T>
-__device__ __forceinline__ T pick6(const T (&a)[NA], int idx) {
-    T r = a[0];
+// ---- steps shared by k_locus_stream and k_ols_rows -------------------------------------------------------------------------
+// the sync column of slot jj of the alleles in play: remove_ns takes N (column 4) out
+template <bool RNS> __device__ __forceinline__ constexpr int allele_of(int jj) { return (RNS && jj >= 4) ? jj + 1 : jj; }
+
+// The filter's q of locus l exactly as the reference forms it (sync.rs:258-271), from the locus' counts in memory: fp64 quotients,
+// multiply, then add, in pool order.  Both kernels decide on a cheaper q~ and come here for a locus whose q~ lies within their band
+// of a threshold (real data almost never does).  tab: the pool table in LDS, w_i at tab[i * TW].  Returns the mask of surviving slots.
+template <bool RNS, int TW>
+__device__ __forceinline__ int literal_q_slotmask(const uint32_t *counts, int64_t l, int n, const double *tab,
+                                                  const LocusParams &P, double (&qe)[RNS ? 5 : 6]) {
+    constexpr int NJ = RNS ? 5 : 6;
 #pragma unroll
-    for (int j = 1; j < NA; ++j) r = (idx == j) ? a[j] : r;
-    return r;
+    for (int j = 0; j < NJ; ++j) qe[j] = 0.0;
+    const uint2_t *rp = reinterpret_cast<const uint2_t *>(counts + (size_t)l * (size_t)n * 6);
+    for (int i = 0; i < n; ++i) {
+        const uint2_t a0 = rp[3 * i], a1 = rp[3 * i + 1], a2 = rp[3 * i + 2];
+        const uint32_t c6[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
+        uint32_t rs = 0u;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) rs += c6[allele_of<RNS>(j)];
+        const double rsd = (double)(rs > 1u ? rs : 1u);
+        const double ri = recip_for_div(rsd);
+        const double wi = tab[i * TW];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) qe[j] = qe[j] + div_by((double)c6[allele_of<RNS>(j)], rsd, ri) * wi;
+    }
+    int slotmask = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) slotmask |= !((qe[j] < P.maf) | (qe[j] > (1.00 - P.maf))) ? (1 << j) : 0;
+    return slotmask;
 }
 
-// index into the packed upper triangle of the 6 x 6 product-sum table
-__device__ __forceinline__ constexpr int tri(int a, int b) { // a <= b
-    return a * NA - a * (a - 1) / 2 + (b - a);
+// the pool table w_i, y_i0, ... (TW doubles per pool) from memory into LDS, by the whole workgroup; the caller synchronises
+template <int TW>
+__device__ __forceinline__ void load_pool_table(double *t, const double *wy, int n) {
+    for (int i = threadIdx.x; i < TW * n; i += LO_THREADS) t[i] = wy[i];
+}
+
+// Buffer descriptor of the nbytes of the batch from address ub on (both wave-uniform; the callers cut nbytes at the end of the
+// batch).  Bytes past the range come back as zeros.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t batch_rsrc(uint64_t ub, uint32_t nbytes) {
+    const uint32_t nrec = (uint32_t)__builtin_amdgcn_readfirstlane((int)nbytes);
+    const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub);
+    const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char *>(((uint64_t)bhi << 32) | blo), 0, nrec, 0x00020000);
+}
+
+// the second pass' list: locus l of every lane with `listed` set is appended; one returning atomic per wave that has any (the
+// caller's wait for it drains whatever loads are in flight)
+__device__ __forceinline__ void list_append(int64_t *second, unsigned long long *second_count, bool listed,
+                                            int64_t l, int lane) {
+    const unsigned long long bal = __ballot(listed);
+    if (bal) {
+        unsigned long long basev = 0;
+        if (lane == 0) basev = atomicAdd(second_count + SC_LIST, (unsigned long long)__popcll(bal));
+        basev = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(basev >> 32)) << 32) |
+                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)basev);
+        if (listed) second[basev + __popcll(bal & ((1ull << lane) - 1ull))] = l;
+    }
+}
+
+// a count the 32-bit coverage sums cannot take (2^29 or more) was seen by this wave: the host reports it
+__device__ __forceinline__ void raise_complaint(unsigned long long *second_count, int lane) {
+    if (lane == 0) atomicOr(second_count + SC_COMPLAINT, 1ull);
+}
+
+// The staged result of a locus in LDS, RECB bytes: n_out | ids (3 bits each) + nk << 16 | mean frequency | statistic, p-value per trait
+template <int K>
+struct StagedResult {
+    static constexpr int RECB = 16 + 16 * K;
+    char *base;
+    __device__ __forceinline__ void put(int idx, int nout, int idsp, double mf, const double (&st)[K], const double (&pv)[K]) const {
+        char *r = base + (size_t)idx * RECB;
+        *reinterpret_cast<uint2_t *>(r) = uint2_t{(uint32_t)nout, (uint32_t)idsp};
+        *reinterpret_cast<double *>(r + 8) = mf;
+#pragma unroll
+        for (int t = 0; t < K; ++t) {
+            *reinterpret_cast<double *>(r + 16 + 16 * t) = st[t];
+            *reinterpret_cast<double *>(r + 24 + 16 * t) = pv[t];
+        }
+    }
+    __device__ __forceinline__ uint2_t hdr(int j) const { return *reinterpret_cast<const uint2_t *>(base + (size_t)j * RECB); }
+    __device__ __forceinline__ double dbl(int j, int off) const { return *reinterpret_cast<const double *>(base + (size_t)j * RECB + off); }
+};
+
+// p of a locus' chi-square statistic over its n pools x nk surviving alleles (tables/chisq_test.rs:33-35)
+__device__ __forceinline__ double close_chisq(double chi2, int n, int nk) {
+    const double df = (double)(n * nk) - 1.0;
+    return pg_chisq_upper_p(chi2, df, pg_ln_gamma(df / 2.0));
 }
 
 // record layout (struct-of-arrays: field f of locus l at rec[f * L + l])
 constexpr int REC_DOUBLES = 42; // the largest compact record: pearson, 5 outputs x 2 traits (see emit_record)
 // Records (of the second pass) and flags live in groups of 64 slots: field f of slot s at
-// rec[(s / 64) * REC_DOUBLES * 64 + f * 64 + s % 64], so that a wave's stores are whole 512-byte runs.  slot = unit_slot(l, pshift);
-// with pshift = 0 (every caller since round 3) the slot is the locus.
-__device__ __forceinline__ int64_t unit_slot(int64_t l, int pshift) {
-    const int64_t g = l >> (6 + pshift);
-    const int within = (int)(l - (g << (6 + pshift)));
-    const int c = within & ((1 << pshift) - 1);
-    return (((g << pshift) + c) << 6) + (within >> pshift);
-}
-__device__ __forceinline__ size_t rec_base(int64_t slot) {
-    return (size_t)(slot >> 6) * (size_t)(REC_DOUBLES * 64) + (size_t)(slot & 63);
+// rec[(s / 64) * REC_DOUBLES * 64 + f * 64 + s % 64], so that a wave's stores are whole 512-byte runs.  The slot of a locus is the
+// locus itself.
+__device__ __forceinline__ size_t rec_base(int64_t l) {
+    return (size_t)(l >> 6) * (size_t)(REC_DOUBLES * 64) + (size_t)(l & 63);
 }
 constexpr int FLAG_ALIVE = PG_HDR_ALIVE, FLAG_SECOND = 1 << 7; // bits 1..6: surviving alleles
 
@@ -322,8 +393,8 @@ __device__ __forceinline__ double pick_trait(const double (&a)[NJ * K], int idx,
 template <int OP, int NJ, int K, typename AJ>
 __device__ __forceinline__ void emit_record(const Sums<OP, NJ, K> &S, bool poisoned, const bool (&kp)[NJ], bool alive,
                                             bool again, bool valid, int32_t *__restrict__ rec_flags,
-                                            double *__restrict__ rec, int64_t slot, AJ aj, bool sort_desc = false) {
-    const size_t rb = rec_base(slot);
+                                            double *__restrict__ rec, int64_t l, AJ aj, bool sort_desc = false) {
+    const size_t rb = rec_base(l);
     const double pz = poisoned ? NAN : 0.0; // x + NaN = NaN: an uncovered pool makes the plain sums NaN
     int nk = 0, keepmask = 0;
 #pragma unroll
@@ -360,7 +431,7 @@ __device__ __forceinline__ void emit_record(const Sums<OP, NJ, K> &S, bool poiso
         }
     }
     if (valid)
-        rec_flags[slot] = (alive ? FLAG_ALIVE : 0) | keepmask | (again ? FLAG_SECOND : 0) | (nk << H_NK_SHIFT) |
+        rec_flags[l] = (alive ? FLAG_ALIVE : 0) | keepmask | (again ? FLAG_SECOND : 0) | (nk << H_NK_SHIFT) |
                           (ordbits << H_ORD_SHIFT);
     if (OP == OP_LOAD) return; // the header is all the loader needs
     const int D = (valid && alive && !again) ? nk - 1 : 0; // a locus the second pass redoes gets its sums there
@@ -604,6 +675,29 @@ __device__ __forceinline__ void ols_solve(const double (&cs)[PN - 1], const doub
     }
 }
 
+// A biallelic ols_iter locus closed in place from the three sums of its design column (the minor allele, id `idc`): cs = sum f,
+// ff = sum f^2, fy[t] = sum f y_t; pz = NaN when a pool is uncovered over the survivors (x + NaN = NaN: the reference's plain sums are
+// NaN then, sync.rs:176-183), else 0.  Fills the result of a lane with `simple` set whose fit is not singular.
+template <int K>
+__device__ __forceinline__ void close_biallelic_ols(double cs, double ff, const double (&fy)[K], double pz, int idc, bool simple,
+                                                    const LocusParams &P, const double *__restrict__ tcoef, int &nout, int &idsp,
+                                                    double &mf, double (&st)[K], double (&pv)[K]) {
+    double cs1[1], xx1[1][1], xy1[1][MAXK], b1[MAXK][1], p1[MAXK][1];
+    cs1[0] = cs + pz;
+    xx1[0][0] = ff + pz;
+#pragma unroll
+    for (int t = 0; t < MAXK; ++t) xy1[0][t] = (t < K) ? fy[t < K ? t : 0] + pz : 0.0;
+    bool singular;
+    ols_solve<2>(cs1, xx1, xy1, K, P, tcoef, singular, b1, p1);
+    if (simple && !singular) { // Err -> the whole locus is dropped (ols.rs:250-253)
+        nout = 1;
+        idsp = idc;
+        mf = cs1[0] / (double)P.n; // ols.rs:266
+#pragma unroll
+        for (int t = 0; t < K; ++t) { st[t] = b1[t][0]; pv[t] = p1[t][0]; }
+    }
+}
+
 // pearsons_correlation (gwas/correlation_test.rs:7-71) from the shifted sums over the complete pairs
 __device__ __forceinline__ void pearson_close(double sx, double sxx, double sxy, double sy, double syy, double m, int n,
                                               const LocusParams &P, const double *__restrict__ tcoef, double &rr, double &pp) {
@@ -620,10 +714,10 @@ __device__ __forceinline__ void pearson_close(double sx, double sxx, double sxy,
     rr = round(r0 * 1e7) / 1e7; // sensible_round(r, 7), :70 (half away from zero)
 }
 
-// ---- the streaming pass (round 3): every locus, ONE read of its counts, fits closed in place ------------------------
+// ---- the streaming pass: every locus, ONE read of its counts, fits closed in place ------------------------
 // One lane per locus, as the filter demands: q_j = sum_i f_ij w_i must be accumulated sequentially in pool order with
-// separate multiply and add (sync.rs:258-282), and a lane walking its own row does exactly that.  What changed against
-// round 2's k_locus_first (measurements: tools/mb_locus_dma.hip, profiles/r03_mb_locus_*.log):
+// separate multiply and add (sync.rs:258-282), and a lane walking its own row does exactly that.  How it reads and why
+// (measurements: tools/mb_locus_dma.hip, profiles/r03_mb_locus_*.log):
 //  * A lane takes M = period consecutive loci, one after the other, as ONE stream of M * 24 n bytes: that many bytes are a
 //    whole number of 128-byte lines (period = 128 / gcd(24 n, 128)), so every lane's stream starts at the same offset inside
 //    a line, no line is shared by two lanes (the alignment-class units of round 2 fetched the line two neighbouring rows
@@ -659,7 +753,7 @@ constexpr int ST_STAGE = 8192;      // LDS bytes per wave for the results of a u
 template <int OP, int NJ, int K>
 struct Acc { // running sums of one locus; everything accumulated sequentially in pool order
     double q[NJ];         // the filter's pool-size weighted frequencies, every candidate allele in play (sync.rs:258-271), see pool()
-    double cs[NJ], dd[NJ]; // LOAD: sum f with every candidate in play -- the reference's when the dropped alleles have no reads (dd: unused)
+    double cs[NJ];        // LOAD: sum f with every candidate in play -- the reference's when the dropped alleles have no reads
     // The SPECULATED PAIR (round 4).  The reference recomputes the frequencies on the FILTERED counts (gwas/ols.rs:210-230 ->
     // sync.rs:166-192): one stray read of an allele the filter drops changes every denominator of the locus, so sums taken over all
     // candidates are useless for real data.  Instead the sums of a biallelic fit are taken with the denominator c_a + c_b of a pair
@@ -681,7 +775,7 @@ struct Acc { // running sums of one locus; everything accumulated sequentially i
     bool shset;
     __device__ __forceinline__ void clear() {
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { q[j] = 0.0; cs[j] = 0.0; dd[j] = 0.0; }
+        for (int j = 0; j < NJ; ++j) { q[j] = 0.0; cs[j] = 0.0; }
 #pragma unroll
         for (int j = 0; j < 2; ++j) { cs2[j] = 0.0; dd2[j] = 0.0; }
 #pragma unroll
@@ -710,8 +804,7 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
     const StreamOut O, const LocusParams P, const int M, const int staged) {
     constexpr int NJ = RNS ? 5 : 6;
     constexpr int TW = (OP == OP_OLS || OP == OP_PEARSON) ? 1 + K : 1; // doubles per pool in the table: w_i, y_i0, ...
-    constexpr int RECB = 16 + 16 * K;                                  // bytes of a staged result
-    auto aj = [](int jj) { return (RNS && jj >= 4) ? jj + 1 : jj; };
+    auto aj = [](int jj) { return allele_of<RNS>(jj); };
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -720,11 +813,9 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
     const double *tab = reinterpret_cast<const double *>(lds_raw + LO_WAVES * (ST_SLOTB + ST_STAGE));
     const int n = P.n;
     const int64_t L = P.L;
-    {
-        double *t = reinterpret_cast<double *>(lds_raw + LO_WAVES * (ST_SLOTB + ST_STAGE));
-        for (int i = threadIdx.x; i < TW * n; i += LO_THREADS) t[i] = wy[i];
-        __syncthreads();
-    }
+    const StagedResult<K> res{stage};
+    load_pool_table<TW>(reinterpret_cast<double *>(lds_raw + LO_WAVES * (ST_SLOTB + ST_STAGE)), wy, n);
+    __syncthreads();
     const uint32_t rowb = (uint32_t)n * 24u;
     const uint32_t srb = (uint32_t)M * rowb;              // bytes of a lane's stream: a whole number of lines
     const int nh = (int)(srb >> 7);                       // lines per stream
@@ -753,21 +844,12 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
             // descriptor of THIS line: base = the unit's start + 128 h, range = what is left of the batch; bytes past the batch come
             // back as zeros (uncovered pools of loci that are never stored)
             const uint64_t uo = (uint64_t)pre_u * 64u * srb + (uint64_t)pre_h * 128u;
-            const uint64_t ub = base0 + uo;
             // (rounded up to the 16 bytes of a load: a batch ends on an 8-byte boundary, its base is 16-byte aligned)
             const uint64_t left = total_bytes > uo ? ((total_bytes - uo + 15u) & ~(uint64_t)15) : 0;
-            const uint32_t nrec = (uint32_t)__builtin_amdgcn_readfirstlane((int)(left > 0xffffffffull ? 0xffffffffu : (uint32_t)left));
-            const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub);
-            const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32));
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                reinterpret_cast<char *>(((uint64_t)bhi << 32) | blo), 0, nrec, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rsrc = batch_rsrc(base0 + uo, left > 0xffffffffull ? 0xffffffffu : (uint32_t)left);
 #pragma unroll
             for (int i = 0; i < 8; ++i) // the two halves of a row group's line in consecutive instructions
-#ifdef LS_EXP_NTLOAD
-                SR[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vb[i >> 1] + (uint32_t)(i & 1) * 64u, 0, 2);
-#else
                 SR[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vb[i >> 1] + (uint32_t)(i & 1) * 64u, 0, 0);
-#endif
             if (++pre_h >= nh) { pre_h = 0; pre_u += wstride; }
         }
     };
@@ -862,11 +944,6 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
     auto pool = [&](const uint2_t &wa, const uint2_t &wb, const uint2_t &wd, const TabRow &tr, auto chkc) {
         constexpr bool CHK = decltype(chkc)::value;
         const uint32_t c0[6] = {wa.x, wa.y, wb.x, wb.y, wd.x, wd.y};
-#ifdef LS_EXP_NOCOMPUTE
-        if (c0[0] == 0xdeadbeefu && tr.w == 1.5) A.q[0] += (double)(c0[1] + c0[2] + c0[3] + c0[4] + c0[5]);
-        if (CHK) { if (++pi == n) { pi = 0; boundary(); fin_i = iloc++; fin_pending = true; A.clear(); } }
-        return;
-#endif
         uint32_t ci[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) ci[j] = c0[aj(j)];
@@ -897,10 +974,6 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
             // has its q recomputed literally in finish(); everybody else's decision is provably the reference's.
             double f[NAC];
             const double wi = tr.w;
-#ifdef LS_EXP_QEXACT // (timing experiment: the literal evaluation)
-#pragma unroll
-            for (int j = 0; j < NAC; ++j) { f[j] = div_by((double)ci[j], rsd, rinv); A.q[j] = A.q[j] + f[j] * wi; }
-#else
             {
                 const double wr = wi * rinv;
 #pragma unroll
@@ -910,7 +983,6 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
 #pragma unroll
                 for (int j = 0; j < NAC; ++j) f[j] = div_by((double)ci[j], rsd, rinv);
             }
-#endif
             if constexpr (OP == OP_LOAD) {
 #pragma unroll
                 for (int j = 0; j < NAC; ++j) A.cs[j] = A.cs[j] + f[j];
@@ -983,9 +1055,6 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
             }
         };
         {
-#ifdef LS_EXP_NOFASTPATH
-            arith(std::integral_constant<int, NJ>{});
-#else
             // (tested for every pool: skipping the test for a while after a pool that needed the general code was measured -- nothing on
             // error-bearing counts, where nearly every pool has a stray read in one of the wave's 64 loci, and -3 % on clean ones)
             uint32_t others = 0u;
@@ -993,7 +1062,6 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
             for (int j = 2; j < NJ; ++j) others |= ci[j];
             if (__any(others != 0u)) arith(std::integral_constant<int, NJ>{});
             else arith(std::integral_constant<int, 2>{});
-#endif
         }
         // the locus' last pool: decide, keep what the closing needs (it runs at the end of the turn) and start the next locus
         if constexpr (CHK) {
@@ -1007,22 +1075,8 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
         }
     };
 
-    // one staged result: n_out | ids (3 bits each) + nk << 16 | mean frequency | statistic per trait | p-value per trait
-    auto put_result = [&](int idx, int nout, int idsp, double mf, const double (&st)[K], const double (&pv)[K]) {
-        char *r = stage + (size_t)idx * RECB;
-        *reinterpret_cast<uint2_t *>(r) = uint2_t{(uint32_t)nout, (uint32_t)idsp};
-        *reinterpret_cast<double *>(r + 8) = mf;
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-            *reinterpret_cast<double *>(r + 16 + 16 * t) = st[t];
-            *reinterpret_cast<double *>(r + 24 + 16 * t) = pv[t];
-        }
-    };
     // the operator's output arrays of locus l from one result
     auto store_result = [&](int64_t l, int nout, int idsp, double mf, const double (&st)[K], const double (&pv)[K]) {
-#ifdef LS_EXP_NOSTORE // (timing experiments only: tools/exp_locus.sh)
-        if (nout != 12345) return;
-#endif
         const int nk = (idsp >> 16) & 7;
         if (OP == OP_CHISQ) {
             O.n_out[l] = nout;
@@ -1058,24 +1112,7 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
         if (__any((fh & (1 << 7)) != 0 && valid)) {
             if ((fh & (1 << 7)) != 0 && valid) {
                 double qe[NJ];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) qe[j] = 0.0;
-                const uint2_t *rp = reinterpret_cast<const uint2_t *>(counts + (size_t)l * (size_t)n * 6);
-                for (int i = 0; i < n; ++i) {
-                    const uint2_t a0 = rp[3 * i], a1 = rp[3 * i + 1], a2 = rp[3 * i + 2];
-                    const uint32_t c6[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
-                    uint32_t rs = 0u;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) rs += c6[aj(j)];
-                    const double rsd = (double)(rs > 1u ? rs : 1u);
-                    const double ri = recip_for_div(rsd);
-                    const double wi = tab[i * TW];
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) qe[j] = qe[j] + div_by((double)c6[aj(j)], rsd, ri) * wi;
-                }
-                slotmask = 0;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) slotmask |= !((qe[j] < P.maf) | (qe[j] > (1.00 - P.maf))) ? (1 << j) : 0;
+                slotmask = literal_q_slotmask<RNS, TW>(counts, l, n, tab, P, qe);
             }
         }
         int nk = 0, keepmask = 0;
@@ -1127,28 +1164,14 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
         } else if (deferred) {
             rec_flags[l] = FLAG_ALIVE | keepmask | FLAG_SECOND | (nk << H_NK_SHIFT); // the second pass wants the surviving alleles
         }
-        // the list of the second pass: one returning atomic per unit that has any (its wait drains the line in flight)
-        {
-            const unsigned long long bal = __ballot(deferred);
-            if (bal) {
-                unsigned long long basev = 0;
-                if (lane == 0) basev = atomicAdd(second_count + SC_LIST, (unsigned long long)__popcll(bal));
-                basev = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(basev >> 32)) << 32) |
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)basev);
-                if (deferred) second[basev + __popcll(bal & ((1ull << lane) - 1ull))] = l;
-            }
-        }
+        list_append(second, second_count, deferred, l, lane);
         if (OP == OP_LOAD) return;
         // ---- close the locus ------------------------------------------------------------------------------------------------------
         int nout = 0, idsp = 0;
         double mf = NAN, st[K], pv[K];
 #pragma unroll
         for (int t = 0; t < K; ++t) { st[t] = NAN; pv[t] = NAN; }
-#ifdef LS_EXP_NOCLOSE
-        const bool simple = alive && !deferred && nk == 12345;
-#else
         const bool simple = alive && !deferred;
-#endif
         if (OP == OP_CHISQ) {
             // every surviving allele is listed (column order), alive or not (the row of the locus)
             int r = 0;
@@ -1162,26 +1185,15 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
             if (__any(simple)) {
                 const double acc = fv[2 < NFV ? 2 : 0] / fv[0] + fv[3 < NFV ? 3 : 0] / fv[1 < NFV ? 1 : 0];
                 const double chi2 = fv[4 < NFV ? 4 : 0] * (acc - 1.0) + pz; // tables/chisq_test.rs:15-31 regrouped
-                const double df = (double)(n * nk) - 1.0;
-                const double p = pg_chisq_upper_p(chi2, df, pg_ln_gamma(df / 2.0)); // :33-35
+                const double p = close_chisq(chi2, n, nk);
                 if (simple) { st[0] = chi2; pv[0] = p; nout = nk; }
             }
         } else if (__any(simple)) {
-            if (OP == OP_OLS) {
-                double cs1[1], xx1[1][1], xy1[1][MAXK], b1[MAXK][1], p1[MAXK][1];
-                cs1[0] = fv[0] + pz;
-                xx1[0][0] = fv[1 < NFV ? 1 : 0] + pz;
+            if constexpr (OP == OP_OLS) {
+                double fy[K];
 #pragma unroll
-                for (int t = 0; t < MAXK; ++t) xy1[0][t] = (t < K) ? fv[(2 + t) < NFV ? 2 + t : 0] + pz : 0.0;
-                bool singular;
-                ols_solve<2>(cs1, xx1, xy1, K, P, tcoef, singular, b1, p1);
-                if (simple && !singular) { // Err -> the whole locus is dropped (ols.rs:250-253)
-                    nout = 1;
-                    idsp = (fh >> 12) & 7;
-                    mf = cs1[0] / (double)n; // ols.rs:266
-#pragma unroll
-                    for (int t = 0; t < K; ++t) { st[t] = b1[t][0]; pv[t] = p1[t][0]; }
-                }
+                for (int t = 0; t < K; ++t) fy[t] = fv[2 + t];
+                close_biallelic_ols<K>(fv[0], fv[1], fy, pz, (fh >> 12) & 7, simple, P, tcoef, nout, idsp, mf, st, pv);
             } else { // OP_PEARSON
                 double rr, pp;
                 pearson_close(fv[1 < NFV ? 1 : 0], fv[2 < NFV ? 2 : 0], fv[3 < NFV ? 3 : 0], P.py[0], P.pyy[0], P.pn[0], n, P, tcoef, rr, pp);
@@ -1195,7 +1207,7 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
             }
         }
         // a deferred locus gets the "dropped" pattern here; k_locus_second overwrites it later in the stream
-        if (staged & 1) put_result(lane * M + fin_i, nout, idsp, mf, st, pv);
+        if (staged & 1) res.put(lane * M + fin_i, nout, idsp, mf, st, pv);
         else if (valid) store_result(l, nout, idsp, mf, st, pv);
     };
 
@@ -1206,29 +1218,22 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
     const bool coalesced = (staged & 2) != 0; // the host checked: 16-byte aligned arrays, every trait of the call in this launch
     auto flush_unit = [&](int64_t unit) {
         __builtin_amdgcn_wave_barrier();
-#ifdef LS_EXP_SMALLOUT // (timing experiment: every unit writes the first unit's region -- the stores stay, the memory traffic goes)
-        const int64_t l0 = 0;
-        const int nv = (int)lpu;
-#else
         const int64_t l0 = unit * lpu;
         const int nv = (int)((L - l0) < lpu ? (L - l0) : lpu); // loci of this unit that exist
-#endif
         if (OP == OP_LOAD) {
             for (int idx = lane; idx < nv; idx += 64) rec_flags[l0 + idx] = *reinterpret_cast<const int32_t *>(stage + (size_t)idx * 4);
         } else if (!coalesced) {
             for (int idx = lane; idx < nv; idx += 64) {
-                const char *rp = stage + (size_t)idx * RECB;
-                const uint2_t h = *reinterpret_cast<const uint2_t *>(rp);
+                const uint2_t h = res.hdr(idx);
                 double st[K], pv[K];
 #pragma unroll
                 for (int t = 0; t < K; ++t) {
-                    st[t] = *reinterpret_cast<const double *>(rp + 16 + 16 * t);
-                    pv[t] = *reinterpret_cast<const double *>(rp + 24 + 16 * t);
+                    st[t] = res.dbl(idx, 16 + 16 * t);
+                    pv[t] = res.dbl(idx, 24 + 16 * t);
                 }
-                store_result(l0 + idx, (int)h.x, (int)h.y, *reinterpret_cast<const double *>(rp + 8), st, pv);
+                store_result(l0 + idx, (int)h.x, (int)h.y, res.dbl(idx, 8), st, pv);
             }
         } else {
-#ifndef LS_EXP_NOSTORE
             // one array: EPL elements per locus, element (j, sub) = get(j, sub); 16 bytes per lane and store
             auto emit32 = [&](int32_t *base, auto eplc, auto get) {
                 constexpr int EPL = decltype(eplc)::value;
@@ -1246,11 +1251,8 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
                         const int j = e / EPL;
                         v[u] = get(j < nv ? j : nv - 1, e - j * EPL);
                     }
-#ifndef LS_EXP_PLAINSTORE // results are written once and not read by this launch: non-temporal (measured: -25 .. -35 us per million loci)
+                    // results are written once and not read by this launch: non-temporal (measured: -25 .. -35 us per million loci)
                     if (c * 4 + 3 < ne) __builtin_nontemporal_store(uint4_t{(uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], (uint32_t)v[3]}, reinterpret_cast<uint4_t *>(dst + c * 4));
-#else
-                    if (c * 4 + 3 < ne) *reinterpret_cast<uint4_t *>(dst + c * 4) = uint4_t{(uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], (uint32_t)v[3]};
-#endif
                     else {
 #pragma unroll
                         for (int u = 0; u < 4; ++u) if (c * 4 + u < ne) dst[c * 4 + u] = v[u];
@@ -1273,48 +1275,41 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
                         const int j = e / EPL;
                         v[u] = get(j < nv ? j : nv - 1, e - j * EPL);
                     }
-#ifndef LS_EXP_PLAINSTORE
                     typedef double d2v __attribute__((ext_vector_type(2)));
                     if (c * 2 + 1 < ne) __builtin_nontemporal_store(d2v{v[0], v[1]}, reinterpret_cast<d2v *>(dst + c * 2));
-#else
-                    if (c * 2 + 1 < ne) *reinterpret_cast<double2 *>(dst + c * 2) = double2{v[0], v[1]};
-#endif
                     else dst[c * 2] = v[0];
                 }
             };
-            auto hdr_of = [&](int j) { return *reinterpret_cast<const uint2_t *>(stage + (size_t)j * RECB); };
-            auto dbl_of = [&](int j, int off) { return *reinterpret_cast<const double *>(stage + (size_t)j * RECB + off); };
             if (OP == OP_CHISQ) {
-                emit32(O.n_out, std::integral_constant<int, 1>{}, [&](int j, int) { return (int)hdr_of(j).x; });
+                emit32(O.n_out, std::integral_constant<int, 1>{}, [&](int j, int) { return (int)res.hdr(j).x; });
                 // the surviving alleles of the row: the slots some locus of the unit needs (slots r >= n_out[l] are unspecified)
                 int mx = 0;
-                for (int idx = lane; idx < nv; idx += 64) mx = max(mx, (int)((hdr_of(idx).y >> 16) & 7u));
+                for (int idx = lane; idx < nv; idx += 64) mx = max(mx, (int)((res.hdr(idx).y >> 16) & 7u));
                 for (int off = 32; off >= 1; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
                 mx = __builtin_amdgcn_readfirstlane(mx);
 #pragma unroll
                 for (int r = 0; r < PG_MAX_OUT; ++r)
                     if (r < mx)
                         emit32(O.ids + (size_t)r * P.L, std::integral_constant<int, 1>{}, [&](int j, int) {
-                            const int idsp = (int)hdr_of(j).y;
+                            const int idsp = (int)res.hdr(j).y;
                             return r < ((idsp >> 16) & 7) ? ((idsp >> (3 * r)) & 7) : -1;
                         });
-                emit64(O.stat, std::integral_constant<int, 1>{}, [&](int j, int) { return dbl_of(j, 16); });
-                emit64(O.pv, std::integral_constant<int, 1>{}, [&](int j, int) { return dbl_of(j, 24); });
+                emit64(O.stat, std::integral_constant<int, 1>{}, [&](int j, int) { return res.dbl(j, 16); });
+                emit64(O.pv, std::integral_constant<int, 1>{}, [&](int j, int) { return res.dbl(j, 24); });
             } else {
                 // (only single-output loci are closed in this pass: slot 0 of every array, the other slots are not written)
                 if (P.t0 == 0 || OP == OP_PEARSON) {
-                    emit32(O.n_out, std::integral_constant<int, 1>{}, [&](int j, int) { return (int)hdr_of(j).x; });
+                    emit32(O.n_out, std::integral_constant<int, 1>{}, [&](int j, int) { return (int)res.hdr(j).x; });
                     emit32(O.ids, std::integral_constant<int, 1>{}, [&](int j, int) {
-                        const uint2_t h = hdr_of(j);
+                        const uint2_t h = res.hdr(j);
                         return h.x ? (int)(h.y & 7u) : -1;
                     });
-                    emit64(O.mf, std::integral_constant<int, 1>{}, [&](int j, int) { return hdr_of(j).x ? dbl_of(j, 8) : NAN; });
+                    emit64(O.mf, std::integral_constant<int, 1>{}, [&](int j, int) { return res.hdr(j).x ? res.dbl(j, 8) : NAN; });
                 }
                 // [slot 0][locus][trait], every trait of the call in this launch (k_total == K, t0 == 0)
-                emit64(O.stat, std::integral_constant<int, K>{}, [&](int j, int t) { return hdr_of(j).x ? dbl_of(j, 16 + 16 * t) : NAN; });
-                emit64(O.pv, std::integral_constant<int, K>{}, [&](int j, int t) { return hdr_of(j).x ? dbl_of(j, 24 + 16 * t) : NAN; });
+                emit64(O.stat, std::integral_constant<int, K>{}, [&](int j, int t) { return res.hdr(j).x ? res.dbl(j, 16 + 16 * t) : NAN; });
+                emit64(O.pv, std::integral_constant<int, K>{}, [&](int j, int t) { return res.hdr(j).x ? res.dbl(j, 24 + 16 * t) : NAN; });
             }
-#endif
         }
         __builtin_amdgcn_wave_barrier();
     };
@@ -1341,7 +1336,7 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
             }
             if (staged & 1) flush_unit(cur_u);
             if (__any((orm_unit >> 29) != 0u)) {
-                if (lane == 0) atomicOr(second_count + SC_COMPLAINT, 1ull);
+                raise_complaint(second_count, lane);
                 orm_unit = 0;
             }
         }
@@ -1402,17 +1397,13 @@ __global__ __launch_bounds__(LO_THREADS, LO_BLOCKS_DEF) void k_locus_stream(
         for (int T = 0; T < nturn; ++T) {
             turn(std::true_type{});
             if (fin_pending) { // (at most one locus ends per turn: n >= 16 pools, checked by the host)
-#ifndef LS_EXP_NOFINISH
                 finish(cur_u);
-#endif
                 fin_pending = false;
             }
         }
-#ifndef LS_EXP_NOFLUSH
         if (staged & 1) flush_unit(cur_u);
-#endif
-        if (__any((orm_unit >> 29) != 0u)) { // a count the 32-bit coverage sums cannot take: the host reports it
-            if (lane == 0) atomicOr(second_count + SC_COMPLAINT, 1ull);
+        if (__any((orm_unit >> 29) != 0u)) {
+            raise_complaint(second_count, lane);
             orm_unit = 0;
         }
         cur_u += wstride;
@@ -1477,9 +1468,8 @@ __device__ __forceinline__ void close_locus(const int64_t l, const int32_t *rec_
     // (only the loci the streaming pass listed come here: everything else was closed there)
     do {
         const int n = P.n, k = P.k;
-        const int64_t slot = unit_slot(l, P.pshift);
-        const size_t rb = rec_base(slot);
-        const int hdr = rec_flags[slot];
+        const size_t rb = rec_base(l);
+        const int hdr = rec_flags[l];
         const bool alive = (hdr & FLAG_ALIVE) != 0;
         const int nk = (hdr >> H_NK_SHIFT) & 7;
         const int ordbits = hdr >> H_ORD_SHIFT;
@@ -1489,10 +1479,9 @@ __device__ __forceinline__ void close_locus(const int64_t l, const int32_t *rec_
 #pragma unroll
             for (int r = 0; r < PG_MAX_OUT; ++r) ids_out[PG_OIX(l, r)] = (r < nk) ? ((ordbits >> (3 * r)) & 7) : -1;
             const double chi2 = alive ? rec[rb] : NAN;
-            const double df = (double)(n * nk) - 1.0;
             n_out[l] = alive ? nk : 0;
             stat_out[l] = chi2;
-            pv_out[l] = alive ? pg_chisq_upper_p(chi2, df, pg_ln_gamma(df / 2.0)) : NAN;
+            pv_out[l] = alive ? close_chisq(chi2, n, nk) : NAN;
             break;
         }
 
@@ -1546,7 +1535,7 @@ __device__ __forceinline__ void close_locus(const int64_t l, const int32_t *rec_
     } while (false);
 }
 
-// ---- ols_iter and chisq_test, order-free (round 4): a LOCUS PER ROW OF LANES instead of a locus per lane ----------------------------
+// ---- ols_iter and chisq_test, order-free: a LOCUS PER ROW OF LANES instead of a locus per lane ----------------------------
 // The streaming pass above reads with the lane-per-locus request pattern (0.68 - 0.74 of the HBM peak with nothing else going on) because
 // the filter's q must be summed in pool order -- and it has to SPECULATE on the surviving pair, because it sees a locus once.  ols_iter
 // and chisq_test do not need pool-order sums: their decisions (which alleles survive, which is the major one, is the fit singular)
@@ -1585,17 +1574,11 @@ __device__ __forceinline__ T row_all(T v, OPF op) {
     if constexpr (LPL >= 64) v = op(v, __shfl_xor(v, 32));
     return v;
 }
-#ifndef RW_UNROLL
-#define RW_UNROLL 2
-#endif
 constexpr int RW_MAXR = 7;              // rounds per locus at most (112 / 16, 224 / 32, 448 / 64 pools per lane)
 constexpr int RW_NP = 11;               // 16-byte pieces per lane and group: 11 KB >= 24 bytes x 448 pools (x 2 loci x 224, x 4 x 112)
 constexpr int RW_BUF = RW_NP * 1024;
 #ifndef RW_DIRECT_OCC
 #define RW_DIRECT_OCC 3
-#endif
-#ifndef RW_DIRECT_SETS
-#define RW_DIRECT_SETS 1
 #endif
 
 template <int OP, int LPL, bool RNS, int K, bool DIRECT>
@@ -1606,9 +1589,9 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
     constexpr int NJ = RNS ? 5 : 6;
     constexpr int GL = 64 / LPL;            // loci per group
     constexpr int TW = (OP == OP_OLS) ? 1 + K : 1; // doubles per pool in the table: w_i (, y_i0, ...)
-    constexpr int RECB = 16 + 16 * K;
+    constexpr int RECB = StagedResult<K>::RECB;
     constexpr int NSUM = 2 + K;             // staged per locus: cs, sum f^2, sum f y_t of the design column (chisq_test: sum_j A_j / cs_j, covered pools)
-    auto aj = [](int jj) { return (RNS && jj >= 4) ? jj + 1 : jj; };
+    auto aj = [](int jj) { return allele_of<RNS>(jj); };
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1617,15 +1600,14 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
     char *buf = lds_raw + wave * PER_WAVE;
     double *sums = reinterpret_cast<double *>(buf + BUFB);
     int32_t *hdrs = reinterpret_cast<int32_t *>(buf + BUFB + 64 * NSUM * 8);
-    char *stage = buf + BUFB + 64 * NSUM * 8 + 64 * 4;
+    const StagedResult<K> res{buf + BUFB + 64 * NSUM * 8 + 64 * 4};
     const double *tab = reinterpret_cast<const double *>(lds_raw + LO_WAVES * PER_WAVE);
     const int n = P.n;
     const int64_t L = P.L;
     const float *tabf = reinterpret_cast<const float *>(lds_raw + LO_WAVES * PER_WAVE + sizeof(double) * TW * n); // the weights in fp32
     {
-        double *t = reinterpret_cast<double *>(lds_raw + LO_WAVES * PER_WAVE);
         float *tf = reinterpret_cast<float *>(lds_raw + LO_WAVES * PER_WAVE + sizeof(double) * TW * n);
-        for (int i = threadIdx.x; i < TW * n; i += LO_THREADS) t[i] = wy[i];
+        load_pool_table<TW>(reinterpret_cast<double *>(lds_raw + LO_WAVES * PER_WAVE), wy, n);
         for (int i = threadIdx.x; i < n; i += LO_THREADS) tf[i] = (float)wy[i * TW];
         __syncthreads();
     }
@@ -1647,11 +1629,7 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
         const uint64_t go = ((uint64_t)pre_u * 64u + (uint64_t)pre_g * GL) * rowb; // (past the batch: the descriptor answers with zeros)
         const uint64_t left = total_bytes > go ? total_bytes - go : 0;
         const uint64_t lim = left < grpb ? left : grpb;                          // this group's bytes only: the rest of the buffer stays zero
-        const uint64_t ub = base0 + (left ? go : 0);
-        const uint32_t nrec = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((lim + 15u) & ~(uint64_t)15));
-        const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub);
-        const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32));
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char *>(((uint64_t)bhi << 32) | blo), 0, nrec, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc = batch_rsrc(base0 + (left ? go : 0), (uint32_t)((lim + 15u) & ~(uint64_t)15));
 #pragma unroll
         for (int i = 0; i < RW_NP; ++i) SR[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (uint32_t)lane * 16u + (uint32_t)i * 1024u, 0, 0);
         if (++pre_g >= LPL) { pre_g = 0; pre_u += wstride; }
@@ -1661,8 +1639,8 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
         for (int i = 0; i < RW_NP; ++i) *reinterpret_cast<uint4_t *>(buf + lane * 16 + i * 1024) = SR[i];
     };
     // DIRECT: the counts of this lane's pools (round t: pool t LPL + li of the row's locus) straight from memory into registers, 16 + 8
-    // bytes per pool; 16 lanes x 24 bytes = 384 contiguous bytes per row and round.  Two register sets: the next group's loads are in
-    // flight while the current group is summed.  Pools past the row's end (the last round) and rounds past the last one point beyond
+    // bytes per pool; 16 lanes x 24 bytes = 384 contiguous bytes per row and round.  One register set: the other waves of the SIMD cover
+    // the wait for the next group's loads.  Pools past the row's end (the last round) and rounds past the last one point beyond
     // the descriptor's range and read zeros.
     struct RowRegs { uint4_t a[RW_MAXR]; uint2_t b[RW_MAXR]; };
     uint32_t voff[RW_MAXR];
@@ -1672,11 +1650,7 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
         const uint64_t go = ((uint64_t)pre_u * 64u + (uint64_t)pre_g * GL) * rowb;
         const uint64_t left = total_bytes > go ? total_bytes - go : 0;
         const uint64_t lim = left < grpb ? left : grpb;
-        const uint64_t ub = base0 + (left ? go : 0);
-        const uint32_t nrec = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lim);
-        const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub);
-        const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ub >> 32));
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char *>(((uint64_t)bhi << 32) | blo), 0, nrec, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc = batch_rsrc(base0 + (left ? go : 0), (uint32_t)lim);
 #pragma unroll
         for (int t = 0; t < RW_MAXR; ++t) {
             R.a[t] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[t], 0, 0);
@@ -1691,9 +1665,6 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
     uint32_t orm_unit = 0;
     int ndirty = 0;
     RowRegs RA;
-#if RW_DIRECT_SETS == 2
-    RowRegs RB;
-#endif
     if constexpr (DIRECT) issue_direct(RA);
     else issue_group();
     for (int64_t unit = wid; unit < nunits; unit += wstride) {
@@ -1786,27 +1757,9 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
             if (__any(band && l < L)) { // the literal q (sync.rs:258-271) of a locus inside the band: every lane of its row, redundantly
                 if (band && l < L) {
                     double qe[NJ];
+                    slotmask = literal_q_slotmask<RNS, TW>(counts, l, n, tab, P, qe);
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) qe[j] = 0.0;
-                    const uint2_t *rp = reinterpret_cast<const uint2_t *>(counts + (size_t)l * (size_t)n * 6); // (its row in memory: rare)
-                    for (int i = 0; i < n; ++i) {
-                        const uint2_t w0 = rp[3 * i], w1 = rp[3 * i + 1], w2 = rp[3 * i + 2];
-                        const uint32_t c0[6] = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y};
-                        uint32_t rs = 0u;
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) rs += c0[aj(j)];
-                        const double rsd = (double)(rs > 1u ? rs : 1u);
-                        const double ri = recip_for_div(rsd);
-                        const double wi = tab[i * TW];
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) qe[j] = qe[j] + div_by((double)c0[aj(j)], rsd, ri) * wi;
-                    }
-                    slotmask = 0;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        slotmask |= !((qe[j] < P.maf) | (qe[j] > (1.00 - P.maf))) ? (1 << j) : 0;
-                        q[j] = (float)qe[j];
-                    }
+                    for (int j = 0; j < NJ; ++j) q[j] = (float)qe[j];
                 }
             }
             int nk = 0, keepmask = 0, sa = 0, sb = 0;
@@ -1988,19 +1941,10 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
             }
         };
         if constexpr (DIRECT) {
-#if RW_DIRECT_SETS == 2
-            for (int g = 0; g < LPL; g += 2) {    // (RA holds group g; the set just summed takes the loads of the group after next)
-                issue_direct(RB);
-                group_body(RA, g);
-                issue_direct(RA);
-                group_body(RB, g + 1);
-            }
-#else
-            for (int g = 0; g < LPL; ++g) {       // (one set: the other waves of the SIMD cover the wait)
+            for (int g = 0; g < LPL; ++g) {
                 group_body(RA, g);
                 issue_direct(RA);
             }
-#endif
         } else {
             for (int g = 0; g < LPL; ++g) {
                 __builtin_amdgcn_wave_barrier();
@@ -2015,15 +1959,7 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
         {
             const int64_t l = unit * 64 + lane;
             const int hdr = hdrs[lane];
-            const bool listed = (hdr & (1 << 30)) != 0;
-            const unsigned long long bal = __ballot(listed);
-            if (bal) {
-                unsigned long long basev = 0;
-                if (lane == 0) basev = atomicAdd(second_count + SC_LIST, (unsigned long long)__popcll(bal));
-                basev = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(basev >> 32)) << 32) |
-                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)basev);
-                if (listed) second[basev + __popcll(bal & ((1ull << lane) - 1ull))] = l;
-            }
+            list_append(second, second_count, (hdr & (1 << 30)) != 0, l, lane);
             const bool simple = (hdr & 1) != 0;
             int nout = 0, idsp = 0;
             double mf = NAN, st[K], pv[K];
@@ -2034,77 +1970,57 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
                     const double pz = (hdr & 2) ? NAN : 0.0;
                     const int nk = (hdr >> 4) & 7;
                     const double chi2 = sums[lane * NSUM + 1] * (sums[lane * NSUM] - 1.0) + pz; // tables/chisq_test.rs:15-31 regrouped
-                    const double df = (double)(n * nk) - 1.0;
-                    const double p = pg_chisq_upper_p(chi2, df, pg_ln_gamma(df / 2.0)); // :33-35
+                    const double p = close_chisq(chi2, n, nk);
                     if (simple) { st[0] = chi2; pv[0] = p; nout = nk; idsp = (hdr >> 8) & 0x7fff; }
                 }
             } else if (__any(simple)) {
                 const double pz = (hdr & 2) ? NAN : 0.0; // a pool uncovered over the survivors: NaN frequencies, NaN sums (sync.rs:176-183)
-                double cs1[1], xx1[1][1], xy1[1][MAXK], b1[MAXK][1], p1[MAXK][1];
-                cs1[0] = sums[lane * NSUM] + pz;
-                xx1[0][0] = sums[lane * NSUM + 1] + pz;
+                double fy[K];
 #pragma unroll
-                for (int t = 0; t < MAXK; ++t) xy1[0][t] = (t < K) ? sums[lane * NSUM + 2 + (t < K ? t : 0)] + pz : 0.0;
-                bool singular;
-                ols_solve<2>(cs1, xx1, xy1, K, P, tcoef, singular, b1, p1);
-                if (simple && !singular) { // Err -> the whole locus is dropped (ols.rs:250-253)
-                    nout = 1;
-                    idsp = (hdr >> 4) & 7;
-                    mf = cs1[0] / (double)n; // ols.rs:266
-#pragma unroll
-                    for (int t = 0; t < K; ++t) { st[t] = b1[t][0]; pv[t] = p1[t][0]; }
-                }
+                for (int t = 0; t < K; ++t) fy[t] = sums[lane * NSUM + 2 + t];
+                close_biallelic_ols<K>(sums[lane * NSUM], sums[lane * NSUM + 1], fy, pz, (hdr >> 4) & 7, simple, P, tcoef, nout, idsp, mf, st, pv);
             }
             // (a listed locus gets the "dropped" pattern here; the second pass overwrites it later in the stream)
-            char *r = stage + (size_t)lane * RECB;
-            *reinterpret_cast<uint2_t *>(r) = uint2_t{(uint32_t)nout, (uint32_t)idsp};
-            *reinterpret_cast<double *>(r + 8) = mf;
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                *reinterpret_cast<double *>(r + 16 + 16 * t) = st[t];
-                *reinterpret_cast<double *>(r + 24 + 16 * t) = pv[t];
-            }
+            res.put(lane, nout, idsp, mf, st, pv);
         }
         __builtin_amdgcn_wave_barrier();
         {   // slot 0 of every output array, 64 consecutive loci: contiguous runs
             const int64_t l0 = unit * 64;
             const int nv = (int)((L - l0) < 64 ? (L - l0) : 64);
-            auto hdr_of = [&](int j) { return *reinterpret_cast<const uint2_t *>(stage + (size_t)j * RECB); };
-            auto dbl_of = [&](int j, int off) { return *reinterpret_cast<const double *>(stage + (size_t)j * RECB + off); };
             if constexpr (OP == OP_CHISQ) {
                 if (lane < nv) { // n_out, the surviving alleles in the slots below it (column order), chi2, p: plain [L] arrays
-                    const uint2_t h = hdr_of(lane);
+                    const uint2_t h = res.hdr(lane);
                     const int no = (int)h.x;
                     O.n_out[l0 + lane] = no;
 #pragma unroll
                     for (int r = 0; r < PG_MAX_OUT; ++r)
                         if (r < no) O.ids[(size_t)r * (size_t)P.L + (size_t)(l0 + lane)] = (int)((h.y >> (3 * r)) & 7u);
-                    O.stat[l0 + lane] = dbl_of(lane, 16);
-                    O.pv[l0 + lane] = dbl_of(lane, 24);
+                    O.stat[l0 + lane] = res.dbl(lane, 16);
+                    O.pv[l0 + lane] = res.dbl(lane, 24);
                 }
             } else if (lane < nv) {
-                const uint2_t h = hdr_of(lane);
+                const uint2_t h = res.hdr(lane);
                 if (coalesced) {
                     __builtin_nontemporal_store((int32_t)h.x, O.n_out + l0 + lane);
                     __builtin_nontemporal_store(h.x ? (int32_t)(h.y & 7u) : -1, O.ids + l0 + lane);
-                    __builtin_nontemporal_store(h.x ? dbl_of(lane, 8) : NAN, O.mf + l0 + lane);
+                    __builtin_nontemporal_store(h.x ? res.dbl(lane, 8) : NAN, O.mf + l0 + lane);
                 } else if (P.t0 == 0) {
                     O.n_out[l0 + lane] = (int32_t)h.x;
                     O.ids[l0 + lane] = h.x ? (int32_t)(h.y & 7u) : -1;
-                    O.mf[l0 + lane] = h.x ? dbl_of(lane, 8) : NAN;
+                    O.mf[l0 + lane] = h.x ? res.dbl(lane, 8) : NAN;
                 }
             }
             // stat / pval: [slot 0][locus][trait of the call]
             for (int e = lane; OP == OP_OLS && e < nv * K; e += 64) {
                 const int j = e / K, t = e - j * K;
-                const bool on = hdr_of(j).x != 0;
+                const bool on = res.hdr(j).x != 0;
                 const size_t o = (size_t)(l0 + j) * P.k_total + P.t0 + t;
-                O.stat[o] = on ? dbl_of(j, 16 + 16 * t) : NAN;
-                O.pv[o] = on ? dbl_of(j, 24 + 16 * t) : NAN;
+                O.stat[o] = on ? res.dbl(j, 16 + 16 * t) : NAN;
+                O.pv[o] = on ? res.dbl(j, 24 + 16 * t) : NAN;
             }
         }
-        if (__any((orm_unit >> 29) != 0u)) { // a count the 32-bit coverage sums cannot take: the host reports it
-            if (lane == 0) atomicOr(second_count + SC_COMPLAINT, 1ull);
+        if (__any((orm_unit >> 29) != 0u)) {
+            raise_complaint(second_count, lane);
             orm_unit = 0;
         }
     }
@@ -2117,9 +2033,8 @@ __global__ __launch_bounds__(LO_THREADS, (DIRECT ? RW_DIRECT_OCC : 2)) void k_ol
 }
 
 // ---- second pass: only the loci the first pass listed ----------------------------------------------
-// ---- second pass: only the loci the first pass listed ----------------------------------------------
 // One lane per listed locus (rows gathered through the list).  The survivors are known now (flags), so the sums are taken over
-// the frequencies of the FILTERED counts, as the reference does (gwas/ols.rs:210-230 -> sync.rs:166-192).  Round 4:
+// the frequencies of the FILTERED counts, as the reference does (gwas/ols.rs:210-230 -> sync.rs:166-192):
 //  * the surviving columns are COMPACTED (NS running columns instead of all six: 3 / 6 / 10 / 15 cross products for 2 / 3 / 4 / 5
 //    survivors instead of 21) and the code is specialised on the largest survivor count of the wave;
 //  * rows still arrive through a wave-private LDS tile in stages of eight pools (48 lanes fetch 4 rows x 192 contiguous bytes per
@@ -2222,7 +2137,7 @@ __device__ __forceinline__ void second_tile(const uint32_t *__restrict__ counts,
         __builtin_amdgcn_wave_barrier();
     }
     auto ajc = [&](int r) { return col[r] & 7; };
-    emit_record<OP, NS, K>(A, n_missing > 0, kp, true, false, valid, rec_flags, rec, unit_slot(l, P.pshift), ajc, P.sort_desc != 0);
+    emit_record<OP, NS, K>(A, n_missing > 0, kp, true, false, valid, rec_flags, rec, l, ajc, P.sort_desc != 0);
 }
 
 // The list grouped by the number of surviving alleles: group b (b + 2 survivors) occupies whole tiles of 64 entries of `sorted`, so
@@ -2239,7 +2154,7 @@ __device__ __forceinline__ void group_tiles(const unsigned long long *__restrict
 
 // how many listed loci keep 2, 3, .. alleles (five atomics per wave)
 __global__ __launch_bounds__(256) void k_locus_hist(const int64_t *__restrict__ second, unsigned long long *second_count,
-                                                    const int32_t *__restrict__ rec_flags, int64_t total, int pshift) {
+                                                    const int32_t *__restrict__ rec_flags, int64_t total) {
     const int lane = threadIdx.x & 63;
     int c[LO_NB];
 #pragma unroll
@@ -2247,7 +2162,7 @@ __global__ __launch_bounds__(256) void k_locus_hist(const int64_t *__restrict__ 
     const int64_t nw = (int64_t)gridDim.x * 4;
     for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t * 64 < total; t += nw) {
         const int64_t e = t * 64 + lane;
-        const int nk = e < total ? ((rec_flags[unit_slot(second[e], pshift)] >> H_NK_SHIFT) & 7) : 0;
+        const int nk = e < total ? ((rec_flags[second[e]] >> H_NK_SHIFT) & 7) : 0;
 #pragma unroll
         for (int b = 0; b < LO_NB; ++b) c[b] += __popcll(__ballot(nk == b + 2));
     }
@@ -2260,8 +2175,7 @@ __global__ __launch_bounds__(256) void k_locus_hist(const int64_t *__restrict__ 
 
 constexpr int SORT_CH = 16; // tiles per wave and reservation
 __global__ __launch_bounds__(256) void k_locus_sort(const int64_t *__restrict__ second, unsigned long long *second_count,
-                                                    const int32_t *__restrict__ rec_flags, int64_t *__restrict__ sorted, int64_t total,
-                                                    int pshift) {
+                                                    const int32_t *__restrict__ rec_flags, int64_t *__restrict__ sorted, int64_t total) {
     const int lane = threadIdx.x & 63;
     int64_t cnt[LO_NB], first[LO_NB + 1];
     group_tiles(second_count, cnt, first);
@@ -2279,7 +2193,7 @@ __global__ __launch_bounds__(256) void k_locus_sort(const int64_t *__restrict__ 
             const int64_t e = (t0 + u) * 64 + lane;
             const bool valid = e < total;
             lv[u] = valid ? second[e] : 0;
-            nkv[u] = valid ? ((rec_flags[unit_slot(lv[u], pshift)] >> H_NK_SHIFT) & 7) : 0;
+            nkv[u] = valid ? ((rec_flags[lv[u]] >> H_NK_SHIFT) & 7) : 0;
 #pragma unroll
             for (int b = 0; b < LO_NB; ++b) c[b] += __popcll(__ballot(nkv[u] == b + 2));
         }
@@ -2309,7 +2223,7 @@ __global__ __launch_bounds__(256) void k_locus_sort(const int64_t *__restrict__ 
 // compiled for -- the group's when the list is grouped (k_locus_sort), the largest of the tile's loci when it is not (short lists)
 __device__ __forceinline__ int tile_entry(const int64_t t, const int grouped, const int64_t total, const int64_t (&cnt)[LO_NB],
                                           const int64_t (&first)[LO_NB + 1], const int64_t *__restrict__ list,
-                                          const int32_t *__restrict__ rec_flags, const int pshift, const int lane, int64_t &l, bool &valid) {
+                                          const int32_t *__restrict__ rec_flags, const int lane, int64_t &l, bool &valid) {
     if (grouped) {
         int b = 0;
 #pragma unroll
@@ -2326,7 +2240,7 @@ __device__ __forceinline__ int tile_entry(const int64_t t, const int grouped, co
     const int64_t e = t * 64 + lane;
     valid = e < total;
     l = list[valid ? e : total - 1];
-    int nsw = (rec_flags[unit_slot(l, pshift)] >> H_NK_SHIFT) & 7;
+    int nsw = (rec_flags[l] >> H_NK_SHIFT) & 7;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) nsw = max(nsw, __shfl_xor(nsw, off));
     return __builtin_amdgcn_readfirstlane(nsw);
@@ -2349,11 +2263,11 @@ __global__ __launch_bounds__(LO_THREADS) void k_locus_second(
     for (int64_t t = (int64_t)blockIdx.x * LO_WAVES + wave; t < ntile; t += wstride) {
         int64_t l;
         bool valid;
-        const int ns = tile_entry(t, grouped, total, cnt, first, list, rec_flags, P.pshift, lane, l, valid);
+        const int ns = tile_entry(t, grouped, total, cnt, first, list, rec_flags, lane, l, valid);
         __builtin_amdgcn_wave_barrier();
         lidx[lane] = l;
         __builtin_amdgcn_wave_barrier();
-        const int mask = rec_flags[unit_slot(l, P.pshift)];
+        const int mask = rec_flags[l];
         // (the arithmetic of a locus does not depend on the variant: padding columns contribute exact zeros to sums that are never read)
         if (ns <= 2) second_tile<OP, 2, K, PB>(counts, Y, rec_flags, rec, tile, lidx, l, mask, valid, P, lane);
         else if (ns == 3) second_tile<OP, 3, K, PB>(counts, Y, rec_flags, rec, tile, lidx, l, mask, valid, P, lane);
@@ -2378,7 +2292,7 @@ __global__ __launch_bounds__(256) void k_locus_close(const int32_t *rec_flags, c
     for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < ntile; t += nw) {
         int64_t l;
         bool valid;
-        const int ns = tile_entry(t, grouped, total, cnt, first, list, rec_flags, P.pshift, lane, l, valid);
+        const int ns = tile_entry(t, grouped, total, cnt, first, list, rec_flags, lane, l, valid);
         if (!valid) continue;
         if (!grouped) close_locus<OP, 0>(l, rec_flags, rec, tcoef, O.n_out, O.ids, O.mf, O.stat, O.pv, P);
         else if (ns == 2) close_locus<OP, 2>(l, rec_flags, rec, tcoef, O.n_out, O.ids, O.mf, O.stat, O.pv, P);
@@ -2410,6 +2324,22 @@ struct StreamWs { // device pointers into the context's workspace
     int32_t *flags;
 };
 
+// The kernel instance of a run-time choice: `inst(r, a, c)` is called with rns, alt and c (one of CS...) as compile-time constants
+// (std::integral_constant) and returns the address of its instance.
+template <int... CS, typename F>
+const void *pick_kernel(bool rns, bool alt, int c, F inst) {
+    const void *k = nullptr;
+    auto one = [&](auto r, auto a, auto cc) {
+        if (rns == decltype(r)::value && alt == decltype(a)::value && c == decltype(cc)::value) k = inst(r, a, cc);
+    };
+    auto four = [&](auto cc) {
+        one(std::true_type{}, std::true_type{}, cc); one(std::true_type{}, std::false_type{}, cc);
+        one(std::false_type{}, std::true_type{}, cc); one(std::false_type{}, std::false_type{}, cc);
+    };
+    (four(std::integral_constant<int, CS>{}), ...);
+    return k;
+}
+
 template <int OP>
 int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const StreamWs &W, const StreamOut &O, const LocusParams &P, int kg, bool rns,
                   int64_t *listed, bool *complaint) {
@@ -2429,12 +2359,10 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
     const int64_t blocks = (nunits + LO_WAVES - 1) / LO_WAVES;
     const int64_t cap = (int64_t)ctx->cus * LO_BLOCKS_DEF; // the resident blocks: one long sequence of units per wave
     const int grid = (int)(blocks < cap ? blocks : cap);
-    auto pick = [&]() -> const void * {
-        if (OP == OP_OLS && kg == 2)
-            return rns ? (const void *)k_locus_stream<OP, true, (OP == OP_OLS ? 2 : 1)> : (const void *)k_locus_stream<OP, false, (OP == OP_OLS ? 2 : 1)>;
-        return rns ? (const void *)k_locus_stream<OP, true, 1> : (const void *)k_locus_stream<OP, false, 1>;
-    };
-    const void *kstream = pick();
+    const bool two = OP == OP_OLS && kg == 2; // two traits in one launch: ols_iter only
+    const void *kstream = pick_kernel<0>(rns, two, 0, [](auto r, auto a, auto) {
+        return (const void *)k_locus_stream<OP, decltype(r)::value, (OP == OP_OLS && decltype(a)::value) ? 2 : 1>;
+    });
     PG_HIP(ctx, hipFuncSetAttribute(kstream, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     PG_HIP(ctx, hipMemsetAsync(W.second_count, 0, 8 * SC_WORDS, ctx->stream)); // the list's length and groups, the sort's cursors, the streaming pass' complaint flag
     // ols_iter from 32 pools up: the order-free kernel (a locus per row of 16 / 32 / 64 lanes, coalesced reads) or the streaming pass
@@ -2461,20 +2389,11 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
             // PG_SW_ROWS_DIRECT (=0) puts chisq_test back on the buffer: the tests run both.
             bool direct = OP == OP_CHISQ;
             if (const char *e = pg_switch(PG_SW_ROWS_DIRECT)) direct = direct && std::strcmp(e, "0") != 0;
-            auto pick_rows = [&]() -> const void * {
-                if constexpr (OP == OP_CHISQ) {
-#define PG_ROWS(LPLV) (direct ? (rns ? (const void *)k_ols_rows<OP, LPLV, true, 1, true> : (const void *)k_ols_rows<OP, LPLV, false, 1, true>) \
-                              : (rns ? (const void *)k_ols_rows<OP, LPLV, true, 1, false> : (const void *)k_ols_rows<OP, LPLV, false, 1, false>))
-                    return lpl == 16 ? PG_ROWS(16) : (lpl == 32 ? PG_ROWS(32) : PG_ROWS(64));
-#undef PG_ROWS
-                } else {
-#define PG_ROWS(LPLV) (kg == 2 ? (rns ? (const void *)k_ols_rows<OP, LPLV, true, 2, false> : (const void *)k_ols_rows<OP, LPLV, false, 2, false>) \
-                               : (rns ? (const void *)k_ols_rows<OP, LPLV, true, 1, false> : (const void *)k_ols_rows<OP, LPLV, false, 1, false>))
-                    return lpl == 16 ? PG_ROWS(16) : (lpl == 32 ? PG_ROWS(32) : PG_ROWS(64));
-#undef PG_ROWS
-                }
-            };
-            const void *krows = pick_rows();
+            // (the second choice: chisq_test register / buffer variant, ols_iter one / two traits)
+            const void *krows = pick_kernel<16, 32, 64>(rns, OP == OP_CHISQ ? direct : two, lpl, [](auto r, auto a, auto c) {
+                constexpr bool ALT = decltype(a)::value;
+                return (const void *)k_ols_rows<OP, decltype(c)::value, decltype(r)::value, (OP == OP_OLS && ALT) ? 2 : 1, OP == OP_CHISQ && ALT>;
+            });
             const size_t per_wave = (direct ? 0 : (size_t)RW_BUF) + 64 * (2 + kg) * 8 + 64 * 4 + 64 * (16 + 16 * kg);
             const size_t shr = (size_t)LO_WAVES * per_wave + sizeof(double) * (size_t)TW * n + sizeof(float) * (size_t)n;
             PG_HIP(ctx, hipFuncSetAttribute(krows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shr));
@@ -2513,15 +2432,9 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
     if (total == 0 || *complaint) return PG_OK;
     if (kid >= 0) pg_prof_begin(ctx, kid | PG_PROF_CONT);
     const bool p16 = ((int64_t)n * 24) % 16 == 0;
-    auto pick_second = [&]() -> const void * {
-        constexpr int KK = (OP == OP_OLS ? 2 : 1);
-        if (OP == OP_OLS && kg == 2)
-            return rns ? (p16 ? (const void *)k_locus_second<OP, 5, KK, 16> : (const void *)k_locus_second<OP, 5, KK, 8>)
-                       : (p16 ? (const void *)k_locus_second<OP, 6, KK, 16> : (const void *)k_locus_second<OP, 6, KK, 8>);
-        return rns ? (p16 ? (const void *)k_locus_second<OP, 5, 1, 16> : (const void *)k_locus_second<OP, 5, 1, 8>)
-                   : (p16 ? (const void *)k_locus_second<OP, 6, 1, 16> : (const void *)k_locus_second<OP, 6, 1, 8>);
-    };
-    const void *ksecond = pick_second();
+    const void *ksecond = pick_kernel<8, 16>(rns, two, p16 ? 16 : 8, [](auto r, auto a, auto pb) {
+        return (const void *)k_locus_second<OP, decltype(r)::value ? 5 : 6, (OP == OP_OLS && decltype(a)::value) ? 2 : 1, decltype(pb)::value>;
+    });
     const size_t shmem2 = (size_t)LO_WAVES * LO_TILEB + (size_t)LO_WAVES * 64 * sizeof(int64_t);
     PG_HIP(ctx, hipFuncSetAttribute(ksecond, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem2));
     {
@@ -2535,10 +2448,10 @@ int launch_passes(pg_ctx *ctx, int kid, const uint32_t *counts_dev, const Stream
             // (few, long-running waves: every wave ends in five atomics on the same five words -- with a wave per tile they took
             // 0.34 ms per million entries, all of it contention)
             hipLaunchKernelGGL(k_locus_hist, dim3((unsigned)(wants < (int64_t)ctx->cus ? wants : (int64_t)ctx->cus)), dim3(256), 0, ctx->stream,
-                               (const int64_t *)W.second, W.second_count, (const int32_t *)W.flags, total, P.pshift);
+                               (const int64_t *)W.second, W.second_count, (const int32_t *)W.flags, total);
             const int64_t wantq = (tiles + 4 * SORT_CH - 1) / (4 * SORT_CH);
             hipLaunchKernelGGL(k_locus_sort, dim3((unsigned)(wantq < caps ? wantq : caps)), dim3(256), 0, ctx->stream,
-                               (const int64_t *)W.second, W.second_count, (const int32_t *)W.flags, W.sorted, total, P.pshift);
+                               (const int64_t *)W.second, W.second_count, (const int32_t *)W.flags, W.sorted, total);
             list = W.sorted;
         }
         const double *a2 = W.Y;
@@ -2581,7 +2494,6 @@ inline LocusParams filter_params(int64_t L, int n, const pg_filter *flt) {
     std::memset(&P, 0, sizeof P);
     P.L = L; P.n = n;
     P.remove_ns = flt->remove_ns ? 1 : 0;
-    P.pshift = 0; // records and flags are indexed by the locus
     P.min_cov = (double)flt->min_coverage_depth;
     P.maf = flt->min_allele_frequency;
     P.max_miss = flt->max_missingness_rate;
@@ -2752,13 +2664,13 @@ __device__ __forceinline__ int load_ncols(int hdr, int kpm1) {
 }
 
 __global__ __launch_bounds__(256) void k_load_count(const int32_t *__restrict__ flags, const int64_t *__restrict__ order,
-                                                    int64_t L, int pshift, int kpm1, int32_t *__restrict__ local,
+                                                    int64_t L, int kpm1, int32_t *__restrict__ local,
                                                     int64_t *__restrict__ blocksum) {
     __shared__ int sc[256];
     const int tid = threadIdx.x;
     const int64_t oi = (int64_t)blockIdx.x * 256 + tid;
     int c = 0;
-    if (oi < L) c = load_ncols(flags[unit_slot(order ? order[oi] : oi, pshift)], kpm1);
+    if (oi < L) c = load_ncols(flags[order ? order[oi] : oi], kpm1);
     sc[tid] = c;
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {
@@ -2773,8 +2685,8 @@ __global__ __launch_bounds__(256) void k_load_count(const int32_t *__restrict__ 
 
 __global__ __launch_bounds__(256) void k_load_emit(const uint32_t *__restrict__ counts, const int32_t *__restrict__ flags,
                                                    const int64_t *__restrict__ order, const int32_t *__restrict__ local,
-                                                   const int64_t *__restrict__ blockoff, int64_t L, int n, int pshift,
-                                                   int kpm1, const int32_t *__restrict__ pool_map, int n_out,
+                                                   const int64_t *__restrict__ blockoff, int64_t L, int n, int kpm1,
+                                                   const int32_t *__restrict__ pool_map, int n_out,
                                                    double *__restrict__ G, int64_t ld, int64_t *__restrict__ col_locus,
                                                    int32_t *__restrict__ col_allele, double *__restrict__ cov) {
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2782,7 +2694,7 @@ __global__ __launch_bounds__(256) void k_load_emit(const uint32_t *__restrict__ 
     if (oi >= L) return;
     const int pool = (int)(gid - oi * n);
     const int64_t l = order ? order[oi] : oi;
-    const int hdr = flags[unit_slot(l, pshift)];
+    const int hdr = flags[l];
     const int ncols = load_ncols(hdr, kpm1);
     if (ncols == 0) return;
     const int64_t off = blockoff[oi >> 8] + local[oi];
@@ -2873,7 +2785,7 @@ int load_plan(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const d
     const size_t t_total = off; off = up16(off + 8);
     const size_t t_pmap = off; off = up16(off + sizeof(int32_t) * (size_t)n);
     FilterPass F;
-    const int kpm1 = keep_p_minus_1 ? 1 : 0, pshift = 0; // flags are indexed by the locus
+    const int kpm1 = keep_p_minus_1 ? 1 : 0;
     int rc = filter_pass(ctx, "load", -1, p_out != nullptr, counts_dev, L, n, pool_sizes, flt, kpm1, off, &F);
     if (rc) return rc;
     const StreamWs &W = F.W;
@@ -2881,7 +2793,7 @@ int load_plan(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const d
     int32_t *local = reinterpret_cast<int32_t *>(tail + t_local);
     int64_t *bsum = reinterpret_cast<int64_t *>(tail + t_bsum), *boff = reinterpret_cast<int64_t *>(tail + t_boff);
     int64_t *tot_dev = reinterpret_cast<int64_t *>(tail + t_total);
-    hipLaunchKernelGGL(k_load_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, W.flags, order_dev, L, pshift, kpm1, local, bsum);
+    hipLaunchKernelGGL(k_load_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, W.flags, order_dev, L, kpm1, local, bsum);
     pg_scan_blocks(ctx, bsum, nb, boff, tot_dev); // pg_text_steps.h
     PG_HIP(ctx, hipGetLastError());
     int64_t tot = 0;
@@ -2892,7 +2804,7 @@ int load_plan(pg_ctx *ctx, const uint32_t *counts_dev, int64_t L, int n, const d
     ctx->load_valid = true;
     ctx->load_counts = counts_dev; ctx->load_order = order_dev;
     ctx->load_L = L; ctx->load_total = tot; ctx->load_nunits = 0;
-    ctx->load_n = n; ctx->load_kpm1 = kpm1; ctx->load_pshift = pshift;
+    ctx->load_n = n; ctx->load_kpm1 = kpm1;
     ctx->load_off_flags = (size_t)(reinterpret_cast<char *>(W.flags) - ws); ctx->load_off_local = F.tail + t_local;
     ctx->load_off_blockoff = F.tail + t_boff; ctx->load_off_poolmap = F.tail + t_pmap;
     return PG_OK;
@@ -2922,8 +2834,8 @@ int load_emit(pg_ctx *ctx, const int32_t *pool_map, int n_out, double *G_dev, in
     hipLaunchKernelGGL(k_load_emit, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, ctx->load_counts,
                        reinterpret_cast<const int32_t *>(ws + ctx->load_off_flags), ctx->load_order,
                        reinterpret_cast<const int32_t *>(ws + ctx->load_off_local),
-                       reinterpret_cast<const int64_t *>(ws + ctx->load_off_blockoff), ctx->load_L, n, ctx->load_pshift,
-                       ctx->load_kpm1, pmap_dev, n_out, G_dev, ld, col_locus_dev, col_allele_dev, cov_dev);
+                       reinterpret_cast<const int64_t *>(ws + ctx->load_off_blockoff), ctx->load_L, n, ctx->load_kpm1,
+                       pmap_dev, n_out, G_dev, ld, col_locus_dev, col_allele_dev, cov_dev);
     PG_HIP(ctx, hipGetLastError());
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // pool_map is the caller's
     return PG_OK;

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (here, no GPU needed): tools/exp_locus.sh <tag> "<-D flags>"   -> tools/exp/libpoolgen_hip_<tag>.so
-# Timing experiments on the count operators: pg_locus_ops.hip rebuilt with experiment macros, linked with the shipped objects.
+# Timing experiments on the count operators: pg_locus_ops.hip rebuilt with the given -D flags (LO_WAVES_DEF, LO_BLOCKS_DEF,
+# RW_DIRECT_OCC), linked with the shipped objects.
 # Run on the GPU box with POOLGEN_HIP_LIB=tools/exp/libpoolgen_hip_<tag>.so python tools/bench_ops.py 100 1000000
 set -e
 cd "$(dirname "$0")/../poolgen_amd/csrc"
