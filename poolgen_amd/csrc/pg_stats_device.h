@@ -12,6 +12,10 @@
 #include <hip/hip_runtime.h>
 
 #define PG_EPS 2.220446049250313e-16
+// statrs' checked_beta_reg sets its prefactor to 0 where ulps_eq!(h, 1.0) (approx' defaults: f64::EPSILON, 4 ulps), so
+// StudentsT::cdf is exactly 0.5 +- 0.5 for 1 - h <= 4 * 2^-53 (|t| up to ~2e-8 sqrt(df)) where the true two-sided tail is
+// 1 - 2.4e-7 at 200 pools.  1 - h is exact for h in [0.5, 1].
+#define PG_T_H_IS_ONE(h) (1.0 - (h) <= 4.440892098500626e-16)
 
 // Two-sided p-value P(|T_df| > |t|).  coef/ncoef from pg_tdist_coef(df) (host): ncoef is a multiple of 8 (zero padded).
 // The series sum_j coef[j] h^j has ~df/2 terms (99 at 200 pools).  A plain Horner loop is ONE dependent chain of that many
@@ -25,6 +29,7 @@ __device__ __forceinline__ double pg_t_two_sided_p(double t_abs, int df,
     // Same input quantisation as statrs StudentsT::cdf: everything is a function of the ROUNDED
     // h = nu / (nu + t*t) and of 1 - h, so that for |t| << sqrt(nu) (where h rounds towards 1 and
     // the reference's p-value is quantised to 1 - c*sqrt(1-h)) both sides see the same argument.
+    // statrs' beta_reg also takes an h within four ulps of 1 for 1 (ulps_eq!, PG_T_H_IS_ONE): the tail is exactly 1 there.
     const double nu = (double)df;
     const double c2 = nu / (nu + t_abs * t_abs); // h = cos^2(theta)
     const double s = sqrt(1.0 - c2);             // sin(theta)
@@ -47,6 +52,7 @@ __device__ __forceinline__ double pg_t_two_sided_p(double t_abs, int df,
     }
     double p = 1.0 - A;
     p = p < 0.0 ? 0.0 : p;
+    p = PG_T_H_IS_ONE(c2) ? 1.0 : p;
     return p > 1.0 ? 1.0 : p;
 }
 
@@ -80,6 +86,8 @@ __device__ __forceinline__ void pg_t_two_sided_p_x2(double ta, double tb, int df
     }
     pa = 1.0 - Aa; pa = pa < 0.0 ? 0.0 : pa; pa = pa > 1.0 ? 1.0 : pa;
     pb = 1.0 - Ab; pb = pb < 0.0 ? 0.0 : pb; pb = pb > 1.0 ? 1.0 : pb;
+    pa = PG_T_H_IS_ONE(ca) ? 1.0 : pa;
+    pb = PG_T_H_IS_ONE(cb2) ? 1.0 : pb;
     if (isinf(ta)) pa = 0.0;
     if (isinf(tb)) pb = 0.0;
 }
