@@ -37,8 +37,8 @@ constexpr int KIN_TPW = 96 / KIN_WAVES;  // max tiles per wave (>= ceil(91 / wav
 #endif
 constexpr int KIN_KC = KIN_KC_DEF;  // loci per LDS stage (4 loci = one MFMA k-step)
 constexpr int KIN_PPT = (KIN_KC * 128 + KIN_THREADS - 1) / KIN_THREADS;  // 16-byte staging pieces per thread per stage (13-tile kernels: per staging half)
-// The 13-tile kernels (193..208 pools, 16 waves) run stages of 32 loci: one barrier and one hand-over per 32 loci, and two loci
-// per wave for the fused sums.  They are STAGED in halves of KIN_KC loci (same registers, same pieces per thread), and the
+// The 13-tile kernels (193..208 pools, 16 waves) run stages of 32 loci: one barrier and one hand-over per 32 loci, and 8 tasks of
+// 4 loci for the fused sums.  They are STAGED in halves of KIN_KC loci (same registers, same pieces per thread), and the
 // launcher's slab rule stays in units of KIN_KC, so a slab may end in a half stage, which the kernel peels.
 constexpr int KC13 = 32;
 constexpr bool KIN_HAS13 = (KIN_WAVES == 16); // (the 8-wave build never runs the 13-tile shape and does not build its kernels)
@@ -357,7 +357,8 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
     // the pools 4 apiece; the 64 partials per value are transposed through a wave-private LDS scratch
     // so that row v of the wave (16 lanes) holds value v, 4 partials per lane, and a 4-step intra-row
     // DPP shift-add finishes the sum in lanes 15/31/47/63 -- no ds_bpermute, no cross-row step, no
-    // extra barrier (a wave's own LDS writes and reads are ordered).
+    // extra barrier (a wave's own LDS writes and reads are ordered).  (The 13-tile kernels form the same sums by DPP rows, without
+    // the scratch and the phenotype registers: spec_rows below.)
     const int NV = 2 + P.k;
     double *scratch = ylds + KIN_FUSE_MAXK * 256 + wave * (4 * 64); // [4 values][64 lanes]
     // this lane's four pools' centred phenotypes: registers, not one more LDS read per use
@@ -442,7 +443,7 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
             // feeds its <= 6 tiles from them.  The stage barrier sits in front of the LAST k-step's MFMAs: their
             // operands are already in registers, and the first reads of the next stage hide behind them.
             constexpr int NC = kin13_ncols(W), NT = kin13_ntiles(W);
-            static_assert(KIN_WAVES == 16 && KC13 == 2 * KIN_KC && KC13 == 2 * KIN_WAVES, "a 32-locus stage: two staging halves, two loci per wave");
+            static_assert(KIN_WAVES == 16 && KC13 == 2 * KIN_KC && KC13 == 2 * KIN_WAVES, "a 32-locus stage: two staging halves, 8 four-locus tasks for 8 of the waves");
             static_assert(NC <= KIN13_MAXC, "fragment registers");
             // A stage is KC13 = 32 loci (8 k-steps, one barrier).  Within ONE stage buffer every k-step, tile column, staging row and
             // fused-sum row is a COMPILE-TIME offset from a per-lane base, so a fragment, strip, rotated-diagonal, staging-store or
@@ -563,95 +564,75 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                     }
                 });
             };
-            // ---- FUSE: the per-locus sums of locus W of the stage (see spec_pass), with the row a compile-time offset from the lane's
-            // pool pointer.  A lane of the fourth 64-pool group that lies past the last pool reads column 0, the shift itself: its
-            // d is +0.0 as in spec_pass, without a clamp or a select.  The sums leave through a buffer descriptor that ends with this
-            // workgroup's loci (a locus past the end is out of range and dropped by the hardware), offset and lane predicate kept.
-            uint32_t srow = lds0 + (uint32_t)(lane * 8), srow3 = lds0 + (uint32_t)((lane + 192 < P.n ? lane + 192 : 0) * 8);
-            const bool sp_on = (lane & 15) == 15 && (lane >> 4) < NV;
-            uint32_t sp_voff = (uint32_t)((W * NV + (lane >> 4)) * 8);
+            // ---- FUSE: the per-locus sums by DPP rows.  A TASK is 4 consecutive loci of the stage: row r = lane >> 4 of the wave is
+            // locus r of the task, and lane i = lane & 15 of the row sums the 13 pools i, i + 16, .., i + 192 of that locus -- slot j
+            // of the chain is tile column j, so its address is the fragment base `lb` plus an immediate (k-step = task, column j).
+            // Within a 32-lane half the rows r, r + 1 and i = 0..15 read 32 consecutive doubles (pitch 208 = 16 mod 32): no bank
+            // conflict; the centred phenotype of the slot is the same address in all four rows (a broadcast over 16 banks).
+            // Only slot 12 (pools 192 + i) can lie past the last pool: such a lane reads column 0 of its row, the shift itself, so
+            // its d is +0.0 exactly -- no select, no correction after the sum (which would cancel on near-fixed loci) -- and its
+            // phenotype is the zero padding.  The four intra-row DPP shift-adds per value leave each locus's total in lane 15 of
+            // its row: no transpose, no scratch, no wave barrier.  13 x (sub, add, fma, fma) + 3 x 4 DPP adds = 64 f64
+            // instructions per 4 loci and one trait, 13 x 5 + 16 = 81 for two.  The order of the operations of a row does not
+            // depend on the task or the stage kind, so a locus has the same sums wherever it sits in a slab.
+            // The sums leave through a buffer descriptor that ends with this workgroup's loci (a locus past the end is out of range
+            // and dropped by the hardware), offset and lane predicate kept.
+            uint32_t srow0 = lds0 + (uint32_t)(kq * LD13 * 8), srow12 = lds0 + (uint32_t)((kq * LD13 + (fi + 192 < P.n ? fi + 192 : 0)) * 8);
+            // (behind the two stage buffers: not flipped, and past the 16-bit offset field -- hidden from the compiler like the flipped
+            //  bases, or it keeps the small part and pays every read with a v_add_u32 of the large one)
+            uint32_t ybase = lds0 + (uint32_t)((2 * BUF13 + fi) * 8);
+            if constexpr (FUSE) asm("" : "+v"(ybase));
+            const bool sp_on = fi == 15;
+            // a wave's task is (W & 7) wherever it has one (see below), so the row's offset in the sums is kept whole and advances by one stage
+            uint32_t sp_voff = (uint32_t)((4 * (W & 7) + kq) * 8) * (uint32_t)NV;
             const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
                 FUSE ? P.spec + l_begin * NV : nullptr, 0, FUSE ? (int)(uint32_t)((uint64_t)(l_end > l_begin ? l_end - l_begin : 0) * NV * 8) : 0, 0x00020000);
-            const double *sc13 = scratch + (lane >> 4) * 64 + (lane & 15);
-            // The sums of NL loci of the stage -- W and W + 16 in a whole stage, W alone in a half stage -- as NL INDEPENDENT chains
-            // issued together: all row reads first, the f64 sums interleaved, the two transposes through the wave's scratch back to
-            // back (the second locus's partials are written behind the first's reads without waiting for their data: a wave's LDS
-            // operations execute in order), the DPP adds interleaved, then the stores.  Per locus the f64 operations and their
-            // order are those of spec_pass, so the sums are the same bits whatever the stage length.
-            auto spec13 = [&](auto nlc) __attribute__((always_inline)) {
-                constexpr int NL = decltype(nlc)::value;
-                double shift[NL], g[NL][4], s1[NL], s2[NL], sy[NL][KIN_FUSE_MAXK], d[NL][4], part[NL][4], tot[NL];
-                static_for<NL>([&](auto jc) __attribute__((always_inline)) {
-                    constexpr int jl = decltype(jc)::value, ro = (W + KIN_WAVES * jl) * LD13;
+            auto spec_rows = [&](auto nyc) __attribute__((always_inline)) { // task W & 7 of the buffer the bases point at, NY traits
+                constexpr int NY = decltype(nyc)::value, ro = 4 * (W & 7) * LD13;
+                const double shift = ldv(srow0, ro); // the same address in the 16 lanes of a row: a broadcast
+                double s1 = 0.0, s2 = 0.0, sy[NY];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) g[jl][j] = j < 3 ? ldv(srow, ro + 64 * j) : ldv(srow3, ro);
+                for (int t = 0; t < NY; ++t) sy[t] = 0.0;
+                static_for<13>([&](auto jc) __attribute__((always_inline)) {
+                    constexpr int j = decltype(jc)::value;
+                    const double d = (j < 12 ? ldv(lb, ro + 16 * j) : ldv(srow12, ro)) - shift;
+                    s1 += d;
+                    s2 = fma(d, d, s2);
+#pragma unroll
+                    for (int t = 0; t < NY; ++t) sy[t] = fma(d, ldv(ybase, t * 256 + 16 * j), sy[t]);
                 });
-                // the shift is pool 0 of the row, which lane 0 has just read: taken from there into scalar registers (the same value as
-                // spec_pass's broadcast read, without a read, a base register and two vector registers of its own)
+                double tot[2 + NY];
+                tot[0] = s1; tot[1] = s2;
 #pragma unroll
-                for (int jl = 0; jl < NL; ++jl)
-                    shift[jl] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(g[jl][0])), __builtin_amdgcn_readfirstlane(__double2loint(g[jl][0])));
+                for (int t = 0; t < NY; ++t) tot[2 + t] = sy[t];
 #pragma unroll
-                for (int jl = 0; jl < NL; ++jl) {
-                    s1[jl] = 0.0; s2[jl] = 0.0;
+                for (int v = 0; v < 2 + NY; ++v) tot[v] = dpp_add<0x111, 0xf>(tot[v]); // row_shr:1
 #pragma unroll
-                    for (int t = 0; t < KIN_FUSE_MAXK; ++t) sy[jl][t] = 0.0;
-                }
+                for (int v = 0; v < 2 + NY; ++v) tot[v] = dpp_add<0x112, 0xf>(tot[v]); // row_shr:2
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int v = 0; v < 2 + NY; ++v) tot[v] = dpp_add<0x114, 0xf>(tot[v]); // row_shr:4
 #pragma unroll
-                    for (int jl = 0; jl < NL; ++jl) {
-                        d[jl][j] = g[jl][j] - shift[jl];
-                        s1[jl] += d[jl][j];
-                        s2[jl] = fma(d[jl][j], d[jl][j], s2[jl]);
-                        sy[jl][0] = fma(d[jl][j], yreg[0][j], sy[jl][0]);
-                    }
-                const bool two = P.k > 1; // wave-uniform
-                if (two) { // (the second trait's phenotypes are read here, not kept: the one-trait loop has no registers for them)
-                    double y1[4];
-                    // (behind the two stage buffers, i.e. ylds[256 + ...]; spelled off `lds` because capturing `ylds` in this lambda
-                    //  changes the code the compiler emits for the kernels of the OTHER shapes, which must stay as they are)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) y1[j] = lds[2 * BUF13 + 256 + lane + 64 * j];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int jl = 0; jl < NL; ++jl) sy[jl][1] = fma(d[jl][j], y1[j], sy[jl][1]);
-                }
-#pragma unroll
-                for (int jl = 0; jl < NL; ++jl) {
-                    scratch[lane] = s1[jl];
-                    scratch[64 + lane] = s2[jl];
-                    scratch[2 * 64 + lane] = sy[jl][0];
-                    if (two) scratch[3 * 64 + lane] = sy[jl][1];
-                    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) part[jl][q] = sc13[16 * q];
-                    __builtin_amdgcn_wave_barrier();
-                }
-#pragma unroll
-                for (int jl = 0; jl < NL; ++jl) tot[jl] = (part[jl][0] + part[jl][1]) + (part[jl][2] + part[jl][3]);
-#pragma unroll
-                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x111, 0xf>(tot[jl]); // row_shr:1
-#pragma unroll
-                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x112, 0xf>(tot[jl]); // row_shr:2
-#pragma unroll
-                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x114, 0xf>(tot[jl]); // row_shr:4
-#pragma unroll
-                for (int jl = 0; jl < NL; ++jl) tot[jl] = dpp_add<0x118, 0xf>(tot[jl]); // row_shr:8 -> lane 15 of row v holds value v
+                for (int v = 0; v < 2 + NY; ++v) tot[v] = dpp_add<0x118, 0xf>(tot[v]); // row_shr:8 -> lane 15 of row r holds the totals of locus r
                 if (sp_on) {
 #pragma unroll
-                    for (int jl = 0; jl < NL; ++jl)
-                        __builtin_amdgcn_raw_buffer_store_b64((uint2_t){(uint32_t)__double2loint(tot[jl]), (uint32_t)__double2hiint(tot[jl])}, srsrc,
-                                                              sp_voff + (uint32_t)(KIN_WAVES * jl * 8) * (uint32_t)NV, 0, 0);
+                    for (int v = 0; v < 2 + NY; ++v)
+                        __builtin_amdgcn_raw_buffer_store_b64((uint2_t){(uint32_t)__double2loint(tot[v]), (uint32_t)__double2hiint(tot[v])}, srsrc,
+                                                              sp_voff + (uint32_t)(v * 8), 0, 0);
                 }
-                sp_voff += (uint32_t)(NL * KIN_WAVES * 8) * (uint32_t)NV;
             };
-            // FUSE: the four waves of a SIMD (W, W + 4, W + 8, W + 12) do their per-locus sums in different k-steps: 1, 2, 4, 5 of the 8.
-            // None in the barrier's (the last) or the one in front of it, and none in the first, where every wave's first reads of
-            // the new stage are in the LDS queue (measured, fused kernel at 200 pools x 10 M loci, one box, three runs each:
-            // steps 1, 2, 4, 5: 6.70-6.71 ms; 0, 2, 4, 5: 6.73-6.75; 0, 2, 4, 6: 6.74-6.79; the 16-locus loop: 6.96-6.98)
-            constexpr int spec_step = (W / 4) == 0 ? 1 : (W / 4) == 1 ? 2 : (W / 4) == 2 ? 4 : 5, spec_step_half = (W / 4) % KSH;
+            auto spec13 = [&]() __attribute__((always_inline)) {
+                if (P.k > 1) spec_rows(std::integral_constant<int, 2>{}); // wave-uniform
+                else spec_rows(std::integral_constant<int, 1>{});
+            };
+            // FUSE: the 8 tasks of a stage go to the waves 0 .. 7 when the stage computes from buffer 0 and to the waves 8 .. 15 when it
+            // computes from buffer 1 (the parity is compile-time, and a SIMD holds the waves W, W + 4, W + 8, W + 12): two tasks per
+            // SIMD and stage, one task per wave and 64 loci.  The two waves of a SIMD that have a task do it in different k-steps
+            // of the 8; none in the barrier's (the last), and none in the first, where every wave's first reads of the new stage
+            // are in the LDS queue.  A half stage has 4 tasks: one wave per SIMD (0 .. 3), in its second k-step.
+            // (measured, fused kernel at 200 pools x 10 M loci, three runs each, interleaved on one box, profiles/kin_rowsums_ab.txt:
+            //  k-steps 1, 4: 6.83-6.88 ms; 1, 5: 6.82-6.90; 1, 3: 6.90-6.97; 1, 2: 6.98-7.04; the parent's chain: 7.06-7.09;
+            //  and on another box 1, 4: 6.68-6.70; 2, 5: 6.77-6.80; the parent: 6.83-6.87)
+            constexpr int spec_step = ((W / 4) & 1) == 0 ? 1 : 4, spec_step_half = 1;
             // One whole stage, computed from the buffer the read bases point at (buffer B).  Staging of the next stage into the
             // OTHER buffer: its first half is requested at the top and written in the middle, its second half is requested there
             // and written in front of the barrier.  Both writes are safe without a further barrier: the other buffer was last read
@@ -666,7 +647,7 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                 if (more) st_load();
                 static_for<KSW>([&](auto sc) __attribute__((always_inline)) {
                     constexpr int s2 = decltype(sc)::value;
-                    if constexpr (FUSE && s2 == spec_step) spec13(std::integral_constant<int, 2>{});
+                    if constexpr (FUSE && (W < 8) == up && s2 == spec_step) spec13();
                     if constexpr (s2 == KSW / 2 - 1) {
                         if (more) { st_store(std::integral_constant<int, 0>{}); st_load(); }
                     }
@@ -678,7 +659,10 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                         flip(lb, std::bool_constant<up>{});
                         if constexpr ((SMALL & 2) != 0 && has_strip) flip(lbs, std::bool_constant<up>{});
                         if constexpr (ND > 0) { flip(lbr1, std::bool_constant<up>{}); flip(lbr2, std::bool_constant<up>{}); }
-                        if constexpr (FUSE) { flip(srow, std::bool_constant<up>{}); flip(srow3, std::bool_constant<up>{}); }
+                        if constexpr (FUSE) {
+                            flip(srow0, std::bool_constant<up>{}); flip(srow12, std::bool_constant<up>{});
+                            sp_voff += (uint32_t)(KC13 * 8) * (uint32_t)NV;
+                        }
                         static_for<KIN_PPT>([&](auto rc) __attribute__((always_inline)) {
                             if constexpr (st_kind(decltype(rc)::value) != 0) flip(sdst[decltype(rc)::value], std::bool_constant<!up>{});
                         });
@@ -687,11 +671,11 @@ __global__ __launch_bounds__(KIN_THREADS, 1) void k_kinship_syrk(KinParams P) {
                     mfma_set(std::integral_constant<int, s2 & 1>{});
                 });
             };
-            // the half stage a slab may end in: the first KIN_KC rows of the buffer the bases point at, one locus per wave, nothing follows
+            // the half stage a slab may end in: the first KIN_KC rows of the buffer the bases point at, its 4 tasks on the waves 0 .. 3, nothing follows
             auto half_stage = [&]() __attribute__((always_inline)) {
                 static_for<KSH>([&](auto sc) __attribute__((always_inline)) {
                     constexpr int s2 = decltype(sc)::value;
-                    if constexpr (FUSE && s2 == spec_step_half) spec13(std::integral_constant<int, 1>{});
+                    if constexpr (FUSE && W < 4 && s2 == spec_step_half) spec13();
                     if constexpr (s2 + 1 < KSH) load_set(std::integral_constant<int, s2 + 1>{}, std::integral_constant<int, (s2 + 1) & 1>{});
                     mfma_set(std::integral_constant<int, s2 & 1>{});
                 });
@@ -999,11 +983,11 @@ int KIN_LAUNCH_NAME(pg_ctx *ctx, const double *G, int64_t p, int n, int64_t ld, 
     // fused speculative intercept-only sums: only in the single-block path and with phenotypes announced
     const bool spec13 = KIN_HAS13 && P.nb == 1 && P.T == 13;
     // LDS of a launch, in ONE place for the guard and the launch: two stage buffers of the kernel family's stage length (13-tile
-    // kernels: KC13 loci; the rest: KIN_KC), and for the fused sums the phenotypes and the waves' scratch ([4][64] doubles each).
-    // 13-tile, fused: 2 x 32 x 208 x 8 + 4 096 + 32 768 = 143 360 bytes for one trait and for two (the scratch is reused).
+    // kernels: KC13 loci; the rest: KIN_KC), and for the fused sums the phenotypes and, outside the 13-tile kernels (whose sums stay
+    // in DPP rows), the waves' scratch ([4][64] doubles each).  13-tile, fused: 2 x 32 x 208 x 8 + 4 096 = 110 592 bytes.
     auto lds_bytes = [&](bool fused) -> size_t {
         return (size_t)2 * (spec13 ? KC13 : KIN_KC) * ldsld * sizeof(double) +
-               (fused ? ((size_t)KIN_FUSE_MAXK * 256 + (size_t)KIN_WAVES * 4 * 64) * sizeof(double) : 0);
+               (fused ? ((size_t)KIN_FUSE_MAXK * 256 + (spec13 ? 0 : (size_t)KIN_WAVES * 4 * 64)) * sizeof(double) : 0);
     };
     const bool fuse = allow_fuse && ctx->ph_armed && lds_bytes(true) <= 160 * 1024 && P.nb == 1 && ctx->ph_n == n && ctx->ph_k >= 1 && ctx->ph_k <= KIN_FUSE_MAXK &&
                       ctx->ph_ytil_dev != nullptr;

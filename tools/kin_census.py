@@ -14,7 +14,9 @@ that was unrolled over several stages holds one workgroup barrier per stage, so 
     branch  s_cbranch* s_branch                               (waits, barriers and s_nop are listed as "sync")
 
 Registers and spills come from the code object's metadata at the end of the listing (amdhsa.kernels).  No GPU is needed.
-With --json the per-loop rows are printed as one JSON document instead of the table.
+With --json the per-loop rows are printed as one JSON document instead of the table.  With --f64-blocks the f64 VALU count of
+every basic block of a trip is listed per loop: the fused sums' one-trait and two-trait chains are alternatives behind a branch, and
+the table's f64 column adds them up.
 """
 import argparse
 import json
@@ -107,6 +109,24 @@ def census(ins, lo, hi):
     return {k: v / stages for k, v in c.items()}, stages
 
 
+def f64_blocks(ins, labels, lo, hi):
+    """f64 VALU count of every basic block of lines lo..hi that has any, in listing order (a block ends at a label or behind a
+    branch).  Whole trip, not per stage: the fused sums' one-trait and two-trait code are different blocks of one loop."""
+    starts = {i for i in labels.values() if lo < i <= hi}
+    out, n, prev = [], 0, lo
+    for i, op, text in ins:
+        if not lo < i <= hi:
+            continue
+        if any(prev < s <= i for s in starts):
+            out.append(n); n = 0
+        prev = i
+        n += classify(op) == "valu" and (op.endswith("_f64") or "_f64_" in op)
+        if op.startswith(("s_cbranch", "s_branch")):
+            out.append(n); n = 0
+    out.append(n)
+    return [b for b in out if b]
+
+
 def metadata(lines, name):
     """register and spill counts of kernel `name` from the amdhsa.kernels document"""
     out, inside = {}, False
@@ -136,6 +156,7 @@ def main():
     ap.add_argument("listing")
     ap.add_argument("kernel", help="substring of the (mangled) kernel name; every match is reported")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--f64-blocks", action="store_true", help="also list, per loop, the f64 VALU count of each basic block that has any (per trip)")
     a = ap.parse_args()
     lines = open(a.listing).read().split("\n")
     doc = []
@@ -147,6 +168,8 @@ def main():
         for head, back in stage_loops(ins, labels):
             c, stages = census(ins, head, back)
             c["stages_per_iteration"] = stages
+            if a.f64_blocks:
+                c["f64_blocks"] = f64_blocks(ins, labels, head, back)
             rows.append(c)
         doc.append({"kernel": name, "metadata": metadata(lines, name), "loops": rows})
     if not doc:
@@ -164,6 +187,9 @@ def main():
             print(f"  {n:4d}  {r['stages_per_iteration']:5d} " + " ".join(f"{fmt(r[c]):>9}" for c in cols))
         if k["loops"]:
             print("  range       " + " ".join(f"{fmt(min(r[c] for r in k['loops'])) + '-' + fmt(max(r[c] for r in k['loops'])):>9}" for c in cols))
+        if a.f64_blocks:
+            for n, r in enumerate(k["loops"]):
+                print(f"  loop {n:2d}: f64 VALU per basic block of a trip: " + " ".join(str(b) for b in r["f64_blocks"]))
         print("  (per wave and stage; valu excludes mfma; the last five columns are subsets of valu)")
 
 
