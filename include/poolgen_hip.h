@@ -385,6 +385,16 @@ int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p
 int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                int64_t n_windows, double *fst_mean, double *fst_win);
+/* The tables forms: the same arguments and the same bits, but the outputs are DEVICE memory of the same shapes, so a table can
+ * go on to pg_gudmc_dev or to pg_f64_table_dev without touching the host.  The means across windows are summed on the device in
+ * the host forms' order (left to right); pg_fst_tables_dev's batches of windows write straight into fst_win_dev.  Every form
+ * has returned only when its work on the device is done.  (pg_watterson_tables_dev, pg_tajima_d_tables_dev: below.) */
+int pg_pi_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                     const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                     int64_t n_windows, double *pi_win_dev, double *pi_mean_dev);
+int pg_fst_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                      const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                      int64_t n_windows, double *fst_mean_dev, double *fst_win_dev);
 
 /* ---------------------------------------------------------------------------------------
  * watterson_estimator (popgen/watterson_theta.rs:8-188) and tajima_d (popgen/tajima_d.rs:10-96) on
@@ -419,6 +429,16 @@ int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int
                     const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                     const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
                     const double *pool_sizes, double *d_win, double *d_mean, double *theta_win, double *pi_win);
+/* The tables forms of the two (see pg_pi_tables_dev): outputs on the device, the optional ones may be NULL as above. */
+int pg_watterson_tables_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
+                            const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
+                            const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win_dev,
+                            double *theta_mean_dev, int64_t *seg_win_dev);
+int pg_tajima_d_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                           const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                           const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
+                           const double *pool_sizes, double *d_win_dev, double *d_mean_dev, double *theta_win_dev,
+                           double *pi_win_dev);
 
 /* ---------------------------------------------------------------------------------------
  * gudmc (popgen/gudmc.rs:64-462): Tajima's D peaks and troughs against pairwise Fst.  The stage on top of
@@ -461,6 +481,11 @@ int pg_gudmc_dev(pg_ctx *ctx, const double *d_win_dev, const double *fst_win_dev
                  double *width_mean_dev, double *width_sd_dev, int64_t *row_window_dev, double *row_d_dev,
                  double *row_width_dev, double *row_width_from_r_dev, double *row_width_p_dev, double *row_fst_delta_dev,
                  double *row_fst_p_dev);
+/* The tables of the kept windows, as the tables entry points leave them on the device, into the tables of all w windows that
+ * pg_gudmc_dev reads: row keep[q] of table_dev (w x cols) = row q of kept_dev (n_kept x cols), every other row NaN.  keep: host,
+ * increasing, inside [0, w). */
+int pg_window_scatter_dev(pg_ctx *ctx, const double *kept_dev, int64_t n_kept, const int64_t *keep, int64_t w, int64_t cols,
+                          double *table_dev);
 
 /* ---------------------------------------------------------------------------------------
  * sync2csv's writer (FileSyncPhen::write_csv, base/sync.rs:1182-1262): rows [row0, row0 + rows) of the loader's matrix as
@@ -728,6 +753,49 @@ int pg_kinship_rows_dev(pg_ctx *ctx, int64_t p, int k, int64_t row0, int64_t row
 int pg_host_kinship_rows(int64_t p, int k, int64_t row0, int64_t rows, const double *beta, const double *pval,
                          const int32_t *col_chrom, const uint64_t *col_pos, const int32_t *col_allele, const char *chrom_text,
                          const int32_t *chrom_off, int n_chrom, char *text, int64_t cap, int64_t *bytes, int n_threads);
+
+/* ---------------------------------------------------------------------------------------
+ * The popgen writer: the tables of fst, heterozygosity, watterson_estimator and tajima_d and the rows of gudmc, formatted
+ * where the values are.  Conventions of the result writer above, unchanged: *bytes is always set; cap = 0 is the size query;
+ * bytes > cap is PG_ERR_INVALID and writes nothing; nothing at or behind text[bytes] is written; text may have any alignment;
+ * no rows is PG_OK with *bytes = 0; bad arguments fail with PG_ERR_INVALID and *bytes = 0.  Host and device forms give the
+ * same bytes.
+ *
+ * pg_f64_table: rows [row0, row0 + n_rows) of a rows x cols table, cell (r, c) = x[r * row_stride + c * col_stride] (so a
+ * window-major table prints pool by pool with row_stride = 1: no transpose).  Row r is label_r (the bytes
+ * label_text[label_off[r] .. label_off[r + 1]) as given, no separator added; label_off = NULL: no labels), the cells joined by
+ * ',', then '\n'.  A cell is display(x) for n_digits < 0 and roundup_own(x, n_digits) for 0 .. 22; column 0 takes
+ * first_col_digits instead.  The device form works cell by cell (pg_tablefmt.hip), so there is no limit on a row; a label is
+ * at most 2^22 bytes; the total is 64-bit; at most 2^39 - 1 cells per call.  Label offsets that decrease (among the rows
+ * formatted) and a row range outside [0, rows] are PG_ERR_INVALID.
+ * ------------------------------------------------------------------------------------- */
+int pg_f64_table_dev(pg_ctx *ctx, const double *x_dev, int64_t rows, int64_t cols, int64_t row_stride, int64_t col_stride,
+                     int64_t row0, int64_t n_rows, int n_digits, int first_col_digits, const char *label_text_dev,
+                     const int64_t *label_off_dev, char *text_dev, int64_t cap, int64_t *bytes);
+int pg_host_f64_table(const double *x, int64_t rows, int64_t cols, int64_t row_stride, int64_t col_stride, int64_t row0,
+                      int64_t n_rows, int n_digits, int first_col_digits, const char *label_text, const int64_t *label_off,
+                      char *text, int64_t cap, int64_t *bytes, int n_threads);
+/* Rows [row0, row0 + rows) of gudmc's file (gudmc.rs:433-455) from pg_gudmc_dev's outputs as it leaves them (row_* with pitch
+ * w) and the windows' chromosome id, first and last position (here on the device).  The file runs pair by pair, pair
+ * i = a * n + b carrying the rows_dev[b] rows of population b; only rows_dev[n] is read back, for that prefix sum.  A row is
+ *   pop_a,pop_b,chr,pos_ini,pos_fin,R(d_mean[b],7),R(fst_mean[i],7),R(d_sd[b],7),R(fst_sd[i],7),D(d),D(width),D(width_from_r),
+ *   R(width_p,7),R(fst_delta,7),R(fst_p,7)
+ * with the pool names and the chromosome names each as one byte string with int32 offsets (n + 1 and n_chrom + 1).  One lane
+ * per row, at most 2^31 rows per call, a row at most 2^22 bytes.  A row range outside the file's rows, a population with more
+ * than w rows, a row's window outside [0, w) and a window's chromosome id outside [0, n_chrom) are PG_ERR_INVALID. */
+int pg_gudmc_rows_dev(pg_ctx *ctx, int n, int64_t w, int64_t row0, int64_t rows, const int64_t *rows_dev, const double *d_mean_dev,
+                      const double *d_sd_dev, const double *fst_mean_dev, const double *fst_sd_dev, const int64_t *row_window_dev,
+                      const double *row_d_dev, const double *row_width_dev, const double *row_width_from_r_dev,
+                      const double *row_width_p_dev, const double *row_fst_delta_dev, const double *row_fst_p_dev,
+                      const int32_t *win_chr_dev, const uint64_t *win_ini_dev, const uint64_t *win_fin_dev, const char *pool_text_dev,
+                      const int32_t *pool_off_dev, const char *chrom_text_dev, const int32_t *chrom_off_dev, int n_chrom,
+                      char *text_dev, int64_t cap, int64_t *bytes);
+int pg_host_gudmc_rows(int n, int64_t w, int64_t row0, int64_t rows, const int64_t *pop_rows, const double *d_mean, const double *d_sd,
+                       const double *fst_mean, const double *fst_sd, const int64_t *row_window, const double *row_d,
+                       const double *row_width, const double *row_width_from_r, const double *row_width_p, const double *row_fst_delta,
+                       const double *row_fst_p, const int32_t *win_chr, const uint64_t *win_ini, const uint64_t *win_fin,
+                       const char *pool_text, const int32_t *pool_off, const char *chrom_text, const int32_t *chrom_off, int n_chrom,
+                       char *text, int64_t cap, int64_t *bytes, int n_threads);
 
 /* ---------------------------------------------------------------------------------------
  * impute (src/imputation/: filtering_missing.rs, mean_imputation.rs, adaptive_ld_knn_imputation.rs; CLI main.rs:125-142,

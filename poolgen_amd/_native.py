@@ -132,6 +132,15 @@ SIGNATURES = {
     "pg_host_result_rows": (_i, [_i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64, _i]),
     "pg_kinship_rows_dev": (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64]),
     "pg_host_kinship_rows": (_i, [_i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _pi64, _i]),
+    "pg_f64_table_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _i64, _pi64]),
+    "pg_host_f64_table": (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _i64, _pi64, _i]),
+    "pg_gudmc_rows_dev": (_i, [_vp, _i, _i64, _i64, _i64] + [_vp] * 19 + [_i, _vp, _i64, _pi64]),
+    "pg_host_gudmc_rows": (_i, [_i, _i64, _i64, _i64] + [_vp] * 19 + [_i, _vp, _i64, _pi64, _i]),
+    "pg_pi_tables_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "pg_fst_tables_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "pg_watterson_tables_dev": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pg_tajima_d_tables_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pg_window_scatter_dev": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "pg_sync_parse_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "pg_host_sync_parse": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i]),
     "pg_set_missing_by_depth_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _i64, _d]),

@@ -92,6 +92,12 @@ static const char *USAGE =
     "      --result-slab-rows <N>          --result-writer gpu, kinship analyses: rows formatted, copied and written per turn; default: as\n"
     "                                      many as hold 256 MB of text at 128 bytes a row.  The file does not depend on it (the per-locus\n"
     "                                      analyses format the rows of one piece of the input per turn: --stream-chunk-mb)\n"
+    "      --popgen-writer <host|gpu>      fst, heterozygosity, watterson_estimator, tajima_d, gudmc: who formats the tables and gudmc's rows:\n"
+    "                                      the host (the default), or the GPU that computed them (the tables then never leave the device --\n"
+    "                                      gudmc's D and Fst go straight into its fits -- and only the text comes back).  Numbers print as with\n"
+    "                                      --result-writer gpu; the file is the host writer's byte for byte below 2^53\n"
+    "      --popgen-slab-rows <N>          --popgen-writer gpu: rows formatted, copied and written per turn; default: as many as hold 256 MB of\n"
+    "                                      text.  The file does not depend on it\n"
     "      --stream-chunk-mb <N>           size of the pieces the input is taken in (0: whole file, kinship path only)\n"
     "      --n-gpus <N>  [--gpu-ids a,b,..]  fisher_exact_test, chisq_test, pearson_corr, ols_iter, gwalpha, ols_iter_with_kinship: one contiguous\n"
     "                                      part of the input per GPU (own parser threads: --n-threads is the total); the kinship sums are\n"
@@ -153,6 +159,8 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--sync-writer") a.sync_writer = val();
         else if (k == "--result-writer") a.result_writer = val();
         else if (k == "--result-slab-rows") a.result_slab_rows = flag_int(val(), k, 1);
+        else if (k == "--popgen-writer") a.popgen_writer = val();
+        else if (k == "--popgen-slab-rows") a.popgen_slab_rows = flag_int(val(), k, 1);
         else if (k == "--min-depth-set-to-missing") {
             const std::string t = val();
             if (!parse_f64_strict(t, a.min_depth_set_to_missing)) throw std::runtime_error("`" + t + "` isn't a valid number (" + k + ")");
@@ -240,6 +248,16 @@ Analysis checked_analysis(const Args &a, bool &gwalpha_fmt) {
     if (a.result_writer == "gpu" && kinship_rows && a.n_gpus > 1)
         throw std::runtime_error("--result-writer gpu on `" + a.analysis + "` takes one GPU: with --n-gpus " + std::to_string(a.n_gpus) +
                                  " the rows of one trait would interleave the ranks' coefficients; run it without --n-gpus, or with --result-writer host");
+    const bool popgen_tables = analysis == Analysis::fst || analysis == Analysis::heterozygosity || analysis == Analysis::watterson_estimator ||
+                               analysis == Analysis::tajima_d || analysis == Analysis::gudmc;
+    if (a.popgen_writer != "host" && a.popgen_writer != "gpu")
+        throw std::runtime_error("Invalid value `" + a.popgen_writer + "` for --popgen-writer (fst, heterozygosity, watterson_estimator, tajima_d and gudmc "
+                                 "take it). Please select: 'host' or 'gpu'");
+    if ((a.popgen_writer == "gpu" || a.popgen_slab_rows > 0) && !popgen_tables)
+        throw std::runtime_error("--popgen-writer gpu applies to fst, heterozygosity, watterson_estimator, tajima_d and gudmc, which write popgen tables; `" +
+                                 a.analysis + "` writes none");
+    if (a.popgen_slab_rows > 0 && a.popgen_writer != "gpu")
+        throw std::runtime_error("--popgen-slab-rows needs --popgen-writer gpu: the host writer has no slabs");
     gwalpha_fmt = a.phen_format == "gwalpha_fmt";
     if (analysis == Analysis::gwalpha && !gwalpha_fmt)
         throw std::runtime_error("gwalpha needs the GWAlpha.py phenotype file: give it with --phen-format gwalpha_fmt "

@@ -31,6 +31,8 @@ struct Args {
     std::string pileup_parser = "host"; // who parses a *.pileup / *.mpileup input: the host's threads, or the GPU (the counts come back)
     std::string result_writer = "host"; // who formats the result rows of the GWAS analyses: the host's threads, or the GPU that computed them
     int64_t result_slab_rows = 0;       // --result-writer gpu, kinship analyses: rows formatted, copied and written per turn (0 = a byte budget's worth)
+    std::string popgen_writer = "host"; // who formats the tables of fst and the diversity analyses and gudmc's rows: the host, or the GPU that computed them
+    int64_t popgen_slab_rows = 0;       // --popgen-writer gpu: rows formatted, copied and written per turn (0 = a byte budget's worth)
     std::string sync_writer = "host"; // who formats the sync lines pileup2sync / vcf2sync write: the host's threads, or the GPU that parsed the input
     std::string sync_parser = "host"; // who parses a *.sync input: the host's threads, or the GPU (the counts then stay on the device)
     std::string imputation_method = "aLD-kNNi";

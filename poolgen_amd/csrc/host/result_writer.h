@@ -1,5 +1,5 @@
 // result_writer.h -- --result-writer gpu: the result rows of the GWAS analyses formatted by the GPU that computed them
-// (pg_result_rows_dev, pg_kinship_rows_dev).  The statistics stay where the operator left them; only their text comes back, into
+// (pg_result_rows_dev, pg_kinship_rows_dev); --popgen-writer gpu takes the same format-and-write loop (text()).  The statistics stay where the operator left them; only their text comes back, into
 // pinned memory, and is appended to the file the caller has opened (and removes when anything on the way throws).
 #pragma once
 #include "../../../include/poolgen_hip.h"
@@ -22,13 +22,14 @@ inline int64_t result_slab_rows(int flag) { return flag > 0 ? flag : RESULT_SLAB
 
 class DeviceResultWriter {
 public:
-    DeviceResultWriter() = default;
+    // who: the flag's word, "result" (--result-writer) or "popgen" (--popgen-writer): in the messages and in the timing line
+    explicit DeviceResultWriter(const char *who = "result") : who_(who) {}
     DeviceResultWriter(const DeviceResultWriter &) = delete;
     DeviceResultWriter &operator=(const DeviceResultWriter &) = delete;
     ~DeviceResultWriter() {
         if (std::getenv("PGH_TIMING") && text_bytes_ > 0)
-            std::fprintf(stderr, "poolgen: result writer on the GPU, %.1f MB of text: labels up %.3f s, format calls %.3f s, D2H of the text %.3f s, file writes %.3f s\n",
-                         text_bytes_ / 1e6, t_labels_, t_format_, t_d2h_, t_write_);
+            std::fprintf(stderr, "poolgen: %s writer on the GPU, %.1f MB of text: labels up %.3f s, format calls %.3f s, D2H of the text %.3f s, file writes %.3f s\n",
+                         who_, text_bytes_ / 1e6, t_labels_, t_format_, t_d2h_, t_write_);
     }
     // The labels of a piece, up once: chromosome id and position per locus, the name table (SyncBatch's).
     void set_locus_labels(const std::vector<int32_t> &chrom_id, const std::vector<uint64_t> &pos, const std::vector<std::string> &names, int64_t L) {
@@ -69,6 +70,10 @@ public:
                                        off_dev_.get(), n_chrom_, text, cap, need);
         });
     }
+    // Any other formatter of the library's conventions: call(text_dev, cap, &need) formats into the writer's buffer (or asks for
+    // a larger one); its text is appended to fo.
+    template <class Call>
+    void text(pg_ctx *ctx, FILE *fo, Call call) { format_and_write(ctx, fo, call); }
 
 private:
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -89,11 +94,11 @@ private:
         for (int attempt = 0;; ++attempt) { // the buffer of the turn before serves this one; when it does not, the size is known
             const int rc = call(text_dev_.get(), cap_, &need);
             if (rc == PG_OK) break;
-            if (attempt > 0 || need <= cap_) throw std::runtime_error(std::string("--result-writer gpu: ") + pg_last_error(ctx));
+            if (attempt > 0 || need <= cap_) throw std::runtime_error("--" + std::string(who_) + "-writer gpu: " + pg_last_error(ctx));
             cap_ = need + need / 8;
             text_dev_.reset((size_t)cap_, "the text of the result rows");
         }
-        if (pg_synchronize(ctx) != PG_OK) throw std::runtime_error(std::string("--result-writer gpu: ") + pg_last_error(ctx));
+        if (pg_synchronize(ctx) != PG_OK) throw std::runtime_error("--" + std::string(who_) + "-writer gpu: " + pg_last_error(ctx));
         t_format_ += now() - t0; t0 = now();
         if (need == 0) return;
         char *pin = static_cast<char *>(pin_.reserve((size_t)need));
@@ -110,6 +115,7 @@ private:
     PinnedBuf pin_;
     int64_t cap_ = 0;
     int n_chrom_ = 0;
+    const char *who_;
     double t_labels_ = 0, t_format_ = 0, t_d2h_ = 0, t_write_ = 0, text_bytes_ = 0;
 };
 

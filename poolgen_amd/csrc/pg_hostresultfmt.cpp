@@ -86,6 +86,32 @@ extern "C" int pg_host_result_rows(int op, int64_t L, int k, const int32_t *n_ou
     return rf_host_run(U, 0, L, text, cap, bytes, n_threads);
 }
 
+extern "C" int pg_host_gudmc_rows(int n, int64_t w, int64_t row0, int64_t rows, const int64_t *pop_rows, const double *d_mean, const double *d_sd,
+                                  const double *fst_mean, const double *fst_sd, const int64_t *row_window, const double *row_d,
+                                  const double *row_width, const double *row_width_from_r, const double *row_width_p,
+                                  const double *row_fst_delta, const double *row_fst_p, const int32_t *win_chr, const uint64_t *win_ini,
+                                  const uint64_t *win_fin, const char *pool_text, const int32_t *pool_off, const char *chrom_text,
+                                  const int32_t *chrom_off, int n_chrom, char *text, int64_t cap, int64_t *bytes, int n_threads) {
+    if (!bytes) return PG_ERR_INVALID;
+    *bytes = 0;
+    if (n < 1 || w < 1 || row0 < 0 || !rf_host_shape_ok(rows, text, cap) || n_chrom < 0 || !pop_rows) return PG_ERR_INVALID;
+    std::vector<int64_t> first((size_t)n + 1, 0);
+    for (int b = 0; b < n; ++b) {
+        if (pop_rows[b] < 0 || pop_rows[b] > w) return PG_ERR_INVALID;
+        first[b + 1] = first[b] + pop_rows[b];
+    }
+    if (first[n] > INT64_MAX / n || row0 > first[n] * n - rows) return PG_ERR_INVALID;
+    if (rows == 0) return PG_OK;
+    if (!d_mean || !d_sd || !fst_mean || !fst_sd || !row_window || !row_d || !row_width || !row_width_from_r || !row_width_p || !row_fst_delta ||
+        !row_fst_p || !win_chr || !win_ini || !win_fin || !pool_off || !chrom_off || (!chrom_text && n_chrom > 0))
+        return PG_ERR_INVALID;
+    const PgGudmcUnits U{n, w, first.data(), d_mean, d_sd, fst_mean, fst_sd, row_window, row_d, row_width, row_width_from_r, row_width_p,
+                         row_fst_delta, row_fst_p, win_chr, win_ini, win_fin,
+                         PgNames{reinterpret_cast<const unsigned char *>(pool_text), pool_off, n},
+                         PgNames{reinterpret_cast<const unsigned char *>(chrom_text), chrom_off, n_chrom}};
+    return rf_host_run(U, row0, rows, text, cap, bytes, n_threads);
+}
+
 extern "C" int pg_host_kinship_rows(int64_t p, int k, int64_t row0, int64_t rows, const double *beta, const double *pval,
                                     const int32_t *col_chrom, const uint64_t *col_pos, const int32_t *col_allele, const char *chrom_text,
                                     const int32_t *chrom_off, int n_chrom, char *text, int64_t cap, int64_t *bytes, int n_threads) {

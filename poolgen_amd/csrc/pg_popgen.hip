@@ -247,6 +247,15 @@ __global__ __launch_bounds__(256) void k_chunk_reduce(const double *__restrict__
     out[i] = s / denom;
 }
 
+// mean_axis(Axis(0)) of a windows x n table, left to right as the host loops of the host-output entry points add: a lane a pool
+__global__ __launch_bounds__(256) void k_window_mean(const double *__restrict__ vals, int64_t nw, int n, double *__restrict__ mean) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    double s = 0.0;
+    for (int64_t w = 0; w < nw; ++w) s = s + vals[(size_t)w * n + j];
+    mean[j] = s / (double)nw;
+}
+
 int check_shape(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                 const int64_t *locus_col, int64_t L, const int64_t *wh, const int64_t *wt, int64_t nw, const char *who) {
     PG_CHECK(ctx, G_dev && cov_dev && locus_col && p > 0 && n >= 1 && ld >= n && L >= 1, "%s: bad arguments", who);
@@ -289,7 +298,8 @@ void diversity_constants(const double *pool_sizes, int n, std::vector<double> &k
 constexpr double POOL_SIZE_MAX = 1e9; // the harmonic sums are loops over 1 .. pool size
 
 // watterson_estimator (tajima == false: no coverages, no pi) and tajima_d on one locus pass and one window pass
-int diversity_run(pg_ctx *ctx, bool tajima, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+// dev_out: the outputs are device memory (the tables entry points); the kernels write into them and the means are k_window_mean's
+int diversity_run(pg_ctx *ctx, bool dev_out, bool tajima, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                   const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov,
                   const int64_t *win_seed, const int64_t *win_slot, int64_t nw, const double *pool_sizes, double *d_win,
                   double *d_mean, double *theta_win, double *theta_mean, double *pi_win, int64_t *seg_win) {
@@ -320,7 +330,7 @@ int diversity_run(pg_ctx *ctx, bool tajima, const double *G_dev, const double *c
     if ((rc = win.alloc(ctx, sizeof(int64_t) * nwin * nw, who))) return rc;
     if ((rc = kcd.alloc(ctx, sizeof(double) * 3 * n, who))) return rc;
     if ((rc = out.alloc(ctx, sizeof(double) * nout * wn, who))) return rc;
-    if (seg_win && (rc = seg.alloc(ctx, sizeof(int64_t) * wn, who))) return rc;
+    if (seg_win && !dev_out && (rc = seg.alloc(ctx, sizeof(int64_t) * wn, who))) return rc;
     const int64_t *host_win[5] = {win_head, win_tail, win_cov, win_seed, win_slot};
     PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
     for (int i = 0; i < nwin; ++i)
@@ -330,17 +340,31 @@ int diversity_run(pg_ctx *ctx, bool tajima, const double *G_dev, const double *c
     const int64_t *wc = reference ? wt + nw : nullptr, *wsd = reference ? wc + nw : nullptr, *wsl = reference ? wsd + nw : nullptr;
     const dim3 lgrid((unsigned)((ln + 255) / 256)), wgrid((unsigned)((wn + 255) / 256));
     double *theta_dev = out.get(), *pi_dev = tajima ? theta_dev + wn : nullptr, *d_dev = tajima ? pi_dev + wn : nullptr;
+    int64_t *seg_dev = seg.get();
+    if (dev_out) { // straight into the caller's tables, where there are any
+        if (theta_win) theta_dev = theta_win;
+        if (tajima && pi_win) pi_dev = pi_win;
+        if (tajima) d_dev = d_win;
+        seg_dev = seg_win;
+    }
     if (tajima) {
         hipLaunchKernelGGL((k_pop_locus<false, true>), lgrid, dim3(256), 0, ctx->stream, G_dev, cov_dev, lc.get(), L, n, ld,
                            (double *)nullptr, pi.get(), flag.get());
         hipLaunchKernelGGL(k_diversity_windows<true>, wgrid, dim3(256), 0, ctx->stream, pi.get(), flag.get(), wh, wt, wc, wsd, wsl,
-                           nw, n, kcd.get(), seg.get(), theta_dev, pi_dev, d_dev);
+                           nw, n, kcd.get(), seg_dev, theta_dev, pi_dev, d_dev);
     } else {
         hipLaunchKernelGGL(k_poly_locus, lgrid, dim3(256), 0, ctx->stream, G_dev, lc.get(), L, n, ld, flag.get());
         hipLaunchKernelGGL(k_diversity_windows<false>, wgrid, dim3(256), 0, ctx->stream, (const double *)nullptr, flag.get(), wh, wt,
-                           wc, wsd, wsl, nw, n, kcd.get(), seg.get(), theta_dev, pi_dev, d_dev);
+                           wc, wsd, wsl, nw, n, kcd.get(), seg_dev, theta_dev, pi_dev, d_dev);
     }
     PG_HIP(ctx, hipGetLastError());
+    if (dev_out) {
+        hipLaunchKernelGGL(k_window_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tajima ? d_dev : theta_dev, nw, n,
+                           tajima ? d_mean : theta_mean);
+        PG_HIP(ctx, hipGetLastError());
+        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this call
+        return PG_OK;
+    }
     if (theta_win) PG_HIP(ctx, hipMemcpyAsync(theta_win, theta_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
     if (tajima && pi_win) PG_HIP(ctx, hipMemcpyAsync(pi_win, pi_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
     if (tajima) PG_HIP(ctx, hipMemcpyAsync(d_win, d_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
@@ -358,9 +382,10 @@ int diversity_run(pg_ctx *ctx, bool tajima, const double *G_dev, const double *c
 
 } // namespace
 
-extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                         const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
-                         int64_t n_windows, double *pi_win, double *pi_mean) {
+// pg_pi_dev (dev_out = false: host outputs) and pg_pi_tables_dev (device outputs)
+static int pi_run(pg_ctx *ctx, bool dev_out, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                  const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                  int64_t n_windows, double *pi_win, double *pi_mean) {
     if (!ctx) return PG_ERR_INVALID;
     int rc = check_shape(ctx, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, "pi");
     if (rc) return rc;
@@ -373,15 +398,22 @@ extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev
     if ((rc = pi.alloc(ctx, sizeof(double) * (size_t)L * n, "pi"))) return rc;
     if ((rc = wh.alloc(ctx, sizeof(int64_t) * n_windows, "pi"))) return rc;
     if ((rc = wt.alloc(ctx, sizeof(int64_t) * n_windows, "pi"))) return rc;
-    if ((rc = out.alloc(ctx, sizeof(double) * (size_t)n_windows * n, "pi"))) return rc;
+    if (!dev_out && (rc = out.alloc(ctx, sizeof(double) * (size_t)n_windows * n, "pi"))) return rc;
+    double *win_dev = dev_out ? pi_win : out.get();
     PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(ctx, hipMemcpyAsync(wh.get(), win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(ctx, hipMemcpyAsync(wt.get(), win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL((k_pop_locus<true, false>), dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev,
                        cov_dev, lc.get(), L, n, ld, q1.get(), pi.get(), (uint8_t *)nullptr);
     hipLaunchKernelGGL(k_range_mean_1d, dim3((unsigned)(((size_t)n_windows * n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       pi.get(), wh.get(), wt.get(), n_windows, n, out.get());
+                       pi.get(), wh.get(), wt.get(), n_windows, n, win_dev);
     PG_HIP(ctx, hipGetLastError());
+    if (dev_out) {
+        hipLaunchKernelGGL(k_window_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, win_dev, n_windows, n, pi_mean);
+        PG_HIP(ctx, hipGetLastError());
+        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this call
+        return PG_OK;
+    }
     PG_HIP(ctx, hipMemcpyAsync(pi_win, out.get(), sizeof(double) * (size_t)n_windows * n, hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int j = 0; j < n; ++j) { // mean_axis(Axis(0)) over the windows (pi.rs:133): left to right
@@ -392,9 +424,23 @@ extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev
     return PG_OK;
 }
 
-extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                          const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
-                          int64_t n_windows, double *fst_mean, double *fst_win) {
+extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                         const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                         int64_t n_windows, double *pi_win, double *pi_mean) {
+    return pi_run(ctx, false, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, pi_win, pi_mean);
+}
+
+extern "C" int pg_pi_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                                const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                                int64_t n_windows, double *pi_win_dev, double *pi_mean_dev) {
+    return pi_run(ctx, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, pi_win_dev, pi_mean_dev);
+}
+
+// pg_fst_dev (dev_out = false: host outputs) and pg_fst_tables_dev (device outputs: the batches of windows write straight into
+// the caller's table)
+static int fst_run(pg_ctx *ctx, bool dev_out, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                   const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                   int64_t n_windows, double *fst_mean, double *fst_win) {
     if (!ctx) return PG_ERR_INVALID;
     int rc = check_shape(ctx, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, "fst");
     if (rc) return rc;
@@ -415,7 +461,7 @@ extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_de
     if ((rc = chh.alloc(ctx, sizeof(int64_t) * nchunks, "fst"))) return rc;
     if ((rc = cht.alloc(ctx, sizeof(int64_t) * nchunks, "fst"))) return rc;
     if ((rc = part.alloc(ctx, sizeof(double) * nchunks * nn, "fst"))) return rc;
-    if ((rc = mean.alloc(ctx, sizeof(double) * nn, "fst"))) return rc;
+    if (!dev_out && (rc = mean.alloc(ctx, sizeof(double) * nn, "fst"))) return rc;
     if ((rc = bad.alloc(ctx, sizeof(int), "fst"))) return rc;
     PG_HIP(ctx, hipMemsetAsync(bad.get(), 0, sizeof(int), ctx->stream));
     PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
@@ -435,9 +481,9 @@ extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_de
     hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nchunks, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.get(),
                        lc.get(), chh.get(), cht.get(), n, ld, ntile, 0, part.get());
     hipLaunchKernelGGL(k_chunk_reduce, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, ctx->stream, part.get(), nchunks,
-                       (int64_t)nn, (double)L, mean.get());
+                       (int64_t)nn, (double)L, dev_out ? fst_mean : mean.get());
     PG_HIP(ctx, hipGetLastError());
-    PG_HIP(ctx, hipMemcpyAsync(fst_mean, mean.get(), sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev_out) PG_HIP(ctx, hipMemcpyAsync(fst_mean, mean.get(), sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
     if (n_windows > 0) {
         if ((rc = wh.alloc(ctx, sizeof(int64_t) * n_windows, "fst"))) return rc;
         if ((rc = wt.alloc(ctx, sizeof(int64_t) * n_windows, "fst"))) return rc;
@@ -445,12 +491,13 @@ extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_de
         PG_HIP(ctx, hipMemcpyAsync(wt.get(), win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
         // the per-window table in slabs of windows (it is n^2 doubles per window)
         const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(n_windows, (int64_t)(((size_t)1 << 30) / (nn * sizeof(double)))));
-        if ((rc = out.alloc(ctx, sizeof(double) * slab * nn, "fst"))) return rc;
+        if (!dev_out && (rc = out.alloc(ctx, sizeof(double) * slab * nn, "fst"))) return rc;
         for (int64_t w0 = 0; w0 < n_windows; w0 += slab) {
             const int64_t nwb = std::min<int64_t>(slab, n_windows - w0);
             hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nwb, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.get(),
-                               lc.get(), wh.get() + w0, wt.get() + w0, n, ld, ntile, 1, out.get());
+                               lc.get(), wh.get() + w0, wt.get() + w0, n, ld, ntile, 1, dev_out ? fst_win + (size_t)w0 * nn : out.get());
             PG_HIP(ctx, hipGetLastError());
+            if (dev_out) continue;
             PG_HIP(ctx, hipMemcpyAsync(fst_win + (size_t)w0 * nn, out.get(), sizeof(double) * nwb * nn, hipMemcpyDeviceToHost, ctx->stream));
             PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
@@ -459,13 +506,64 @@ extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_de
     return PG_OK;
 }
 
+extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                          const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                          int64_t n_windows, double *fst_mean, double *fst_win) {
+    return fst_run(ctx, false, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, fst_mean, fst_win);
+}
+
+extern "C" int pg_fst_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                                 const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                                 int64_t n_windows, double *fst_mean_dev, double *fst_win_dev) {
+    return fst_run(ctx, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, fst_mean_dev, fst_win_dev);
+}
+
+// row w of the table = row slot[w] of the kept rows, NaN where slot[w] < 0
+__global__ __launch_bounds__(256) void k_window_scatter(const double *__restrict__ kept, const int64_t *__restrict__ slot, int64_t w, int64_t cols,
+                                                        double *__restrict__ table) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= w * cols) return;
+    const int64_t r = i / cols, q = slot[r];
+    table[i] = q >= 0 ? kept[q * cols + (i - r * cols)] : __builtin_nan("");
+}
+
+extern "C" int pg_window_scatter_dev(pg_ctx *ctx, const double *kept_dev, int64_t n_kept, const int64_t *keep, int64_t w, int64_t cols,
+                                     double *table_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    PG_CHECK(ctx, n_kept >= 0 && w >= 1 && cols >= 1 && n_kept <= w && table_dev && (n_kept == 0 || (kept_dev && keep)) && w <= (((int64_t)1 << 39) - 1) / cols,
+             "window_scatter: bad arguments");
+    std::vector<int64_t> slot((size_t)w, -1);
+    for (int64_t q = 0; q < n_kept; ++q) {
+        PG_CHECK(ctx, keep[q] >= 0 && keep[q] < w && (q == 0 || keep[q] > keep[q - 1]), "window_scatter: kept window %lld out of order or range", (long long)q);
+        slot[(size_t)keep[q]] = q;
+    }
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    DevBuf<int64_t> slot_dev;
+    int rc = slot_dev.alloc(ctx, sizeof(int64_t) * (size_t)w, "window_scatter");
+    if (rc) return rc;
+    PG_HIP(ctx, hipMemcpyAsync(slot_dev.get(), slot.data(), sizeof(int64_t) * (size_t)w, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_window_scatter, dim3((unsigned)((w * cols + 255) / 256)), dim3(256), 0, ctx->stream, kept_dev, slot_dev.get(), w, cols, table_dev);
+    PG_HIP(ctx, hipGetLastError());
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this call
+    return PG_OK;
+}
+
 extern "C" int pg_watterson_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
                                 const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
                                 const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win,
                                 double *theta_mean, int64_t *seg_win) {
     if (!ctx) return PG_ERR_INVALID;
-    return diversity_run(ctx, false, G_dev, nullptr, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
+    return diversity_run(ctx, false, false, G_dev, nullptr, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
                          pool_sizes, nullptr, nullptr, theta_win, theta_mean, nullptr, seg_win);
+}
+
+extern "C" int pg_watterson_tables_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
+                                       const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
+                                       const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win_dev,
+                                       double *theta_mean_dev, int64_t *seg_win_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    return diversity_run(ctx, true, false, G_dev, nullptr, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
+                         pool_sizes, nullptr, nullptr, theta_win_dev, theta_mean_dev, nullptr, seg_win_dev);
 }
 
 extern "C" int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
@@ -473,6 +571,16 @@ extern "C" int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *c
                                const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
                                const double *pool_sizes, double *d_win, double *d_mean, double *theta_win, double *pi_win) {
     if (!ctx) return PG_ERR_INVALID;
-    return diversity_run(ctx, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
+    return diversity_run(ctx, false, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
                          pool_sizes, d_win, d_mean, theta_win, nullptr, pi_win, nullptr);
+}
+
+extern "C" int pg_tajima_d_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                                      const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                                      const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
+                                      const double *pool_sizes, double *d_win_dev, double *d_mean_dev, double *theta_win_dev,
+                                      double *pi_win_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    return diversity_run(ctx, true, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
+                         pool_sizes, d_win_dev, d_mean_dev, theta_win_dev, nullptr, pi_win_dev, nullptr);
 }

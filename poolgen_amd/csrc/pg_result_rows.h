@@ -5,6 +5,7 @@
 //   PgF64Units      one value and its '\n'                                    (pg_f64_text_dev / pg_host_f64_text)
 //   PgResultUnits   one locus with all its rows: slots, then traits           (pg_result_rows_dev / pg_host_result_rows)
 //   PgKinshipUnits  one row  label_i,Pheno_j,D(beta),D(pval)                  (pg_kinship_rows_dev / pg_host_kinship_rows)
+//   PgGudmcUnits    one row of gudmc's file, 15 fields                        (pg_gudmc_rows_dev / pg_host_gudmc_rows)
 // Every kind has  bool ok(u)  (may the unit's labels be read and printed?) and  template <class Sink> void write(u, sink).
 // A unit is written into a SINK: PgLenSink only adds the lengths up (the measure half), PgPutSink stores the bytes (the emit
 // half).  The number cells are pg_f64_text.h's: D(x) = display, R(x, nd) = roundup_own.
@@ -147,6 +148,63 @@ struct PgResultUnits {
                 s.ch('\n');
             }
         }
+    }
+};
+
+// gudmc's rows from pg_gudmc_dev's outputs as they lie (pitch w).  The rows of the file run pair by pair, pair i = a * n + b
+// with the rows of population b, so global row r lies where the prefix sums of rows[i % n] place it: first[b] = the rows of the
+// populations in front of b, first[n] = R those of all, and r = a * R + first[b] + j is row j of pair (a, b).
+struct PgGudmcUnits {
+    int n;
+    int64_t w;
+    const int64_t *first; // n + 1
+    const double *d_mean, *d_sd, *f_mean, *f_sd;
+    const int64_t *r_win;
+    const double *r_d, *r_width, *r_wdev, *r_wp, *r_delta, *r_fp;
+    const int32_t *win_chr;
+    const uint64_t *win_ini, *win_fin;
+    PgNames pools, chroms;
+
+    PG_F64_HD void place(int64_t r, int *a, int *b, int64_t *e) const {
+        const int64_t R = first[n], qa = r / R, rem = r - qa * R;
+        int lo = 0, hi = n - 1; // the last population with first[b] <= rem: one without rows is passed over
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (first[mid] <= rem) lo = mid;
+            else hi = mid - 1;
+        }
+        *a = (int)qa;
+        *b = lo;
+        *e = (qa * n + lo) * w + (rem - first[lo]);
+    }
+    PG_F64_HD bool ok(int64_t r) const {
+        int a, b;
+        int64_t e;
+        place(r, &a, &b, &e);
+        const int64_t win = r_win[e];
+        return pools.ok(a) && pools.ok(b) && win >= 0 && win < w && chroms.ok(win_chr[win]);
+    }
+    template <class Sink>
+    PG_F64_HD void write(int64_t r, Sink &s) const {
+        int a, b;
+        int64_t e;
+        place(r, &a, &b, &e);
+        const int64_t i = (int64_t)a * n + b, win = r_win[e];
+        pools.write(a, s); s.ch(',');
+        pools.write(b, s); s.ch(',');
+        chroms.write(win_chr[win], s); s.ch(',');
+        s.u64(win_ini[win]); s.ch(',');
+        s.u64(win_fin[win]); s.ch(',');
+        s.f64(pg_f64_cell(d_mean[b], 7)); s.ch(',');
+        s.f64(pg_f64_cell(f_mean[i], 7)); s.ch(',');
+        s.f64(pg_f64_cell(d_sd[b], 7)); s.ch(',');
+        s.f64(pg_f64_cell(f_sd[i], 7)); s.ch(',');
+        s.f64(pg_f64_parts(r_d[e])); s.ch(',');
+        s.f64(pg_f64_parts(r_width[e])); s.ch(',');
+        s.f64(pg_f64_parts(r_wdev[e])); s.ch(',');
+        s.f64(pg_f64_cell(r_wp[e], 7)); s.ch(',');
+        s.f64(pg_f64_cell(r_delta[e], 7)); s.ch(',');
+        s.f64(pg_f64_cell(r_fp[e], 7)); s.ch('\n');
     }
 };
 

@@ -161,6 +161,51 @@ extern "C" int pg_result_rows_dev(pg_ctx *ctx, int op, int64_t L, int k, const i
     return rf_run(ctx, "result_rows", U, 0, L, text_dev, cap, bytes);
 }
 
+extern "C" int pg_gudmc_rows_dev(pg_ctx *ctx, int n, int64_t w, int64_t row0, int64_t rows, const int64_t *rows_dev, const double *d_mean_dev,
+                                 const double *d_sd_dev, const double *fst_mean_dev, const double *fst_sd_dev, const int64_t *row_window_dev,
+                                 const double *row_d_dev, const double *row_width_dev, const double *row_width_from_r_dev,
+                                 const double *row_width_p_dev, const double *row_fst_delta_dev, const double *row_fst_p_dev,
+                                 const int32_t *win_chr_dev, const uint64_t *win_ini_dev, const uint64_t *win_fin_dev,
+                                 const char *pool_text_dev, const int32_t *pool_off_dev, const char *chrom_text_dev,
+                                 const int32_t *chrom_off_dev, int n_chrom, char *text_dev, int64_t cap, int64_t *bytes) {
+    if (!ctx) return PG_ERR_INVALID;
+    PG_CHECK(ctx, bytes != nullptr, "gudmc_rows: null pointer");
+    *bytes = 0;
+    PG_CHECK(ctx, n >= 1 && w >= 1 && row0 >= 0 && rows >= 0 && rows <= ((int64_t)1 << 31) && cap >= 0 && n_chrom >= 0,
+             "gudmc_rows: bad shape n=%d w=%lld row0=%lld rows=%lld cap=%lld n_chrom=%d", n, (long long)w, (long long)row0, (long long)rows,
+             (long long)cap, n_chrom);
+    PG_CHECK(ctx, cap == 0 || text_dev, "gudmc_rows: null text buffer");
+    PG_CHECK(ctx, rows_dev != nullptr, "gudmc_rows: null pointer");
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<int64_t> first((size_t)n + 1, 0); // the populations' rows come down, for the prefix sum
+    PG_HIP(ctx, hipMemcpyAsync(first.data() + 1, rows_dev, sizeof(int64_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < n; ++b) {
+        PG_CHECK(ctx, first[b + 1] >= 0 && first[b + 1] <= w, "gudmc_rows: population %d has %lld rows of %lld windows", b, (long long)first[b + 1],
+                 (long long)w);
+        first[b + 1] += first[b];
+    }
+    PG_CHECK(ctx, first[n] <= INT64_MAX / n && row0 <= first[n] * n - rows, "gudmc_rows: rows [%lld, %lld) of %lld", (long long)row0,
+             (long long)(row0 + rows), (long long)(first[n] <= INT64_MAX / n ? first[n] * n : -1));
+    if (rows == 0) return PG_OK;
+    PG_CHECK(ctx, d_mean_dev && d_sd_dev && fst_mean_dev && fst_sd_dev && row_window_dev && row_d_dev && row_width_dev && row_width_from_r_dev &&
+                      row_width_p_dev && row_fst_delta_dev && row_fst_p_dev && win_chr_dev && win_ini_dev && win_fin_dev &&
+                      pool_off_dev && chrom_off_dev && (chrom_text_dev || n_chrom == 0),
+             "gudmc_rows: null pointer");
+    DevBuf<int64_t> first_dev;
+    int rc = first_dev.alloc(ctx, sizeof(int64_t) * first.size(), "gudmc_rows");
+    if (rc) return rc;
+    PG_HIP(ctx, hipMemcpyAsync(first_dev.get(), first.data(), sizeof(int64_t) * first.size(), hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (`first` has been read)
+    const PgGudmcUnits U{n, w, first_dev.get(), d_mean_dev, d_sd_dev, fst_mean_dev, fst_sd_dev, row_window_dev, row_d_dev, row_width_dev,
+                         row_width_from_r_dev, row_width_p_dev, row_fst_delta_dev, row_fst_p_dev, win_chr_dev, win_ini_dev, win_fin_dev,
+                         PgNames{reinterpret_cast<const unsigned char *>(pool_text_dev), pool_off_dev, n},
+                         PgNames{reinterpret_cast<const unsigned char *>(chrom_text_dev), chrom_off_dev, n_chrom}};
+    rc = rf_run(ctx, "gudmc_rows", U, row0, rows, text_dev, cap, bytes);
+    if (rc == PG_OK) PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // first_dev goes with this call
+    return rc;
+}
+
 extern "C" int pg_kinship_rows_dev(pg_ctx *ctx, int64_t p, int k, int64_t row0, int64_t rows, const double *beta_dev, const double *pval_dev,
                                    const int32_t *col_chrom_dev, const uint64_t *col_pos_dev, const int32_t *col_allele_dev,
                                    const char *chrom_text_dev, const int32_t *chrom_off_dev, int n_chrom, char *text_dev, int64_t cap,

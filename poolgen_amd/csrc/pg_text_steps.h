@@ -1,5 +1,5 @@
 // pg_text_steps.h -- the steps that the device text paths share, written once: the parsers (pg_vcf.hip, pg_sync.hip,
-// pg_pileup.hip) and the writers (pg_csv.hip, pg_syncfmt.hip, pg_resultfmt.hip); the loader of pg_locus_ops.hip takes the scan of
+// pg_pileup.hip) and the writers (pg_csv.hip, pg_syncfmt.hip, pg_resultfmt.hip, pg_tablefmt.hip); the loader of pg_locus_ops.hip takes the scan of
 // the workgroups' sums.  Nothing here knows a format.  Header-only: everything is in an anonymous namespace, so every translation
 // unit has its own instances (of the templates, those it launches).
 //   text and index   PgText, text_eq_mask, k_text_index<EMIT, Hook>: start[0 .. lines] of a text without host work per line;

@@ -332,6 +332,56 @@ def kinship_rows_host(beta, pval, col_chrom, col_pos, col_allele, chrom_names, r
     return _host_text_call(load_library().pg_host_kinship_rows, "pg_host_kinship_rows", args, n_threads)
 
 
+def label_table(labels):
+    """Row labels -> (one uint8 array of their bytes, int64 offsets: len(labels) + 1), the form the table formatter takes."""
+    raw = [s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in labels]
+    off = np.zeros(len(raw) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(b) for b in raw], dtype=np.int64)
+    return np.frombuffer(b"".join(raw), dtype=np.uint8).copy(), off
+
+
+def _table_view(shape, strides, itemsize=8):
+    """(rows, cols, row_stride, col_stride) in elements of a 2-D view: strided views (a transpose) are taken as they are"""
+    if len(shape) != 2:
+        raise ValueError("f64_table: expected a 2-D table")
+    if any(s % itemsize or s < 0 for s in strides):
+        raise ValueError("f64_table: the view's strides must be non-negative multiples of 8 bytes")
+    return int(shape[0]), int(shape[1]), int(strides[0] // itemsize), int(strides[1] // itemsize)
+
+
+def f64_table_host(x, labels=None, n_digits: int = -1, first_col_digits: int | None = None, row0: int = 0, n_rows: int | None = None,
+                   n_threads: int = 1) -> bytes:
+    """Engine.f64_table on the host (pg_host_f64_table): rows [row0, row0 + n_rows) of a 2-D float64 array (any strides: a
+    transposed view is printed without a copy) as CSV text, row r = labels[r] (as given, no separator added) + the cells
+    joined by ',' + '\\n'.  n_digits < 0 prints Rust's `{}`, 0..22 parse_f64_roundup_and_own; first_col_digits (default:
+    n_digits) applies to column 0."""
+    a = np.asarray(x, dtype=np.float64)
+    rows, cols, rs, cs = _table_view(a.shape, a.strides)
+    n_rows = rows - row0 if n_rows is None else n_rows
+    text, off = (None, None) if labels is None else label_table(labels)
+    if off is not None and len(off) != rows + 1:
+        raise ValueError("f64_table: one label per row of the table")
+    args = [a.ctypes.data if a.size else None, rows, cols, rs, cs, int(row0), int(n_rows), int(n_digits),
+            int(n_digits if first_col_digits is None else first_col_digits), None if text is None else text.ctypes.data,
+            None if off is None else off.ctypes.data]
+    return _host_text_call(load_library().pg_host_f64_table, "pg_host_f64_table", args, n_threads)
+
+
+GUDMC_ROW_KEYS = ("rows", "d_mean", "d_sd", "fst_mean", "fst_sd", "window", "d", "width", "width_dev", "width_p", "fst_delta", "fst_p")
+
+
+def gudmc_rows_host(res, win_chr, win_ini, win_fin, pool_names, chrom_names, row0: int = 0, rows: int | None = None, n_threads: int = 1) -> bytes:
+    """Engine.gudmc_rows on the host (pg_host_gudmc_rows): `res` is the dict of Engine.gudmc_from_tables as NumPy arrays."""
+    keep = [np.ascontiguousarray(res[k], dtype=np.int64 if k in ("rows", "window") else np.float64) for k in GUDMC_ROW_KEYS]
+    n = keep[0].size; w = keep[5].size // max(n * n, 1)
+    ch = np.ascontiguousarray(win_chr, dtype=np.int32); ini = _u64(win_ini); fin = _u64(win_fin)
+    ptext, poff = name_table(pool_names); ctext, coff = name_table(chrom_names)
+    rows = int(keep[0].sum()) * n - row0 if rows is None else rows
+    args = [n, w, int(row0), int(rows)] + [k.ctypes.data for k in keep] + [ch.ctypes.data, ini.ctypes.data, fin.ctypes.data,
+            ptext.ctypes.data if ptext.size else None, poff.ctypes.data, ctext.ctypes.data if ctext.size else None, coff.ctypes.data, len(coff) - 1]
+    return _host_text_call(load_library().pg_host_gudmc_rows, "pg_host_gudmc_rows", args, n_threads)
+
+
 class Engine:
     def __init__(self, device: int | None = None, use_torch_stream: bool = True):
         self._lib = load_library()
@@ -922,6 +972,51 @@ class Engine:
                 names.data_ptr() if names.numel() else None, off.data_ptr(), off.numel() - 1]
         return self._text_call(self._lib.pg_kinship_rows_dev, "pg_kinship_rows_dev", args, out)
 
+    # ---- the popgen writer (pg_tablefmt.hip, pg_resultfmt.hip) -----------------------------------
+    def f64_table(self, x: torch.Tensor, labels=None, n_digits: int = -1, first_col_digits: int | None = None, row0: int = 0,
+                  n_rows: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Rows [row0, row0 + n_rows) of a 2-D float64 tensor on the device (any non-negative strides: a transposed view is
+        printed without a copy) as CSV text, formatted on the GPU one lane per cell: row r = labels[r] (as given, no separator
+        added) + the cells joined by ',' + '\\n'.  n_digits < 0 prints Rust's `{}`, 0..22 parse_f64_roundup_and_own;
+        first_col_digits (default: n_digits) applies to column 0.  `labels`: a list of names, or a (uint8 bytes, int64 offsets)
+        pair of tensors already on the device.  Returns a uint8 tensor on the device; with `out` one call formats into it."""
+        dev = torch.device("cuda", self.device)
+        if x.dtype != torch.float64 or x.device != dev:
+            raise ValueError("f64_table: expected a float64 tensor on this engine's GPU")
+        rows, cols, rs, cs = _table_view(tuple(x.shape), tuple(s * 8 for s in x.stride()))
+        n_rows = rows - row0 if n_rows is None else n_rows
+        if labels is None:
+            text = off = None
+        elif isinstance(labels, tuple):
+            text, off = labels
+        else:
+            t, o = label_table(labels)
+            text, off = torch.from_numpy(t).to(dev), torch.from_numpy(o).to(dev)
+        if off is not None and off.numel() != rows + 1:
+            raise ValueError("f64_table: one label per row of the table")
+        args = [self._ctx, x.data_ptr() if x.numel() else None, rows, cols, rs, cs, int(row0), int(n_rows), int(n_digits),
+                int(n_digits if first_col_digits is None else first_col_digits),
+                None if text is None else (self._dev(text, torch.uint8) if text.numel() else self._dev(off, torch.int64)),
+                None if off is None else self._dev(off, torch.int64)]
+        return self._text_call(self._lib.pg_f64_table_dev, "pg_f64_table_dev", args, out)
+
+    def gudmc_rows(self, res: dict, win_chr, win_ini, win_fin, pool_names, chrom_names, row0: int = 0, rows: int | None = None,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+        """Rows [row0, row0 + rows) of gudmc's file from the dict gudmc_from_tables returns (its tensors stay on the device; only
+        rows[n] is read back), the windows' chromosome ids, first and last positions, the pool names and the chromosome names
+        (by id), formatted on the GPU.  Returns a uint8 tensor on the device."""
+        dev = torch.device("cuda", self.device)
+        n = res["rows"].numel(); w = res["window"].numel() // max(n * n, 1)
+        ch = torch.as_tensor(np.ascontiguousarray(win_chr, dtype=np.int32)).to(dev)
+        ini = torch.as_tensor(_u64(win_ini).view(np.int64)).to(dev); fin = torch.as_tensor(_u64(win_fin).view(np.int64)).to(dev)
+        ptext, poff = self._names_dev(pool_names); ctext, coff = self._names_dev(chrom_names)
+        rows = int(res["rows"].sum().item()) * n - row0 if rows is None else rows
+        args = [self._ctx, n, w, int(row0), int(rows)] + \
+               [self._dev(res[k], torch.int64 if k in ("rows", "window") else torch.float64) for k in GUDMC_ROW_KEYS] + \
+               [ch.data_ptr(), ini.data_ptr(), fin.data_ptr(), ptext.data_ptr() if ptext.numel() else None, poff.data_ptr(),
+                ctext.data_ptr() if ctext.numel() else None, coff.data_ptr(), coff.numel() - 1]
+        return self._text_call(self._lib.pg_gudmc_rows_dev, "pg_gudmc_rows_dev", args, out)
+
     # ---- imputation (src/imputation/) ------------------------------------------------------------
     def _impute_args(self, M, locus_col, n):
         p, ld, n = self._g_dims(M, n)
@@ -1138,6 +1233,54 @@ class Engine:
                                               lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, *cptr, len(wh),
                                               ps.ctypes.data, d.ctypes.data, mean.ctypes.data, theta.ctypes.data,
                                               pi.ctypes.data), "pg_tajima_d_dev")
+        return d, mean, theta, pi
+
+    # The tables forms: the same arguments, the same bits, but the results are CUDA tensors that never touched the host.
+    def _f64_dev(self, *shape):
+        return torch.empty(shape, dtype=torch.float64, device=torch.device("cuda", self.device))
+
+    def theta_pi_tables(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
+        """theta_pi with its results left on the device (pg_pi_tables_dev): (pi per window [n_windows x n], mean [n])."""
+        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
+        win = self._f64_dev(len(wh), n); mean = self._f64_dev(n)
+        self._check(self._lib.pg_pi_tables_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
+                                               lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
+                                               win.data_ptr(), mean.data_ptr()), "pg_pi_tables_dev")
+        return win, mean
+
+    def fst_tables(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
+        """fst with its results left on the device (pg_fst_tables_dev): (genome-wide mean [n x n], per window [n_windows x n*n])."""
+        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
+        mean = self._f64_dev(n, n); win = self._f64_dev(len(wh), n * n)
+        self._check(self._lib.pg_fst_tables_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
+                                                lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
+                                                mean.data_ptr(), win.data_ptr() if len(wh) else None), "pg_fst_tables_dev")
+        return mean, win
+
+    def theta_watterson_tables(self, G, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
+        """theta_watterson with its results left on the device (pg_watterson_tables_dev): (theta_W per window, mean, S per window)."""
+        p, ld, n, lc, wh, wt = self._popgen_args(G, G, locus_col, win_head, win_tail, n)
+        ps = _host_f64(pool_sizes)
+        assert len(ps) == n
+        cptr, keep = self._count_args(count, len(wh))
+        win = self._f64_dev(len(wh), n); mean = self._f64_dev(n)
+        seg = torch.empty((len(wh), n), dtype=torch.int64, device=win.device)
+        self._check(self._lib.pg_watterson_tables_dev(self._ctx, self._dev(G, torch.float64), p, n, ld, lc.ctypes.data, len(lc) - 1,
+                                                      wh.ctypes.data, wt.ctypes.data, *cptr, len(wh), ps.ctypes.data,
+                                                      win.data_ptr(), mean.data_ptr(), seg.data_ptr()), "pg_watterson_tables_dev")
+        return win, mean, seg
+
+    def tajima_d_tables(self, G, cov, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
+        """tajima_d with its results left on the device (pg_tajima_d_tables_dev): (D per window, mean, theta_W, pi per window)."""
+        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
+        ps = _host_f64(pool_sizes)
+        assert len(ps) == n
+        cptr, keep = self._count_args(count, len(wh))
+        d = self._f64_dev(len(wh), n); mean = self._f64_dev(n); theta = self._f64_dev(len(wh), n); pi = self._f64_dev(len(wh), n)
+        self._check(self._lib.pg_tajima_d_tables_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
+                                                     lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, *cptr, len(wh),
+                                                     ps.ctypes.data, d.data_ptr(), mean.data_ptr(), theta.data_ptr(),
+                                                     pi.data_ptr()), "pg_tajima_d_tables_dev")
         return d, mean, theta, pi
 
     def _table(self, a) -> torch.Tensor:
