@@ -375,6 +375,8 @@ int pg_gp_predict_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_
  *   pg_fst_dev: fst_mean (host, n x n) mean over all loci (:145), fst_win (host, n_windows x n*n);
  *               fails with PG_ERR_INVALID where the reference's assert does (a locus whose
  *               frequencies do not sum to one in every pool, :66).
+ * Each is its tables form (below) plus the copy to the host: pg_pi_dev into device memory of its own;
+ * pg_fst_dev window slab by window slab, never more than 2^30 bytes of fst_win on the device.
  * ------------------------------------------------------------------------------------- */
 int64_t pg_host_sliding_windows(const int32_t *chr_id, const uint64_t *pos, int64_t L, uint64_t window_size_bp,
                                 uint64_t window_slide_size_bp, uint64_t min_loci_per_window, int64_t *head,
@@ -385,10 +387,11 @@ int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p
 int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                int64_t n_windows, double *fst_mean, double *fst_win);
-/* The tables forms: the same arguments and the same bits, but the outputs are DEVICE memory of the same shapes, so a table can
- * go on to pg_gudmc_dev or to pg_f64_table_dev without touching the host.  The means across windows are summed on the device in
- * the host forms' order (left to right); pg_fst_tables_dev's batches of windows write straight into fst_win_dev.  Every form
- * has returned only when its work on the device is done.  (pg_watterson_tables_dev, pg_tajima_d_tables_dev: below.) */
+/* The tables forms: the same arguments, but the outputs are DEVICE memory of the same shapes, so a table can go on to
+ * pg_gudmc_dev or to pg_f64_table_dev without touching the host.  They are the one device path of these statistics: a host form
+ * above runs the same refusals and the same kernels and copies the results down, so the two forms agree in every bit.  The means
+ * across windows are summed on the device, left to right; pg_fst_tables_dev's slabs of windows write straight into fst_win_dev.
+ * Every form has returned only when its work on the device is done.  (pg_watterson_tables_dev, pg_tajima_d_tables_dev: below.) */
 int pg_pi_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                      const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                      int64_t n_windows, double *pi_win_dev, double *pi_mean_dev);
@@ -419,17 +422,20 @@ int64_t pg_host_watterson_windows(const int32_t *chr_id, const uint64_t *pos, in
                                   uint64_t window_slide_size_bp, uint64_t min_loci_per_window, int64_t *head,
                                   int64_t *tail, int64_t *cov, int64_t *seed, int64_t *slot);
 /* win_cov, win_seed, win_slot all NULL = counted mode.  pool_sizes: host, n, used as given.
- * theta_win n_windows x n, theta_mean n, seg_win (optional) n_windows x n counts S. */
+ * theta_win n_windows x n, theta_mean n, seg_win (optional) n_windows x n counts S.
+ * The host form of pg_watterson_tables_dev: that into device memory of its own, then the copy down. */
 int pg_watterson_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
                      const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
                      const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win,
                      double *theta_mean, int64_t *seg_win);
-/* d_win n_windows x n, d_mean n; theta_win / pi_win optional outputs of the same pass. */
+/* d_win n_windows x n, d_mean n; theta_win / pi_win optional outputs of the same pass.
+ * The host form of pg_tajima_d_tables_dev, as above. */
 int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                     const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                     const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
                     const double *pool_sizes, double *d_win, double *d_mean, double *theta_win, double *pi_win);
-/* The tables forms of the two (see pg_pi_tables_dev): outputs on the device, the optional ones may be NULL as above. */
+/* The tables forms of the two (see pg_pi_tables_dev), which the host forms above copy from: outputs on the device, the
+ * optional ones may be NULL as above. */
 int pg_watterson_tables_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
                             const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
                             const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win_dev,

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void k_chunk_reduce(const double *__restrict__
     out[i] = s / denom;
 }
 
-// mean_axis(Axis(0)) of a windows x n table, left to right as the host loops of the host-output entry points add: a lane a pool
+// mean_axis(Axis(0)) of a windows x n table, the one statement of it: the windows added left to right, a lane a pool
 __global__ __launch_bounds__(256) void k_window_mean(const double *__restrict__ vals, int64_t nw, int n, double *__restrict__ mean) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
@@ -256,14 +256,19 @@ __global__ __launch_bounds__(256) void k_window_mean(const double *__restrict__ 
     mean[j] = s / (double)nw;
 }
 
-int check_shape(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                const int64_t *locus_col, int64_t L, const int64_t *wh, const int64_t *wt, int64_t nw, const char *who) {
-    PG_CHECK(ctx, G_dev && cov_dev && locus_col && p > 0 && n >= 1 && ld >= n && L >= 1, "%s: bad arguments", who);
-    PG_CHECK(ctx, locus_col[0] == 0 && locus_col[L] == p, "%s: locus_col must run from 0 to p", who);
-    for (int64_t l = 0; l < L; ++l) PG_CHECK(ctx, locus_col[l] < locus_col[l + 1], "%s: empty locus %lld", who, (long long)l);
-    PG_CHECK(ctx, nw >= 0 && (nw == 0 || (wh && wt)), "%s: windows missing", who);
-    for (int64_t w = 0; w < nw; ++w)
-        PG_CHECK(ctx, wh[w] >= 0 && wh[w] <= wt[w] && wt[w] < L, "%s: window %lld out of range", who, (long long)w);
+// What every entry point is handed, as plain data: the loader's matrix with the first column of every locus (host; cov is
+// null where no coverages are read), and the windows (host; cov, seed and slot are the reference's count of
+// watterson_estimator and tajima_d, all three null in the counted mode and for pi and fst).
+struct PopMatrix { const double *G, *cov; int64_t p; int n; int64_t ld; const int64_t *locus_col; int64_t L; };
+struct PopWindows { const int64_t *head, *tail; int64_t nw; const int64_t *cov, *seed, *slot; };
+
+int check_shape(pg_ctx *ctx, const PopMatrix &m, bool with_cov, const PopWindows &w, const char *who) {
+    PG_CHECK(ctx, m.G && (m.cov || !with_cov) && m.locus_col && m.p > 0 && m.n >= 1 && m.ld >= m.n && m.L >= 1, "%s: bad arguments", who);
+    PG_CHECK(ctx, m.locus_col[0] == 0 && m.locus_col[m.L] == m.p, "%s: locus_col must run from 0 to p", who);
+    for (int64_t l = 0; l < m.L; ++l) PG_CHECK(ctx, m.locus_col[l] < m.locus_col[l + 1], "%s: empty locus %lld", who, (long long)l);
+    PG_CHECK(ctx, w.nw >= 0 && (w.nw == 0 || (w.head && w.tail)), "%s: windows missing", who);
+    for (int64_t i = 0; i < w.nw; ++i)
+        PG_CHECK(ctx, w.head[i] >= 0 && w.head[i] <= w.tail[i] && w.tail[i] < m.L, "%s: window %lld out of range", who, (long long)i);
     return PG_OK;
 }
 
@@ -297,225 +302,287 @@ void diversity_constants(const double *pool_sizes, int n, std::vector<double> &k
 
 constexpr double POOL_SIZE_MAX = 1e9; // the harmonic sums are loops over 1 .. pool size
 
-// watterson_estimator (tajima == false: no coverages, no pi) and tajima_d on one locus pass and one window pass
-// dev_out: the outputs are device memory (the tables entry points); the kernels write into them and the means are k_window_mean's
-int diversity_run(pg_ctx *ctx, bool dev_out, bool tajima, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                  const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov,
-                  const int64_t *win_seed, const int64_t *win_slot, int64_t nw, const double *pool_sizes, double *d_win,
-                  double *d_mean, double *theta_win, double *theta_mean, double *pi_win, int64_t *seg_win) {
-    const char *who = tajima ? "tajima_d" : "watterson";
-    int rc = check_shape(ctx, G_dev, tajima ? cov_dev : G_dev, p, n, ld, locus_col, L, win_head, win_tail, nw, who);
+// The statistics per (window, pool): watterson_estimator's theta_W, theta_pi's pi and tajima_d's D, which fills the other two
+// tables on its way where asked to.  A statistic is named by the index of its table (windows x n) in WindowOut: win[stat] and
+// mean (n: its mean across windows) are required, the other tables (tajima_d) and seg (watterson: S per window) optional.
+enum Stat { THETA_W, THETA_PI, TAJIMA_D, N_STATS };
+const char *const STAT_NAME[N_STATS] = {"watterson", "pi", "tajima_d"};
+struct WindowOut { double *win[N_STATS]; int64_t *seg; double *mean; };
+
+// the refusals, the same for both forms: `o` holds the caller's pointers, host or device
+int stat_check(pg_ctx *ctx, Stat stat, const PopMatrix &m, const PopWindows &w, const double *pool_sizes, const WindowOut &o) {
+    const char *who = STAT_NAME[stat];
+    const int rc = check_shape(ctx, m, stat != THETA_W, w, who);
     if (rc) return rc;
-    PG_CHECK(ctx, nw >= 1, "%s: There were no windows defined.", who);
-    PG_CHECK(ctx, pool_sizes && (tajima ? d_win && d_mean : theta_win && theta_mean), "%s: null argument", who);
-    const bool reference = win_cov || win_seed || win_slot;
-    PG_CHECK(ctx, !reference || (win_cov && win_seed && win_slot), "%s: win_cov, win_seed and win_slot go together", who);
-    for (int64_t w = 0; reference && w < nw; ++w)
-        PG_CHECK(ctx, win_cov[w] >= 1 && win_seed[w] >= 0 && win_seed[w] < L && win_slot[w] >= 0 && win_slot[w] < L,
-                 "%s: count of window %lld out of range", who, (long long)w);
-    for (int j = 0; j < n; ++j)
+    if (stat == THETA_PI) {
+        PG_CHECK(ctx, w.nw >= 1 && o.win[THETA_PI] && o.mean, "pi: There were no windows defined."); // pi.rs:81
+        return PG_OK;
+    }
+    PG_CHECK(ctx, w.nw >= 1, "%s: There were no windows defined.", who);
+    PG_CHECK(ctx, pool_sizes && o.win[stat] && o.mean, "%s: null argument", who);
+    const bool reference = w.cov || w.seed || w.slot;
+    PG_CHECK(ctx, !reference || (w.cov && w.seed && w.slot), "%s: win_cov, win_seed and win_slot go together", who);
+    for (int64_t i = 0; reference && i < w.nw; ++i)
+        PG_CHECK(ctx, w.cov[i] >= 1 && w.seed[i] >= 0 && w.seed[i] < m.L && w.slot[i] >= 0 && w.slot[i] < m.L,
+                 "%s: count of window %lld out of range", who, (long long)i);
+    for (int j = 0; j < m.n; ++j)
         PG_CHECK(ctx, !(pool_sizes[j] > POOL_SIZE_MAX), "%s: pool size %d is beyond %.0f", who, j, POOL_SIZE_MAX);
+    return PG_OK;
+}
+
+// watterson_estimator (tajima == false: no coverages, no pi) and tajima_d on one locus pass and one window pass, checked
+// arguments, every pointer of `o` device memory: the kernels write into the caller's tables
+int diversity_tables(pg_ctx *ctx, bool tajima, const PopMatrix &m, const PopWindows &w, const double *pool_sizes, const WindowOut &o) {
+    const char *who = tajima ? "tajima_d" : "watterson";
+    const int n = m.n;
+    const int64_t L = m.L, nw = w.nw;
     std::vector<double> kc;
     diversity_constants(pool_sizes, n, kc);
     PG_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ln = (size_t)L * n, wn = (size_t)nw * n;
-    const int nout = tajima ? 3 : 1; // theta | pi | D
-    DevBuf<int64_t> lc, win, seg;
-    DevBuf<double> pi, kcd, out;
-    DevBuf<uint8_t> flag;
+    const bool reference = w.cov != nullptr;
     const int nwin = reference ? 5 : 2; // head | tail | cov | seed | slot
+    // the window kernel writes theta always and pi for tajima_d: scratch for the one the caller did not ask for
+    double *theta_dev = o.win[THETA_W], *pi_dev = o.win[THETA_PI];
+    const bool own_theta = !theta_dev, own_pi = tajima && !pi_dev;
+    DevBuf<int64_t> lc, win;
+    DevBuf<double> pi, kcd, scratch;
+    DevBuf<uint8_t> flag;
+    int rc;
     if ((rc = lc.alloc(ctx, sizeof(int64_t) * (L + 1), who))) return rc;
     if ((rc = flag.alloc(ctx, ln, who))) return rc;
     if (tajima && (rc = pi.alloc(ctx, sizeof(double) * ln, who))) return rc;
     if ((rc = win.alloc(ctx, sizeof(int64_t) * nwin * nw, who))) return rc;
     if ((rc = kcd.alloc(ctx, sizeof(double) * 3 * n, who))) return rc;
-    if ((rc = out.alloc(ctx, sizeof(double) * nout * wn, who))) return rc;
-    if (seg_win && !dev_out && (rc = seg.alloc(ctx, sizeof(int64_t) * wn, who))) return rc;
-    const int64_t *host_win[5] = {win_head, win_tail, win_cov, win_seed, win_slot};
-    PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = scratch.alloc(ctx, sizeof(double) * ((size_t)own_theta + (size_t)own_pi) * wn, who))) return rc;
+    if (own_theta) theta_dev = scratch.get();
+    if (own_pi) pi_dev = scratch.get() + (own_theta ? wn : 0);
+    const int64_t *host_win[5] = {w.head, w.tail, w.cov, w.seed, w.slot};
+    PG_HIP(ctx, hipMemcpyAsync(lc.get(), m.locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
     for (int i = 0; i < nwin; ++i)
         PG_HIP(ctx, hipMemcpyAsync(win.get() + (size_t)i * nw, host_win[i], sizeof(int64_t) * nw, hipMemcpyHostToDevice, ctx->stream));
     PG_HIP(ctx, hipMemcpyAsync(kcd.get(), kc.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
     const int64_t *wh = win.get(), *wt = wh + nw;
     const int64_t *wc = reference ? wt + nw : nullptr, *wsd = reference ? wc + nw : nullptr, *wsl = reference ? wsd + nw : nullptr;
     const dim3 lgrid((unsigned)((ln + 255) / 256)), wgrid((unsigned)((wn + 255) / 256));
-    double *theta_dev = out.get(), *pi_dev = tajima ? theta_dev + wn : nullptr, *d_dev = tajima ? pi_dev + wn : nullptr;
-    int64_t *seg_dev = seg.get();
-    if (dev_out) { // straight into the caller's tables, where there are any
-        if (theta_win) theta_dev = theta_win;
-        if (tajima && pi_win) pi_dev = pi_win;
-        if (tajima) d_dev = d_win;
-        seg_dev = seg_win;
-    }
     if (tajima) {
-        hipLaunchKernelGGL((k_pop_locus<false, true>), lgrid, dim3(256), 0, ctx->stream, G_dev, cov_dev, lc.get(), L, n, ld,
+        hipLaunchKernelGGL((k_pop_locus<false, true>), lgrid, dim3(256), 0, ctx->stream, m.G, m.cov, lc.get(), L, n, m.ld,
                            (double *)nullptr, pi.get(), flag.get());
         hipLaunchKernelGGL(k_diversity_windows<true>, wgrid, dim3(256), 0, ctx->stream, pi.get(), flag.get(), wh, wt, wc, wsd, wsl,
-                           nw, n, kcd.get(), seg_dev, theta_dev, pi_dev, d_dev);
+                           nw, n, kcd.get(), o.seg, theta_dev, pi_dev, o.win[TAJIMA_D]);
     } else {
-        hipLaunchKernelGGL(k_poly_locus, lgrid, dim3(256), 0, ctx->stream, G_dev, lc.get(), L, n, ld, flag.get());
+        hipLaunchKernelGGL(k_poly_locus, lgrid, dim3(256), 0, ctx->stream, m.G, lc.get(), L, n, m.ld, flag.get());
         hipLaunchKernelGGL(k_diversity_windows<false>, wgrid, dim3(256), 0, ctx->stream, (const double *)nullptr, flag.get(), wh, wt,
-                           wc, wsd, wsl, nw, n, kcd.get(), seg_dev, theta_dev, pi_dev, d_dev);
+                           wc, wsd, wsl, nw, n, kcd.get(), o.seg, theta_dev, (double *)nullptr, (double *)nullptr);
     }
+    hipLaunchKernelGGL(k_window_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tajima ? o.win[TAJIMA_D] : theta_dev, nw, n,
+                       o.mean); // watterson_theta.rs:213-215, tajima_d.rs:98
     PG_HIP(ctx, hipGetLastError());
-    if (dev_out) {
-        hipLaunchKernelGGL(k_window_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tajima ? d_dev : theta_dev, nw, n,
-                           tajima ? d_mean : theta_mean);
-        PG_HIP(ctx, hipGetLastError());
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this call
-        return PG_OK;
-    }
-    if (theta_win) PG_HIP(ctx, hipMemcpyAsync(theta_win, theta_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
-    if (tajima && pi_win) PG_HIP(ctx, hipMemcpyAsync(pi_win, pi_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
-    if (tajima) PG_HIP(ctx, hipMemcpyAsync(d_win, d_dev, sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
-    if (seg_win) PG_HIP(ctx, hipMemcpyAsync(seg_win, seg.get(), sizeof(int64_t) * wn, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const double *vals = tajima ? d_win : theta_win;
-    double *mean = tajima ? d_mean : theta_mean;
-    for (int j = 0; j < n; ++j) { // mean_axis(Axis(0)) over the windows (watterson_theta.rs:213-215, tajima_d.rs:98): left to right
-        double s = 0.0;
-        for (int64_t w = 0; w < nw; ++w) s = s + vals[(size_t)w * n + j];
-        mean[j] = s / (double)nw;
-    }
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this call
     return PG_OK;
 }
 
-} // namespace
-
-// pg_pi_dev (dev_out = false: host outputs) and pg_pi_tables_dev (device outputs)
-static int pi_run(pg_ctx *ctx, bool dev_out, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                  const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
-                  int64_t n_windows, double *pi_win, double *pi_mean) {
-    if (!ctx) return PG_ERR_INVALID;
-    int rc = check_shape(ctx, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, "pi");
-    if (rc) return rc;
-    PG_CHECK(ctx, n_windows >= 1 && pi_win && pi_mean, "pi: There were no windows defined."); // pi.rs:81
+// checked arguments, outputs on the device
+int pi_tables(pg_ctx *ctx, const PopMatrix &m, const PopWindows &w, double *win_dev, double *mean_dev) {
+    const int n = m.n;
+    const int64_t L = m.L, nw = w.nw;
     PG_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf<int64_t> lc, wh, wt;
-    DevBuf<double> q1, pi, out;
+    DevBuf<double> q1, pi;
+    int rc;
     if ((rc = lc.alloc(ctx, sizeof(int64_t) * (L + 1), "pi"))) return rc;
     if ((rc = q1.alloc(ctx, sizeof(double) * (size_t)L * n, "pi"))) return rc;
     if ((rc = pi.alloc(ctx, sizeof(double) * (size_t)L * n, "pi"))) return rc;
-    if ((rc = wh.alloc(ctx, sizeof(int64_t) * n_windows, "pi"))) return rc;
-    if ((rc = wt.alloc(ctx, sizeof(int64_t) * n_windows, "pi"))) return rc;
-    if (!dev_out && (rc = out.alloc(ctx, sizeof(double) * (size_t)n_windows * n, "pi"))) return rc;
-    double *win_dev = dev_out ? pi_win : out.get();
-    PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(wh.get(), win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(wt.get(), win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL((k_pop_locus<true, false>), dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev,
-                       cov_dev, lc.get(), L, n, ld, q1.get(), pi.get(), (uint8_t *)nullptr);
-    hipLaunchKernelGGL(k_range_mean_1d, dim3((unsigned)(((size_t)n_windows * n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       pi.get(), wh.get(), wt.get(), n_windows, n, win_dev);
+    if ((rc = wh.alloc(ctx, sizeof(int64_t) * nw, "pi"))) return rc;
+    if ((rc = wt.alloc(ctx, sizeof(int64_t) * nw, "pi"))) return rc;
+    PG_HIP(ctx, hipMemcpyAsync(lc.get(), m.locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(wh.get(), w.head, sizeof(int64_t) * nw, hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(wt.get(), w.tail, sizeof(int64_t) * nw, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL((k_pop_locus<true, false>), dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, m.G,
+                       m.cov, lc.get(), L, n, m.ld, q1.get(), pi.get(), (uint8_t *)nullptr);
+    hipLaunchKernelGGL(k_range_mean_1d, dim3((unsigned)(((size_t)nw * n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       pi.get(), wh.get(), wt.get(), nw, n, win_dev);
+    hipLaunchKernelGGL(k_window_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, win_dev, nw, n, mean_dev); // pi.rs:133
     PG_HIP(ctx, hipGetLastError());
-    if (dev_out) {
-        hipLaunchKernelGGL(k_window_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, win_dev, n_windows, n, pi_mean);
-        PG_HIP(ctx, hipGetLastError());
-        PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this call
-        return PG_OK;
-    }
-    PG_HIP(ctx, hipMemcpyAsync(pi_win, out.get(), sizeof(double) * (size_t)n_windows * n, hipMemcpyDeviceToHost, ctx->stream));
-    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int j = 0; j < n; ++j) { // mean_axis(Axis(0)) over the windows (pi.rs:133): left to right
-        double s = 0.0;
-        for (int64_t w = 0; w < n_windows; ++w) s = s + pi_win[(size_t)w * n + j];
-        pi_mean[j] = s / (double)n_windows;
-    }
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this call
     return PG_OK;
 }
 
-extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                         const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
-                         int64_t n_windows, double *pi_win, double *pi_mean) {
-    return pi_run(ctx, false, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, pi_win, pi_mean);
+// a statistic's device function: checked arguments, every pointer of `o` device memory
+int stat_tables(pg_ctx *ctx, Stat stat, const PopMatrix &m, const PopWindows &w, const double *pool_sizes, const WindowOut &o) {
+    return stat == THETA_PI ? pi_tables(ctx, m, w, o.win[THETA_PI], o.mean) : diversity_tables(ctx, stat == TAJIMA_D, m, w, pool_sizes, o);
 }
 
-extern "C" int pg_pi_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                                const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
-                                int64_t n_windows, double *pi_win_dev, double *pi_mean_dev) {
-    return pi_run(ctx, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, pi_win_dev, pi_mean_dev);
-}
-
-// pg_fst_dev (dev_out = false: host outputs) and pg_fst_tables_dev (device outputs: the batches of windows write straight into
-// the caller's table)
-static int fst_run(pg_ctx *ctx, bool dev_out, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                   const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
-                   int64_t n_windows, double *fst_mean, double *fst_win) {
+// The tables form: the refusals, then the device function on the caller's device memory.
+int tables_form(pg_ctx *ctx, Stat stat, const PopMatrix &m, const PopWindows &w, const double *pool_sizes, const WindowOut &o) {
     if (!ctx) return PG_ERR_INVALID;
-    int rc = check_shape(ctx, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, "fst");
+    const int rc = stat_check(ctx, stat, m, w, pool_sizes, o);
+    return rc ? rc : stat_tables(ctx, stat, m, w, pool_sizes, o);
+}
+
+// The host form: the same into a block of this call's own, [mean: n | the tables asked for], then the copy down -- so the
+// two forms cannot differ in a bit.
+int host_form(pg_ctx *ctx, Stat stat, const PopMatrix &m, const PopWindows &w, const double *pool_sizes, const WindowOut &host) {
+    if (!ctx) return PG_ERR_INVALID;
+    int rc = stat_check(ctx, stat, m, w, pool_sizes, host);
     if (rc) return rc;
-    PG_CHECK(ctx, fst_mean && (n_windows == 0 || fst_win), "fst: null output");
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t wn = (size_t)w.nw * m.n;
+    size_t asked = 0;
+    for (const double *t : host.win) asked += t != nullptr;
+    DevBuf<double> block;
+    DevBuf<int64_t> seg;
+    if ((rc = block.alloc(ctx, sizeof(double) * (m.n + asked * wn), STAT_NAME[stat]))) return rc;
+    if (host.seg && (rc = seg.alloc(ctx, sizeof(int64_t) * wn, STAT_NAME[stat]))) return rc;
+    WindowOut dev = {{nullptr, nullptr, nullptr}, seg.get(), block.get()};
+    double *next = block.get() + m.n;
+    for (int t = 0; t < N_STATS; ++t)
+        if (host.win[t]) { dev.win[t] = next; next += wn; }
+    if ((rc = stat_tables(ctx, stat, m, w, pool_sizes, dev))) return rc;
+    for (int t = 0; t < N_STATS; ++t)
+        if (host.win[t]) PG_HIP(ctx, hipMemcpyAsync(host.win[t], dev.win[t], sizeof(double) * wn, hipMemcpyDeviceToHost, ctx->stream));
+    if (host.seg) PG_HIP(ctx, hipMemcpyAsync(host.seg, dev.seg, sizeof(int64_t) * wn, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(host.mean, dev.mean, sizeof(double) * m.n, hipMemcpyDeviceToHost, ctx->stream));
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PG_OK;
+}
+
+// ---- fst, in two steps, so that the host form never holds more than a slab of the window table on the device ----
+
+int fst_check(pg_ctx *ctx, const PopMatrix &m, const PopWindows &w, const double *fst_mean, const double *fst_win) {
+    const int rc = check_shape(ctx, m, true, w, "fst");
+    if (rc) return rc;
+    PG_CHECK(ctx, fst_mean && (w.nw == 0 || fst_win), "fst: null output");
+    return PG_OK;
+}
+
+// what the first step leaves on the device for the second: the loci's first columns, q1 per (locus, pool), the windows
+struct FstPlan { DevBuf<int64_t> lc, wh, wt; DevBuf<double> q1; };
+
+// k_fst_ranges over `ranges` ranges of loci (head, tail: device), n x n each, queued on the context's stream: their sums for step
+// 1, or (divide) their means -- step 2, windows [w0, w0 + k) of the per-window table, is this on s.wh + w0 and s.wt + w0
+int fst_ranges(pg_ctx *ctx, const PopMatrix &m, const FstPlan &s, const int64_t *head, const int64_t *tail, int64_t ranges, int divide,
+               double *out_dev) {
+    const int ntile = (m.n + FTILE - 1) / FTILE;
+    const int ntri = ntile * (ntile + 1) / 2;
+    hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)ranges, ntri), dim3(FT * FT), 0, ctx->stream, m.G, s.q1.get(), s.lc.get(), head, tail,
+                       m.n, m.ld, ntile, divide, out_dev);
+    PG_HIP(ctx, hipGetLastError());
+    return PG_OK;
+}
+
+// Step 1 (checked arguments): the reference's guard, q1, the genome-wide mean into mean_dev (n x n), the windows sent up.
+int fst_prepare(pg_ctx *ctx, const PopMatrix &m, const PopWindows &w, double *mean_dev, FstPlan &s) {
+    const int n = m.n;
+    const int64_t L = m.L;
     PG_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)n * n;
     // the genome-wide mean: equal chunks of loci -> partial sums -> one ordered reduction
     const int64_t chunk = std::max<int64_t>(64, (L + 2047) / 2048);
     const int64_t nchunks = (L + chunk - 1) / chunk;
-    std::vector<int64_t> ch(nchunks), ct(nchunks);
-    for (int64_t c = 0; c < nchunks; ++c) { ch[c] = c * chunk; ct[c] = std::min<int64_t>(L, (c + 1) * chunk) - 1; }
-    DevBuf<int64_t> lc, wh, wt, chh, cht;
-    DevBuf<double> q1, pi, part, mean, out;
+    std::vector<int64_t> ch(2 * nchunks); // heads | tails
+    for (int64_t c = 0; c < nchunks; ++c) { ch[c] = c * chunk; ch[nchunks + c] = std::min<int64_t>(L, (c + 1) * chunk) - 1; }
+    DevBuf<int64_t> chunks;
+    DevBuf<double> pi, part;
     DevBuf<int> bad;
-    if ((rc = lc.alloc(ctx, sizeof(int64_t) * (L + 1), "fst"))) return rc;
-    if ((rc = q1.alloc(ctx, sizeof(double) * (size_t)L * n, "fst"))) return rc;
+    int rc;
+    if ((rc = s.lc.alloc(ctx, sizeof(int64_t) * (L + 1), "fst"))) return rc;
+    if ((rc = s.q1.alloc(ctx, sizeof(double) * (size_t)L * n, "fst"))) return rc;
     if ((rc = pi.alloc(ctx, sizeof(double) * (size_t)L * n, "fst"))) return rc;
-    if ((rc = chh.alloc(ctx, sizeof(int64_t) * nchunks, "fst"))) return rc;
-    if ((rc = cht.alloc(ctx, sizeof(int64_t) * nchunks, "fst"))) return rc;
+    if ((rc = chunks.alloc(ctx, sizeof(int64_t) * 2 * nchunks, "fst"))) return rc;
     if ((rc = part.alloc(ctx, sizeof(double) * nchunks * nn, "fst"))) return rc;
-    if (!dev_out && (rc = mean.alloc(ctx, sizeof(double) * nn, "fst"))) return rc;
     if ((rc = bad.alloc(ctx, sizeof(int), "fst"))) return rc;
+    if ((rc = s.wh.alloc(ctx, sizeof(int64_t) * w.nw, "fst"))) return rc;
+    if ((rc = s.wt.alloc(ctx, sizeof(int64_t) * w.nw, "fst"))) return rc;
     PG_HIP(ctx, hipMemsetAsync(bad.get(), 0, sizeof(int), ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(lc.get(), locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(chh.get(), ch.data(), sizeof(int64_t) * nchunks, hipMemcpyHostToDevice, ctx->stream));
-    PG_HIP(ctx, hipMemcpyAsync(cht.get(), ct.data(), sizeof(int64_t) * nchunks, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_pop_check, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, ctx->stream, G_dev, lc.get(), L, n,
-                       ld, bad.get());
-    hipLaunchKernelGGL((k_pop_locus<true, false>), dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, G_dev,
-                       cov_dev, lc.get(), L, n, ld, q1.get(), pi.get(), (uint8_t *)nullptr);
+    PG_HIP(ctx, hipMemcpyAsync(s.lc.get(), m.locus_col, sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, ctx->stream));
+    PG_HIP(ctx, hipMemcpyAsync(chunks.get(), ch.data(), sizeof(int64_t) * 2 * nchunks, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_pop_check, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, ctx->stream, m.G, s.lc.get(), L, n, m.ld, bad.get());
+    hipLaunchKernelGGL((k_pop_locus<true, false>), dim3((unsigned)(((size_t)L * n + 255) / 256)), dim3(256), 0, ctx->stream, m.G,
+                       m.cov, s.lc.get(), L, n, m.ld, s.q1.get(), pi.get(), (uint8_t *)nullptr);
     int hbad = 0;
     PG_HIP(ctx, hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (hbad) // the reference's assert!((g.sum_axis(Axis(1)).sum() - n as f64).abs() <= f64::EPSILON) (fst.rs:66)
         return pg_fail(ctx, PG_ERR_INVALID, "fst: the allele frequencies of a locus do not sum up to one in every pool");
-    const int ntile = (n + FTILE - 1) / FTILE;
-    const int ntri = ntile * (ntile + 1) / 2;
-    hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nchunks, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.get(),
-                       lc.get(), chh.get(), cht.get(), n, ld, ntile, 0, part.get());
+    if ((rc = fst_ranges(ctx, m, s, chunks.get(), chunks.get() + nchunks, nchunks, 0, part.get()))) return rc;
     hipLaunchKernelGGL(k_chunk_reduce, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, ctx->stream, part.get(), nchunks,
-                       (int64_t)nn, (double)L, dev_out ? fst_mean : mean.get());
+                       (int64_t)nn, (double)L, mean_dev);
     PG_HIP(ctx, hipGetLastError());
-    if (!dev_out) PG_HIP(ctx, hipMemcpyAsync(fst_mean, mean.get(), sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_windows > 0) {
-        if ((rc = wh.alloc(ctx, sizeof(int64_t) * n_windows, "fst"))) return rc;
-        if ((rc = wt.alloc(ctx, sizeof(int64_t) * n_windows, "fst"))) return rc;
-        PG_HIP(ctx, hipMemcpyAsync(wh.get(), win_head, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
-        PG_HIP(ctx, hipMemcpyAsync(wt.get(), win_tail, sizeof(int64_t) * n_windows, hipMemcpyHostToDevice, ctx->stream));
-        // the per-window table in slabs of windows (it is n^2 doubles per window)
-        const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(n_windows, (int64_t)(((size_t)1 << 30) / (nn * sizeof(double)))));
-        if (!dev_out && (rc = out.alloc(ctx, sizeof(double) * slab * nn, "fst"))) return rc;
-        for (int64_t w0 = 0; w0 < n_windows; w0 += slab) {
-            const int64_t nwb = std::min<int64_t>(slab, n_windows - w0);
-            hipLaunchKernelGGL(k_fst_ranges, dim3((unsigned)nwb, ntri), dim3(FT * FT), 0, ctx->stream, G_dev, q1.get(),
-                               lc.get(), wh.get() + w0, wt.get() + w0, n, ld, ntile, 1, dev_out ? fst_win + (size_t)w0 * nn : out.get());
-            PG_HIP(ctx, hipGetLastError());
-            if (dev_out) continue;
-            PG_HIP(ctx, hipMemcpyAsync(fst_win + (size_t)w0 * nn, out.get(), sizeof(double) * nwb * nn, hipMemcpyDeviceToHost, ctx->stream));
-            PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
+    if (w.nw > 0) {
+        PG_HIP(ctx, hipMemcpyAsync(s.wh.get(), w.head, sizeof(int64_t) * w.nw, hipMemcpyHostToDevice, ctx->stream));
+        PG_HIP(ctx, hipMemcpyAsync(s.wt.get(), w.tail, sizeof(int64_t) * w.nw, hipMemcpyHostToDevice, ctx->stream));
     }
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries go with this step
+    return PG_OK;
+}
+
+// the windows of one launch, in both forms: the slab of the host form, 2^30 bytes of the table (it is n^2 doubles per window)
+int64_t fst_slab(int n, int64_t nw) {
+    return std::min<int64_t>(nw, std::max<int64_t>(1, (int64_t)(((size_t)1 << 30) / ((size_t)n * n * sizeof(double)))));
+}
+
+} // namespace
+
+extern "C" int pg_pi_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                         const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                         int64_t n_windows, double *pi_win, double *pi_mean) {
+    return host_form(ctx, THETA_PI, {G_dev, cov_dev, p, n, ld, locus_col, L}, {win_head, win_tail, n_windows, nullptr, nullptr, nullptr}, nullptr,
+                     {{nullptr, pi_win, nullptr}, nullptr, pi_mean});
+}
+
+extern "C" int pg_pi_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                                const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                                int64_t n_windows, double *pi_win_dev, double *pi_mean_dev) {
+    return tables_form(ctx, THETA_PI, {G_dev, cov_dev, p, n, ld, locus_col, L}, {win_head, win_tail, n_windows, nullptr, nullptr, nullptr}, nullptr,
+                       {{nullptr, pi_win_dev, nullptr}, nullptr, pi_mean_dev});
+}
+
+// the slabs of windows write straight into the caller's table
+extern "C" int pg_fst_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
+                                 const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
+                                 int64_t n_windows, double *fst_mean_dev, double *fst_win_dev) {
+    if (!ctx) return PG_ERR_INVALID;
+    const PopMatrix m = {G_dev, cov_dev, p, n, ld, locus_col, L};
+    const PopWindows w = {win_head, win_tail, n_windows, nullptr, nullptr, nullptr};
+    int rc = fst_check(ctx, m, w, fst_mean_dev, fst_win_dev);
+    if (rc) return rc;
+    FstPlan s;
+    if ((rc = fst_prepare(ctx, m, w, fst_mean_dev, s))) return rc;
+    const int64_t slab = fst_slab(n, n_windows);
+    for (int64_t w0 = 0; w0 < n_windows; w0 += slab)
+        if ((rc = fst_ranges(ctx, m, s, s.wh.get() + w0, s.wt.get() + w0, std::min<int64_t>(slab, n_windows - w0), 1, fst_win_dev + (size_t)w0 * n * n)))
+            return rc;
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PG_OK;
 }
 
+// slab by slab through one slab of device memory
 extern "C" int pg_fst_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                           const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                           int64_t n_windows, double *fst_mean, double *fst_win) {
-    return fst_run(ctx, false, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, fst_mean, fst_win);
-}
-
-extern "C" int pg_fst_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
-                                 const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
-                                 int64_t n_windows, double *fst_mean_dev, double *fst_win_dev) {
-    return fst_run(ctx, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, n_windows, fst_mean_dev, fst_win_dev);
+    if (!ctx) return PG_ERR_INVALID;
+    const PopMatrix m = {G_dev, cov_dev, p, n, ld, locus_col, L};
+    const PopWindows w = {win_head, win_tail, n_windows, nullptr, nullptr, nullptr};
+    int rc = fst_check(ctx, m, w, fst_mean, fst_win);
+    if (rc) return rc;
+    PG_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n * n;
+    const int64_t slab = fst_slab(n, n_windows);
+    FstPlan s;
+    DevBuf<double> mean, out;
+    if ((rc = mean.alloc(ctx, sizeof(double) * nn, "fst"))) return rc;
+    if ((rc = out.alloc(ctx, sizeof(double) * slab * nn, "fst"))) return rc;
+    if ((rc = fst_prepare(ctx, m, w, mean.get(), s))) return rc;
+    PG_HIP(ctx, hipMemcpyAsync(fst_mean, mean.get(), sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
+    for (int64_t w0 = 0; w0 < n_windows; w0 += slab) {
+        const int64_t nwb = std::min<int64_t>(slab, n_windows - w0);
+        if ((rc = fst_ranges(ctx, m, s, s.wh.get() + w0, s.wt.get() + w0, nwb, 1, out.get()))) return rc;
+        PG_HIP(ctx, hipMemcpyAsync(fst_win + (size_t)w0 * nn, out.get(), sizeof(double) * nwb * nn, hipMemcpyDeviceToHost, ctx->stream));
+        PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PG_OK;
 }
 
 // row w of the table = row slot[w] of the kept rows, NaN where slot[w] < 0
@@ -552,27 +619,24 @@ extern "C" int pg_watterson_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int
                                 const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
                                 const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win,
                                 double *theta_mean, int64_t *seg_win) {
-    if (!ctx) return PG_ERR_INVALID;
-    return diversity_run(ctx, false, false, G_dev, nullptr, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
-                         pool_sizes, nullptr, nullptr, theta_win, theta_mean, nullptr, seg_win);
+    return host_form(ctx, THETA_W, {G_dev, nullptr, p, n, ld, locus_col, L}, {win_head, win_tail, n_windows, win_cov, win_seed, win_slot}, pool_sizes,
+                     {{theta_win, nullptr, nullptr}, seg_win, theta_mean});
 }
 
 extern "C" int pg_watterson_tables_dev(pg_ctx *ctx, const double *G_dev, int64_t p, int n, int64_t ld, const int64_t *locus_col, int64_t L,
                                        const int64_t *win_head, const int64_t *win_tail, const int64_t *win_cov, const int64_t *win_seed,
                                        const int64_t *win_slot, int64_t n_windows, const double *pool_sizes, double *theta_win_dev,
                                        double *theta_mean_dev, int64_t *seg_win_dev) {
-    if (!ctx) return PG_ERR_INVALID;
-    return diversity_run(ctx, true, false, G_dev, nullptr, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
-                         pool_sizes, nullptr, nullptr, theta_win_dev, theta_mean_dev, nullptr, seg_win_dev);
+    return tables_form(ctx, THETA_W, {G_dev, nullptr, p, n, ld, locus_col, L}, {win_head, win_tail, n_windows, win_cov, win_seed, win_slot}, pool_sizes,
+                       {{theta_win_dev, nullptr, nullptr}, seg_win_dev, theta_mean_dev});
 }
 
 extern "C" int pg_tajima_d_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
                                const int64_t *locus_col, int64_t L, const int64_t *win_head, const int64_t *win_tail,
                                const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
                                const double *pool_sizes, double *d_win, double *d_mean, double *theta_win, double *pi_win) {
-    if (!ctx) return PG_ERR_INVALID;
-    return diversity_run(ctx, false, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
-                         pool_sizes, d_win, d_mean, theta_win, nullptr, pi_win, nullptr);
+    return host_form(ctx, TAJIMA_D, {G_dev, cov_dev, p, n, ld, locus_col, L}, {win_head, win_tail, n_windows, win_cov, win_seed, win_slot}, pool_sizes,
+                     {{theta_win, pi_win, d_win}, nullptr, d_mean});
 }
 
 extern "C" int pg_tajima_d_tables_dev(pg_ctx *ctx, const double *G_dev, const double *cov_dev, int64_t p, int n, int64_t ld,
@@ -580,7 +644,6 @@ extern "C" int pg_tajima_d_tables_dev(pg_ctx *ctx, const double *G_dev, const do
                                       const int64_t *win_cov, const int64_t *win_seed, const int64_t *win_slot, int64_t n_windows,
                                       const double *pool_sizes, double *d_win_dev, double *d_mean_dev, double *theta_win_dev,
                                       double *pi_win_dev) {
-    if (!ctx) return PG_ERR_INVALID;
-    return diversity_run(ctx, true, true, G_dev, cov_dev, p, n, ld, locus_col, L, win_head, win_tail, win_cov, win_seed, win_slot, n_windows,
-                         pool_sizes, d_win_dev, d_mean_dev, theta_win_dev, nullptr, pi_win_dev, nullptr);
+    return tables_form(ctx, TAJIMA_D, {G_dev, cov_dev, p, n, ld, locus_col, L}, {win_head, win_tail, n_windows, win_cov, win_seed, win_slot}, pool_sizes,
+                       {{theta_win_dev, pi_win_dev, d_win_dev}, nullptr, d_mean_dev});
 }

@@ -1168,24 +1168,6 @@ class Engine:
         wh = np.ascontiguousarray(win_head, dtype=np.int64); wt = np.ascontiguousarray(win_tail, dtype=np.int64)
         return p, ld, n, lc, wh, wt
 
-    def theta_pi(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
-        """popgen::theta_pi (popgen/pi.rs:10-113): (pi per window [n_windows x n], mean across windows [n])."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
-        win = np.empty((len(wh), n)); mean = np.empty(n)
-        self._check(self._lib.pg_pi_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
-                                        lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
-                                        win.ctypes.data, mean.ctypes.data), "pg_pi_dev")
-        return win, mean
-
-    def fst(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
-        """popgen::fst (popgen/fst.rs:10-115, :158-200): (genome-wide mean [n x n], per window [n_windows x n*n])."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
-        mean = np.empty((n, n)); win = np.empty((len(wh), n * n))
-        self._check(self._lib.pg_fst_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
-                                         lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
-                                         mean.ctypes.data, win.ctypes.data), "pg_fst_dev")
-        return mean, win
-
     def watterson_windows(self, chrom_ids, pos, window_size_bp: int, window_slide_size_bp: int, min_loci_per_window: int):
         """theta_watterson's own window loop (popgen/watterson_theta.rs:56-164) -> (head, tail, cov, seed, slot): head/tail
         as sliding_windows; cov, seed, slot describe the reference's segregating-site count (include/poolgen_hip.h)."""
@@ -1207,81 +1189,81 @@ class Engine:
             raise ValueError("count must be (cov, seed, slot), one entry per window each")
         return [c.ctypes.data for c in keep], keep
 
+    # One marshalling per statistic, shared by its two forms: `fn` names the C entry point, `new(shape, dtype)` allocates an
+    # output -- _on_host for the host forms (numpy), _on_device for the tables forms: the same arguments, the same bits, but
+    # the results are CUDA tensors that never touched the host.
+    _on_host = staticmethod(np.empty)
+
+    def _on_device(self, shape, dtype=np.float64):
+        return torch.empty(shape, dtype=torch.float64 if dtype is np.float64 else torch.int64, device=torch.device("cuda", self.device))
+
+    @staticmethod
+    def _ptr(a):
+        return a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data
+
+    def _theta_pi(self, fn, new, G, cov, locus_col, win_head, win_tail, n):
+        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
+        win = new((len(wh), n)); mean = new((n,))
+        self._check(getattr(self._lib, fn)(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
+                                           lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
+                                           self._ptr(win), self._ptr(mean)), fn)
+        return win, mean
+
+    def _fst(self, fn, new, G, cov, locus_col, win_head, win_tail, n):
+        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
+        mean = new((n, n)); win = new((len(wh), n * n))
+        self._check(getattr(self._lib, fn)(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
+                                           lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
+                                           self._ptr(mean), self._ptr(win) if len(wh) else None), fn)
+        return mean, win
+
+    def _diversity(self, fn, new, G, cov, locus_col, win_head, win_tail, pool_sizes, count, n):
+        """theta_watterson (cov is None: the entry point takes no coverages) and tajima_d"""
+        p, ld, n, lc, wh, wt = self._popgen_args(G, G if cov is None else cov, locus_col, win_head, win_tail, n)
+        ps = _host_f64(pool_sizes)
+        assert len(ps) == n
+        cptr, keep = self._count_args(count, len(wh))
+        matrix = [self._dev(G, torch.float64)] + ([] if cov is None else [self._dev(cov, torch.float64)])
+        win = (len(wh), n)  # D, mean, theta_W, pi -- or theta_W, mean, S
+        out = [new(win), new((n,))] + ([new(win, np.int64)] if cov is None else [new(win), new(win)])
+        self._check(getattr(self._lib, fn)(self._ctx, *matrix, p, n, ld, lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data,
+                                           *cptr, len(wh), ps.ctypes.data, *[self._ptr(o) for o in out]), fn)
+        return tuple(out)
+
+    def theta_pi(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
+        """popgen::theta_pi (popgen/pi.rs:10-113): (pi per window [n_windows x n], mean across windows [n])."""
+        return self._theta_pi("pg_pi_dev", self._on_host, G, cov, locus_col, win_head, win_tail, n)
+
+    def theta_pi_tables(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
+        """theta_pi with its results left on the device (pg_pi_tables_dev): (pi per window [n_windows x n], mean [n])."""
+        return self._theta_pi("pg_pi_tables_dev", self._on_device, G, cov, locus_col, win_head, win_tail, n)
+
+    def fst(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
+        """popgen::fst (popgen/fst.rs:10-115, :158-200): (genome-wide mean [n x n], per window [n_windows x n*n])."""
+        return self._fst("pg_fst_dev", self._on_host, G, cov, locus_col, win_head, win_tail, n)
+
+    def fst_tables(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
+        """fst with its results left on the device (pg_fst_tables_dev): (genome-wide mean [n x n], per window [n_windows x n*n])."""
+        return self._fst("pg_fst_tables_dev", self._on_device, G, cov, locus_col, win_head, win_tail, n)
+
     def theta_watterson(self, G, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
         """popgen::theta_watterson (popgen/watterson_theta.rs:36-188): (theta_W per window [n_windows x n], mean across
         windows [n], segregating sites per window [n_windows x n]).  count = (cov, seed, slot) of watterson_windows
         reproduces the reference's count; None counts the polymorphic loci of each window.  pool_sizes are used as given."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, G, locus_col, win_head, win_tail, n)
-        ps = _host_f64(pool_sizes)
-        assert len(ps) == n
-        cptr, keep = self._count_args(count, len(wh))
-        win = np.empty((len(wh), n)); mean = np.empty(n); seg = np.empty((len(wh), n), dtype=np.int64)
-        self._check(self._lib.pg_watterson_dev(self._ctx, self._dev(G, torch.float64), p, n, ld, lc.ctypes.data, len(lc) - 1,
-                                               wh.ctypes.data, wt.ctypes.data, *cptr, len(wh), ps.ctypes.data,
-                                               win.ctypes.data, mean.ctypes.data, seg.ctypes.data), "pg_watterson_dev")
-        return win, mean, seg
+        return self._diversity("pg_watterson_dev", self._on_host, G, None, locus_col, win_head, win_tail, pool_sizes, count, n)
+
+    def theta_watterson_tables(self, G, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
+        """theta_watterson with its results left on the device (pg_watterson_tables_dev): (theta_W per window, mean, S per window)."""
+        return self._diversity("pg_watterson_tables_dev", self._on_device, G, None, locus_col, win_head, win_tail, pool_sizes, count, n)
 
     def tajima_d(self, G, cov, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
         """popgen::tajima_d (popgen/tajima_d.rs:10-96) in one pass over G: (D per window [n_windows x n], mean across
         windows [n], theta_W per window, pi per window).  count as for theta_watterson."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
-        ps = _host_f64(pool_sizes)
-        assert len(ps) == n
-        cptr, keep = self._count_args(count, len(wh))
-        d = np.empty((len(wh), n)); mean = np.empty(n); theta = np.empty((len(wh), n)); pi = np.empty((len(wh), n))
-        self._check(self._lib.pg_tajima_d_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
-                                              lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, *cptr, len(wh),
-                                              ps.ctypes.data, d.ctypes.data, mean.ctypes.data, theta.ctypes.data,
-                                              pi.ctypes.data), "pg_tajima_d_dev")
-        return d, mean, theta, pi
-
-    # The tables forms: the same arguments, the same bits, but the results are CUDA tensors that never touched the host.
-    def _f64_dev(self, *shape):
-        return torch.empty(shape, dtype=torch.float64, device=torch.device("cuda", self.device))
-
-    def theta_pi_tables(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
-        """theta_pi with its results left on the device (pg_pi_tables_dev): (pi per window [n_windows x n], mean [n])."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
-        win = self._f64_dev(len(wh), n); mean = self._f64_dev(n)
-        self._check(self._lib.pg_pi_tables_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
-                                               lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
-                                               win.data_ptr(), mean.data_ptr()), "pg_pi_tables_dev")
-        return win, mean
-
-    def fst_tables(self, G, cov, locus_col, win_head, win_tail, n: int | None = None):
-        """fst with its results left on the device (pg_fst_tables_dev): (genome-wide mean [n x n], per window [n_windows x n*n])."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
-        mean = self._f64_dev(n, n); win = self._f64_dev(len(wh), n * n)
-        self._check(self._lib.pg_fst_tables_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
-                                                lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, len(wh),
-                                                mean.data_ptr(), win.data_ptr() if len(wh) else None), "pg_fst_tables_dev")
-        return mean, win
-
-    def theta_watterson_tables(self, G, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
-        """theta_watterson with its results left on the device (pg_watterson_tables_dev): (theta_W per window, mean, S per window)."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, G, locus_col, win_head, win_tail, n)
-        ps = _host_f64(pool_sizes)
-        assert len(ps) == n
-        cptr, keep = self._count_args(count, len(wh))
-        win = self._f64_dev(len(wh), n); mean = self._f64_dev(n)
-        seg = torch.empty((len(wh), n), dtype=torch.int64, device=win.device)
-        self._check(self._lib.pg_watterson_tables_dev(self._ctx, self._dev(G, torch.float64), p, n, ld, lc.ctypes.data, len(lc) - 1,
-                                                      wh.ctypes.data, wt.ctypes.data, *cptr, len(wh), ps.ctypes.data,
-                                                      win.data_ptr(), mean.data_ptr(), seg.data_ptr()), "pg_watterson_tables_dev")
-        return win, mean, seg
+        return self._diversity("pg_tajima_d_dev", self._on_host, G, cov, locus_col, win_head, win_tail, pool_sizes, count, n)
 
     def tajima_d_tables(self, G, cov, locus_col, win_head, win_tail, pool_sizes, count=None, n: int | None = None):
         """tajima_d with its results left on the device (pg_tajima_d_tables_dev): (D per window, mean, theta_W, pi per window)."""
-        p, ld, n, lc, wh, wt = self._popgen_args(G, cov, locus_col, win_head, win_tail, n)
-        ps = _host_f64(pool_sizes)
-        assert len(ps) == n
-        cptr, keep = self._count_args(count, len(wh))
-        d = self._f64_dev(len(wh), n); mean = self._f64_dev(n); theta = self._f64_dev(len(wh), n); pi = self._f64_dev(len(wh), n)
-        self._check(self._lib.pg_tajima_d_tables_dev(self._ctx, self._dev(G, torch.float64), self._dev(cov, torch.float64), p, n, ld,
-                                                     lc.ctypes.data, len(lc) - 1, wh.ctypes.data, wt.ctypes.data, *cptr, len(wh),
-                                                     ps.ctypes.data, d.data_ptr(), mean.data_ptr(), theta.data_ptr(),
-                                                     pi.data_ptr()), "pg_tajima_d_tables_dev")
-        return d, mean, theta, pi
+        return self._diversity("pg_tajima_d_tables_dev", self._on_device, G, cov, locus_col, win_head, win_tail, pool_sizes, count, n)
 
     def _table(self, a) -> torch.Tensor:
         """a 2-D fp64 table (numpy or torch) as a contiguous tensor on this engine's GPU"""
@@ -1333,10 +1315,10 @@ class Engine:
 
     def gudmc(self, G, cov, locus_col, win_head, win_tail, win_chr, win_ini, win_fin, pool_sizes,
               sigma_threshold: float = 2.0, recombination_rate_cM_per_Mb: float = 0.73, count=None, n: int | None = None) -> dict:
-        """tajima_d, fst and gudmc_from_tables in one call; count as for tajima_d.  The two tables come down from the device and
-        go up again (pg_tajima_d_dev and pg_fst_dev return host tables): w * (n + n*n) doubles against n*n*w rows out."""
-        d_win = self.tajima_d(G, cov, locus_col, win_head, win_tail, pool_sizes, count=count, n=n)[0]
-        fst_win = self.fst(G, cov, locus_col, win_head, win_tail, n=n)[1]
+        """tajima_d_tables, fst_tables and gudmc_from_tables in one call; count as for tajima_d.  The two tables stay on the
+        device from the kernels that write them to the one that reads them."""
+        d_win = self.tajima_d_tables(G, cov, locus_col, win_head, win_tail, pool_sizes, count=count, n=n)[0]
+        fst_win = self.fst_tables(G, cov, locus_col, win_head, win_tail, n=n)[1]
         return self.gudmc_from_tables(d_win, fst_win, win_chr, win_ini, win_fin, sigma_threshold, recombination_rate_cM_per_Mb)
 
     # ---- genomic prediction -------------------------------------------------------------------

@@ -77,7 +77,7 @@ def check_diversity(engine, oracle, case, wh, wt, n, count, terms, what):
 
 
 # ---- the 32 x 32 tiles of pool pairs -----------------------------------------------------------------------------------------
-# k_fst_ranges (pg_popgen.hip:169-171, :180-187, :232-237): ntile = ceil(n / 32) tiles per edge, the upper triangle of them as
+# k_fst_ranges (pg_popgen.hip: FT, FR, FTILE; its launch in fst_ranges): ntile = ceil(n / 32) tiles per edge, the upper triangle of them as
 # grid.y; a thread holds 4 x 4 pairs, pool indices past n - 1 are clamped for the loads and masked for the stores.
 # (n, tiles per edge, tiles launched)
 TILE_POINTS = [
@@ -114,7 +114,7 @@ def test_fst_tiles_and_diversity_across_pool_counts(engine, oracle, n, ntile, nt
 
 
 # ---- the chunks of the genome-wide mean --------------------------------------------------------------------------------------
-# pg_fst_dev (pg_popgen.hip:464-467): chunk = max(64, ceil(L / 2048)) loci per partial sum, ceil(L / chunk) chunks, the last one
+# pg_fst_dev (pg_popgen.hip, fst_prepare): chunk = max(64, ceil(L / 2048)) loci per partial sum, ceil(L / chunk) chunks, the last one
 # partial; k_chunk_reduce adds the partial sums in chunk order.
 # (L, chunk, chunks, loci in the last chunk)
 CHUNK_POINTS = [
@@ -141,7 +141,7 @@ def test_fst_mean_across_the_chunk_rule(engine, oracle, L, chunk, nchunks, last)
 
 # ---- the slabs of the per-window table ---------------------------------------------------------------------------------------
 def test_fst_window_table_second_slab(engine, oracle):
-    """pg_fst_dev produces the n_windows x n^2 table 2^30 / (8 n^2) windows at a time (pg_popgen.hip:506-515).  n = 450 pools: slab =
+    """pg_fst_dev produces the n_windows x n^2 table 2^30 / (8 n^2) windows at a time (pg_popgen.hip: fst_slab, the loop in pg_fst_dev).  n = 450 pools: slab =
     662 windows; 665 one-locus windows make a second trip with w0 = 662 (window offsets wh + w0, host offset w0 * n^2).  The table
     is 665 * 450^2 doubles = 1.08 GB of host memory.  The oracle is asked for the first two windows and the five around the seam
     only (bit for bit); every window of the second slab must be finite and symmetric, and differ from the first slab's windows."""
@@ -169,7 +169,7 @@ def test_fst_window_table_second_slab(engine, oracle):
 
 
 # ---- one thread per (window, pool) -------------------------------------------------------------------------------------------
-# k_range_mean_1d (theta_pi, pg_popgen.hip:102-112, :441) and k_diversity_windows (:119-155, :331): n_windows * n threads in blocks of
+# k_range_mean_1d (theta_pi; launched in pi_tables of pg_popgen.hip) and k_diversity_windows (launched in diversity_tables): n_windows * n threads in blocks of
 # 256, the tail of the last block masked.  The engine returns host arrays of exactly n_windows x n, so a thread that ran past the end
 # would show as a wrong or missing value in the last window, not as an overwritten neighbour.
 # (n, n_windows, blocks)

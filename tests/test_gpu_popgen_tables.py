@@ -1,8 +1,9 @@
 """The tables forms of the popgen entry points (pg_pi_tables_dev, pg_fst_tables_dev, pg_watterson_tables_dev,
 pg_tajima_d_tables_dev): each leaves on the device exactly the bits that the host-output entry point returns -- which the tests
 beside this one hold against the oracle and the restatement -- at the shapes of test_gpu_popgen.py / test_gpu_popgen_diversity.py
-(n below and above one wave and no multiple of 64, overlapping windows, both counting modes).  pg_window_scatter_dev: the kept
-windows at their places, NaN elsewhere."""
+(n below and above one wave and no multiple of 64, overlapping windows, both counting modes).  The host forms are the tables forms
+plus a copy, so the mean across windows is also held against numpy over the table returned with it.  pg_window_scatter_dev: the
+kept windows at their places, NaN elsewhere."""
 import numpy as np
 import pytest
 import torch
@@ -21,8 +22,8 @@ def same_bits(dev, host):
     return dev.is_cuda and tuple(dev.shape) == host.shape and np.array_equal(bits(dev), bits(host))
 
 
-@pytest.mark.parametrize("n,L,win,slide,minl", [(12, 600, 400, 200, 2), (37, 1500, 1000, 500, 3), (200, 800, 5000, 2500, 10)])
-def test_tables_forms_return_the_host_forms_bits(engine, n, L, win, slide, minl):
+def tables_case(engine, n, L, win, slide, minl):
+    """the matrix, the loci's first columns, watterson_windows' five arrays and the pool sizes of one shape"""
     from poolgen_amd import Filter
     counts = make_counts(L, n, 23)
     rng = np.random.default_rng(2)
@@ -35,6 +36,12 @@ def test_tables_forms_return_the_host_forms_bits(engine, n, L, win, slide, minl)
     loci = cl[starts[:-1]]
     wh, wt, wc, wseed, wslot = engine.watterson_windows(chrom[loci], pos[loci], win, slide, minl)
     assert len(wh) > 3
+    return G, cov, starts, (wh, wt, wc, wseed, wslot), ps
+
+
+@pytest.mark.parametrize("n,L,win,slide,minl", [(12, 600, 400, 200, 2), (37, 1500, 1000, 500, 3), (200, 800, 5000, 2500, 10)])
+def test_tables_forms_return_the_host_forms_bits(engine, n, L, win, slide, minl):
+    G, cov, starts, (wh, wt, wc, wseed, wslot), ps = tables_case(engine, n, L, win, slide, minl)
     for dev, host in zip(engine.theta_pi_tables(G, cov, starts, wh, wt, n=n), engine.theta_pi(G, cov, starts, wh, wt, n=n)):
         assert same_bits(dev, host)
     fm, fw = engine.fst(G, cov, starts, wh, wt, n=n)
@@ -49,6 +56,36 @@ def test_tables_forms_return_the_host_forms_bits(engine, n, L, win, slide, minl)
         for dev, host in zip(got, want):
             assert same_bits(dev, host)
         assert (want[0] != 0).any()
+
+
+def is_mean_of(mean, win):
+    """mean [n] is mean_axis(Axis(0)) of win [nw x n] bit for bit: the windows added left to right from 0.0, one division;
+    a NaN equals a NaN whatever its payload"""
+    mean, win = mean.cpu().numpy(), win.cpu().numpy()
+    with np.errstate(all="ignore"):
+        s = np.zeros(win.shape[1])
+        for w in range(win.shape[0]):
+            s = s + win[w]
+        want = s / win.shape[0]
+    nan = np.isnan(want)
+    return mean.shape == want.shape and np.array_equal(np.isnan(mean), nan) and np.array_equal(bits(mean)[~nan], bits(want)[~nan])
+
+
+@pytest.mark.parametrize("n,L,win,slide,minl", [(12, 600, 400, 200, 2), (37, 1500, 1000, 500, 3)])
+def test_window_means_are_the_means_of_the_tables_returned(engine, n, L, win, slide, minl):
+    """The host forms copy the tables forms' results, so tables against host no longer holds two mean computations against
+    each other: the device mean (k_window_mean) against numpy over the very table returned with it, at all windows and at
+    a single one."""
+    G, cov, starts, windows, ps = tables_case(engine, n, L, win, slide, minl)
+    for nw in (len(windows[0]), 1):
+        wh, wt, wc, wseed, wslot = (x[:nw] for x in windows)
+        pw, pm = engine.theta_pi_tables(G, cov, starts, wh, wt, n=n)
+        assert pw.shape == (nw, n) and is_mean_of(pm, pw)
+        for count in ((wc, wseed, wslot), None):
+            tw, tm, seg = engine.theta_watterson_tables(G, starts, wh, wt, ps, count=count, n=n)
+            assert tw.shape == (nw, n) and is_mean_of(tm, tw)
+            d, dm, theta, pi = engine.tajima_d_tables(G, cov, starts, wh, wt, ps, count=count, n=n)
+            assert d.shape == (nw, n) and is_mean_of(dm, d)
 
 
 def test_fst_tables_without_windows_and_refusals(engine):

@@ -1,8 +1,10 @@
 """Throughput of fst / theta_pi / tajima_d / theta_watterson / gudmc on a resident synthetic matrix:
     python tools/bench_popgen.py [pools] [loci] [--rounds R] [--baseline-lib other/libpoolgen_hip.so]
 Every leg is warmed up once, then the legs alternate for R rounds in this one process and the median wall time of each is
-printed (one JSON line per leg).  --baseline-lib adds a `theta_pi_baseline` leg: pg_pi_dev of another build of the library
-(e.g. the previous commit's) on the same matrix and windows, loaded beside this one.
+printed (one JSON line per leg).  --baseline-lib adds two legs that call pg_pi_dev the same way, on the same matrix and windows
+with locus_col already an array (the Engine's `theta_pi` leg also converts it from a list on every call, which costs more
+than the kernels): `theta_pi_raw` of this build and `theta_pi_baseline` of another build of the library (e.g. the previous
+commit's), loaded beside this one.
 The gudmc legs: `gudmc_stage` = pg_gudmc_dev alone on the two tables already on the device, `gudmc` = tajima_d + fst + the stage
 (Engine.gudmc); one more line gives the histogram of the iterations the D and Fst fits took (10000 = the cap)."""
 import argparse
@@ -55,11 +57,14 @@ if args.baseline_lib:
     lc = np.ascontiguousarray(starts, dtype=np.int64)
     bwin, bmean = np.empty((len(wh), n)), np.empty(n)
 
-    def baseline():
-        assert base.pg_pi_dev(bctx, G.data_ptr(), cov.data_ptr(), G.shape[0], n, G.shape[1], lc.ctypes.data, nl, wh.ctypes.data,
-                              wt.ctypes.data, len(wh), bwin.ctypes.data, bmean.ctypes.data) == 0
-        return bwin, bmean
-    legs.insert(1, ("theta_pi_baseline", baseline))
+    def raw(lib, ctx):
+        def call():
+            assert lib.pg_pi_dev(ctx, G.data_ptr(), cov.data_ptr(), G.shape[0], n, G.shape[1], lc.ctypes.data, nl, wh.ctypes.data,
+                                 wt.ctypes.data, len(wh), bwin.ctypes.data, bmean.ctypes.data) == 0
+            return bwin, bmean
+        return call
+    baseline = raw(base, bctx)
+    legs[1:1] = [("theta_pi_raw", raw(eng._lib, eng._ctx)), ("theta_pi_baseline", baseline)]
     assert np.array_equal(baseline()[0], eng.theta_pi(G, cov, starts, wh, wt, n=n)[0])
 times = {name: [] for name, _ in legs}
 for name, fn in legs:
